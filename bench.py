@@ -11,8 +11,8 @@ Multi-GPU (SURVEY 8e, weak scaling): ONE global seeded batch of
 pairs_per_gpu x N pairs (mini_parallel_amd.synthetic.config_shard: pair i is
 the same whoever generates it); rank r scores shard_range(B, r, N) with no
 data-path collective; after the timed region the scores are gathered to every
-rank over RCCL (all_gather, the only collective of the path) and rank 0 checks
-the gathered scores against the oracle on a sample taken from every shard.
+rank over RCCL (all_gather, the only collective of the path) and, with
+--full, rank 0 checks them against the oracle on a sample from every shard.
 value = cells of all ranks / max-over-ranks wall time.
 
 Launch: ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``
@@ -20,10 +20,18 @@ Launch: ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``
 processes itself (children, before anything touches the GPU).  Fewer visible
 GPUs than N is an error (exit status 3), never a quiet n_gpus = 1.
 
-Extra fields: ``roofline`` (HBM, as north_star asks; algorithmic bytes per
-launch / average launch time from HIP events on the launch stream), ``valu``
-(the binding VALU-integer ceilings: the loop's instruction mix, SURVEY 8d's
-mapping-independent i32 ceiling and the lone-wave issue bound),
+A plain run (``bench.py --gpus N --steps K --warmup W``) sets up, warms up,
+times the K steps, gathers the scores, writes them if ``--dump-outputs DIR``
+is given (DIR/scores.npy, plus end_i.npy / end_j.npy when the scoring asks
+for the best cell; the inputs are seeded, so two builds compare output for
+output) and prints the line.  Its ``roofline`` (HBM, as north_star asks;
+algorithmic bytes per launch / average launch time from HIP events on the
+launch stream) and ``valu`` (the binding VALU-integer ceilings: the loop's
+instruction mix, SURVEY 8d's mapping-independent i32 ceiling and the
+lone-wave issue bound) come from the timed steps themselves.
+
+Everything that takes runs of its own is behind ``--full`` (null without
+it): ``pipelined_two_streams``,
 ``cpu_baseline`` (oracle restatement on rank 0's host cores, bounded sample,
 at every N), ``parity``, ``pcie_inclusive``, ``cut_windows_roofline`` and,
 at every N, ``configs_extra``: the other BASELINE configs, sharded over the
@@ -124,15 +132,24 @@ def parse(argv=None):
                     help="ranks (one per GPU); default 1, or WORLD_SIZE under torch.distributed.run")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the bench measures or checks: "
+                         "pipelined_two_streams, cpu_baseline and parity (--cpu-seconds), pcie_inclusive and "
+                         "cut_windows_roofline (--no-pcie), configs_extra (--extra-configs).  Without it a run "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (the gathered scores; end_i / end_j too when "
+                         "the scoring asks for the best cell) as DIR/<name>.npy, float32")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 5],
                     help="BASELINE config whose batch shape is timed (2 = the metric's)")
     ap.add_argument("--pairs", type=int, default=0, help="override pairs per GPU")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target CPU work for the cpu_baseline sample (0 disables)")
+                    help="--full: target CPU work for the cpu_baseline sample (0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-memory (PCIe) rate")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the host-memory (PCIe) rate")
     ap.add_argument("--extra-configs", default="3,4,5",
-                    help="other BASELINE configs timed as configs_extra keys at every N ('' or 'none' = none)")
+                    help="--full: other BASELINE configs timed as configs_extra keys at every N "
+                         "('' or 'none' = none)")
     ap.add_argument("--c3-pairs", type=int, default=0, help="config-3 leg: pairs per GPU (default 1M)")
     ap.add_argument("--c5-pairs", type=int, default=0, help="config-5 leg: pairs per GPU (default 100k)")
     ap.add_argument("--c4-reads-per-file", type=int, default=C4_READS_PER_FILE,
@@ -1434,7 +1451,8 @@ def _torch():
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
-    extras = [int(x) for x in args.extra_configs.split(",") if x.strip().isdigit()]
+    # the other BASELINE configs (and their lane sets) belong to --full
+    extras = [int(x) for x in args.extra_configs.split(",") if x.strip().isdigit()] if args.full else []
     if "WORLD_SIZE" in os.environ:
         world = int(os.environ["WORLD_SIZE"])
         if args.gpus is not None and args.gpus != world:
@@ -1544,12 +1562,15 @@ def main(argv=None):
     # Two batches in flight (an extra figure, not `value`).  Before any
     # all_gather: after one, kernels on the two streams stopped overlapping on
     # the box (tools/pipe_probe.py: 34.7 -> 42.7 us per step).
-    pipe = pipelined_steps(job, ctx, cfg, batch, scoring, work, stream2, args) if gpu else None
+    outs = (work.score, work.ei, work.ej) if gpu else None
+    if gpu and args.dump_outputs:
+        outs = tuple(t.clone() for t in outs)  # the last timed step's, before --full runs the step again
+    pipe = pipelined_steps(job, ctx, cfg, batch, scoring, work, stream2, args) if gpu and args.full else None
 
     # Final score/coordinate gather over RCCL (outside the timed region): the
     # only collective of the path.  Concatenated in rank order = global order.
     if gpu:
-        g_score, g_i, g_j = job.gather(work.score, work.ei, work.ej)
+        g_score, g_i, g_j = job.gather(*outs)
     else:
         (g_score,) = mdist.gather_results(torch.from_numpy(holder["s"]))
         g_i = g_j = None
@@ -1587,7 +1608,7 @@ def main(argv=None):
         if not gpu:
             parity = {"standin": True}
         else:
-            if args.cpu_seconds > 0:
+            if args.full and args.cpu_seconds > 0:
                 # the CPU baseline on rank 0's shard; parity of the whole
                 # gathered batch on a sample from every shard at N > 1
                 cpu, parity = cpu_baseline(args, batch, scoring, g_score[:batch.n_pairs],
@@ -1601,7 +1622,7 @@ def main(argv=None):
                                             + parity["all_shards"]["mismatches"])
             # PCIe-inclusive rates (never `value`): the same batch from host
             # memory, scores back on the host, rank 0.
-            if not args.no_pcie:
+            if args.full and not args.no_pcie:
                 pcie = pcie_rates(ctx, batch, scoring, cells, g_score[:batch.n_pairs])
                 cut = cut_roofline(ctx, dev, stream)
 
@@ -1657,6 +1678,11 @@ def main(argv=None):
         if not gpu:
             line["standin"] = True
             line["standin_scores"] = g_score.tolist() if g_score.size <= 100_000 else None
+        if args.dump_outputs:
+            arrays = {"scores": g_score}
+            if scoring.want_coords and g_i is not None:
+                arrays.update(end_i=g_i, end_j=g_j)
+            dump_outputs(args.dump_outputs, arrays)
         detail = write_detail(args, world, line)
         print(json.dumps(fit_line(compact_line(line, detail))), flush=True)
 
@@ -1689,6 +1715,27 @@ def prepare_datasets(args, extras, world):
                 m["segments"] = [{k: s[k] for k in ("segment", "reads", "score", "bytes")} for s in segs[:4]]
                 m["segments_total"] = len(segs)
                 m["_segment_rates"] = [(s["cells"], s["oracle_s"]) for s in segs]
+
+
+DUMP_LIMIT = 60_000_000  # bytes of array data one --dump-outputs may write in all (under 64 MB with headers)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the per-pair result arrays of the last timed step (all
+    ranks', in global pair order), each as d/<name>.npy in float32 -- exact:
+    scores stay below 2^24, coordinates below 2^15.  Arrays that together
+    pass DUMP_LIMIT are cut to one fixed seeded sample of the pairs, the same
+    in every array and every run, whose indices are written beside them
+    (sample_index.npy, float64)."""
+    os.makedirs(d, exist_ok=True)
+    n = len(arrays["scores"])
+    keep = DUMP_LIMIT // (4 * len(arrays) + 8)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        np.save(os.path.join(d, "sample_index.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a).astype(np.float32))
 
 
 # The driver keeps ~9.6 KB of a run's output tail (stdout, then stderr) and

@@ -66,7 +66,7 @@ def test_fit_line_enforces_the_limit_at_run_time():
 
 @pytest.mark.gpu
 def test_bench_json_line(tmp_path):
-    cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--pairs", "2000",
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--pairs", "2000",
            "--cpu-seconds", "1", "--no-pcie", "--c3-pairs", "20000", "--c5-pairs", "10000",
            "--c4-reads-per-file", "20000", "--c4-segment-reads", "10000", "--c4-pool", "3",
            "--c3-fastq-reads", "16000", "--c4-dir", str(tmp_path / "c4"),
@@ -157,6 +157,44 @@ def test_bench_json_line(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_the_timed_scores(tmp_path, oracle):
+    """The plain command (`--gpus 1 --steps K --warmup W`, no --full): the
+    contract's keys from K timed steps, none of the other measurements, and
+    --dump-outputs holding the timed path's scores of all 10,000 pairs --
+    bit-exact with the oracle on the seeded batch."""
+    import numpy as np
+    from mini_parallel_amd.synthetic import config_shard
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--c4-dir", str(tmp_path / "c4"), "--detail", str(tmp_path / "detail.json"),
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        assert line["metric"] == json.load(f)["metric"]
+    assert line["unit"] == "GCUPS" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert line["n_gpus"] == 1 and line["steps"] == 7 and line["warmup"] == 2
+    cells = line["config"]["cells_per_gpu_step"]
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - cells / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.05 * line["value"]
+    assert line["roofline"]["frac"] > 0 and 0 < line["valu"]["frac"] < 1.5
+    assert line["cpu_baseline"] is None and set(line["summary"]) == {"units", "c2"}
+    assert not (tmp_path / "c4").exists()
+    with open(tmp_path / "detail.json") as f:
+        d = json.load(f)
+    for k in ("configs_extra", "cpu_baseline", "pcie_inclusive", "cut_windows_roofline", "pipelined_two_streams"):
+        assert d[k] is None, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["scores.npy"]
+    got = np.load(tmp_path / "out" / "scores.npy")
+    b = config_shard(2, 0, 10_000)
+    want, _, _, _ = oracle.sw_batch_simd(b.reads, b.read_len, b.wins, b.win_len, threads=8, coords=False)
+    assert got.dtype == np.float32 and np.array_equal(got, want)
+    assert d["gathered_scores"]["score_sum"] == int(want.astype(np.int64).sum())
+
+
+@pytest.mark.gpu
 def test_bench_more_gpus_than_visible_fails():
     """On the 1-GPU box `bench.py --gpus 2` must exit non-zero with a message
     (never a quiet n_gpus = 1 line)."""
@@ -180,7 +218,7 @@ def test_bench_share_gpu_two_ranks(tmp_path):
     device).  Every leg must be bit-exact with results gathered in shard
     order, and the line must say it is oversubscribed (never a scaling point).
     Anchor: gpu.rs:117,125 (the reference uses devices[0] only)."""
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1",
            "--pairs", "2000", "--cpu-seconds", "1", "--no-pcie", "--c3-pairs", "20000", "--c5-pairs", "10000",
            "--c4-reads-per-file", "20000", "--c4-segment-reads", "10000", "--c4-pool", "3",
            "--c3-fastq-reads", "16000", "--c4-dir", str(tmp_path / "c4"), "--detail", str(tmp_path / "detail.json")]

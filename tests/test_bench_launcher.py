@@ -91,7 +91,47 @@ def test_single_rank_standin(tmp_path):
     _check(_json_line(r.stdout), 1)
 
 
-EXTRA = ["--cpu-standin", "--steps", "1", "--warmup", "0", "--pairs", "1000", "--cpu-seconds", "0", "--no-pcie",
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full a run times its steps and nothing else -- no other
+    config, no lane set, no baseline -- and --dump-outputs writes the gathered
+    scores of both ranks in global pair order as float32."""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--cpu-standin", "--steps", "2", "--warmup", "1",
+                        "--pairs", "3000", "--c4-dir", str(tmp_path / "c4"), "--detail", str(tmp_path / "d.json"),
+                        "--dump-outputs", str(out)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    _check(d, 2)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    for k in ("configs_extra", "cpu_baseline", "pcie_inclusive", "cut_windows_roofline", "pipelined_two_streams"):
+        assert d[k] is None, k
+    assert set(d["_line"]["summary"]) == {"units", "c2"} and not (tmp_path / "c4").exists()
+    assert sorted(p.name for p in out.iterdir()) == ["scores.npy"]
+    got = np.load(out / "scores.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, standin_scores(config_shard(2, 0, 6000)))
+
+
+def test_dump_outputs_samples_past_the_limit(tmp_path, monkeypatch):
+    """Arrays over the size limit are cut to one seeded sample of the pairs:
+    the same pairs in every array and in every run, indices beside them."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2000)
+    s = np.arange(1000, dtype=np.int32) * 3
+    arrays = {"scores": s, "end_i": (s % 150).astype(np.int16), "end_j": (s % 300).astype(np.int16)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    total = 0
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a[idx.astype(np.int64)])
+        assert np.array_equal(got, np.load(tmp_path / "b" / f"{name}.npy"))
+        total += got.nbytes
+    assert total + idx.nbytes <= 2000
+
+
+EXTRA = ["--full", "--cpu-standin", "--steps", "1", "--warmup", "0", "--pairs", "1000", "--cpu-seconds", "0", "--no-pcie",
          "--extra-configs", "3,4,5", "--c3-pairs", "1500", "--c5-pairs", "1300", "--c4-reads-per-file", "120",
          "--c4-segment-reads", "40", "--c4-pool", "5", "--c3-fastq-reads", "320"]
 
