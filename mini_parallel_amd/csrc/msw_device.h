@@ -142,10 +142,40 @@ struct PairMeta {
 #define MSW_PROBE_CONST_LEN 0
 #endif
 
-template <bool SPLIT, bool GEN>
+// Kernel arguments the prologue needs, read at kernel entry: the empty asm
+// takes them as scalar operands, so their loads are issued together and
+// waited on once, on a scalar cache that is cold at every launch, instead of
+// at each place of first use behind the vector loads.
+__device__ __forceinline__ void pin_args(const SwParams& p) {
+    asm volatile("" ::"s"(p.reads), "s"(p.wins), "s"(p.read_len), "s"(p.win_len), "s"(p.order), "s"(p.slot_lens),
+                 "s"(p.read_stride), "s"(p.win_stride), "s"(p.n_slots), "s"(p.lds_stride), "s"(p.code_shift),
+                 "s"(p.win_vec), "s"(p.slot_base), "s"(p.group_lanes), "s"(p.groups), "s"(p.f16_ok), "s"(p.f16_hi),
+                 "s"(p.f16_ngap2), "s"(p.out_by_slot), "s"(p.out_slot_base), "s"(p.score), "s"(p.match2),
+                 "s"(p.delta2), "s"(p.gap2), "s"(p.open_ext2), "s"(p.bias2), "s"(p.f16_noe2), "s"(p.end_i),
+                 "s"(p.end_j));
+}
+
+// Lengths of padding slots (and of idle lanes) are masked to 0; an empty
+// genome window reads the genome's start.
+template <bool GEN>
+__device__ __forceinline__ void mask_meta(PairMeta& q) {
+    q.ma = q.va ? q.ma : 0;
+    q.mb = q.vb ? q.mb : 0;
+    q.na = q.va ? q.na : 0;
+    q.nb = q.vb ? q.nb : 0;
+    if constexpr (GEN) {
+        q.sa = q.na > 0 ? q.sa : 0;
+        q.sb = q.nb > 0 ? q.sb : 0;
+    }
+}
+
+// Pair indices and the loads of the pair lengths, unmasked (mask_meta).
+// IDENT: identity slot order and per-pair lengths (p.order and p.slot_lens
+// null) known at compile time -- the indices come from the slot number alone,
+// so nothing issued after the length loads has to wait for them.
+template <bool SPLIT, bool GEN, bool IDENT>
 __device__ __forceinline__ PairMeta load_meta(const SwParams& p, int g, uint32_t block, bool active) {
-    // Branch-free: clamped indices keep every load legal (n_slots >= 1), the
-    // lengths of padding slots (and of idle lanes) are masked to 0 afterwards.
+    // Branch-free: clamped indices keep every load legal (n_slots >= 1).
     PairMeta q;
     const uint32_t slot_a = block * pairs_per_wave(SPLIT, p.groups) + (SPLIT ? g : 2u * g);
     const uint32_t slot_b = SPLIT ? slot_a : slot_a + 1;
@@ -153,39 +183,37 @@ __device__ __forceinline__ PairMeta load_meta(const SwParams& p, int g, uint32_t
     const uint32_t sa = min(slot_a, last), sb = min(slot_b, last);
     q.va = active && slot_a < p.n_slots;
     q.vb = active && slot_b < p.n_slots;
-    q.pa = p.order ? p.order[sa] : p.slot_base + sa;
-    q.pb = SPLIT ? q.pa : (p.order ? p.order[sb] : p.slot_base + sb);
+    if constexpr (IDENT) {
+        q.pa = p.slot_base + sa;
+        q.pb = SPLIT ? q.pa : p.slot_base + sb;
+    } else {
+        q.pa = p.order ? p.order[sa] : p.slot_base + sa;
+        q.pb = SPLIT ? q.pa : (p.order ? p.order[sb] : p.slot_base + sb);
+    }
     // Slot-ordered results (length-bucketed batches): a wave's pairs are
     // scattered over the batch, its slots are consecutive -- the stores stay
     // contiguous and the host / a gather pass restores pair order.
     q.oa = p.out_by_slot ? p.out_slot_base + sa : q.pa;
     q.ob = p.out_by_slot ? p.out_slot_base + sb : q.pb;
-    int ma, na, mb, nb;
-    if (p.slot_lens) {  // lengths in slot order (planned batches): contiguous, not gathered
+    if (!IDENT && p.slot_lens) {  // lengths in slot order (planned batches): contiguous, not gathered
         const uint32_t la = p.slot_lens[p.out_slot_base + sa];
         const uint32_t lb = SPLIT ? la : p.slot_lens[p.out_slot_base + sb];
-        ma = (int)(la & 0xFFFFu);
-        na = (int)(la >> 16);
-        mb = (int)(lb & 0xFFFFu);
-        nb = (int)(lb >> 16);
+        q.ma = (int)(la & 0xFFFFu);
+        q.na = (int)(la >> 16);
+        q.mb = (int)(lb & 0xFFFFu);
+        q.nb = (int)(lb >> 16);
     } else if (MSW_PROBE_CONST_LEN) {
-        ma = mb = 150;
-        na = nb = 300;
+        q.ma = q.mb = 150;
+        q.na = q.nb = 300;
     } else {
-        ma = p.read_len[q.pa];
-        na = p.win_len[q.pa];
-        mb = SPLIT ? ma : (int)p.read_len[q.pb];
-        nb = SPLIT ? na : (int)p.win_len[q.pb];
+        q.ma = p.read_len[q.pa];
+        q.na = p.win_len[q.pa];
+        q.mb = SPLIT ? q.ma : (int)p.read_len[q.pb];
+        q.nb = SPLIT ? q.na : (int)p.win_len[q.pb];
     }
-    q.ma = q.va ? ma : 0;
-    q.mb = q.vb ? mb : 0;
-    q.na = q.va ? na : 0;
-    q.nb = q.vb ? nb : 0;
-    if constexpr (GEN) {  // loaded beside the lengths (same round trip); an empty window reads the genome's start
-        const int64_t sa = p.win_pos[q.pa];
-        const int64_t sb = SPLIT ? sa : p.win_pos[q.pb];
-        q.sa = q.na > 0 ? sa : 0;
-        q.sb = q.nb > 0 ? sb : 0;
+    if constexpr (GEN) {  // loaded beside the lengths (same round trip)
+        q.sa = p.win_pos[q.pa];
+        q.sb = SPLIT ? q.sa : p.win_pos[q.pb];
     }
     return q;
 }
@@ -513,12 +541,14 @@ __device__ __forceinline__ uint32_t win_selector(uint32_t word, uint32_t shift) 
 }
 
 // A read byte outside A/C/G/T (N, lower case, ...) can never equal a window
-// byte of a fast-path wave, so its row (like a padding row) is all mismatch.
-__device__ __forceinline__ uint32_t row_table(uint32_t v, uint32_t shift, uint32_t mis4, uint32_t match_hi) {
-    const uint32_t b = v >> shift;
-    if ((v & kReadSentinel) || !is_acgt(b)) return mis4;
-    const uint32_t sh = 8u * base_class(b);
-    return (mis4 & ~(0xFFu << sh)) | (match_hi << sh);
+// byte of a fast-path wave, so its row (like a padding row, in_read false) is
+// all mismatch.  Straight from the read byte, branch-free: the class's table
+// byte is flipped from mismatch to match (d = their xor) only if the byte is
+// that class's own base.
+__device__ __forceinline__ uint32_t row_table(uint32_t b, bool in_read, uint32_t mis4, uint32_t d) {
+    const uint32_t sh = ((b << 2) ^ (b << 1)) & 0x18u;  // 8 * base_class(b)
+    const bool hit = in_read && ((0x54474341u >> sh) & 0xFFu) == b;
+    return mis4 ^ ((hit ? d : 0u) << sh);
 }
 
 // Checks this lane's share of the group's staged window stream; returns true
@@ -559,19 +589,24 @@ struct WinRound {
     uint32_t prev[kRound];  // split: the byte before each chunk
 };
 
-template <bool SPLIT, bool GEN>
+// CLAMP: the last chunk loaded per pair is the end of ITS window, which needs
+// the pair's (masked) length before the loads can go out.
+template <bool SPLIT, bool GEN, bool CLAMP>
 __device__ __forceinline__ void load_round(const SwParams& p, const PairMeta& q, int k0, int lg, int G,
                                            WinRound& w) {
     const uint8_t* wa = win_row<GEN>(p, q.pa, q.sa);
     const uint8_t* wb = win_row<GEN>(p, q.pb, q.sb);
-    // last chunk to load per pair: the end of ITS window (not the launch's
-    // longest, which a length bucket's short windows would over-read by up to
-    // a 128-byte line each), and never past the row or the stream -- lanes
-    // past it re-load that chunk (the same line, coalesced)
+    // last chunk to load: never past the row or the stream -- lanes past it
+    // re-load that chunk (the same line, coalesced).  The length-bucketed grid
+    // and the genome instances also stop at the end of each pair's own window
+    // (not the launch's longest, which a length bucket's short windows would
+    // over-read by up to a 128-byte line each; a genome window may end at the
+    // genome's last byte); every other launch clamps by the row alone, so its
+    // window loads go out without waiting for the lengths.
     const int stream_top = (int)((p.lds_stride - kLead) >> 4);
-    const int top = (GEN ? stream_top : min((int)(p.win_stride >> 4), stream_top)) - 1;
-    const int top_a = max(min(top, ((q.na + 15) >> 4) - 1), 0);
-    const int top_b = max(min(top, ((q.nb + 15) >> 4) - 1), 0);
+    const int top = max((GEN ? stream_top : min((int)(p.win_stride >> 4), stream_top)) - 1, 0);
+    const int top_a = CLAMP ? max(min(top, ((q.na + 15) >> 4) - 1), 0) : top;
+    const int top_b = CLAMP ? max(min(top, ((q.nb + 15) >> 4) - 1), 0) : top;
     const int last = win_last<GEN>(p, q.na);
 #pragma unroll
     for (int u = 0; u < kRound; ++u) {
@@ -678,7 +713,9 @@ constexpr bool explicit_sched(bool affine, bool coords) { return !affine || coor
 constexpr int step_unroll(bool /*affine*/, bool coords) { return coords ? 2 : 4; }
 constexpr int perm_lead(bool affine, bool coords) { return !affine && !coords ? 2 : 0; }
 
-template <int KR, bool AFFINE, bool COORDS, bool SPLIT, bool GEN = false>
+// PLAN: a block of the length-bucketed grid (sw_multi_kernel): p.order is set,
+// and the window loads stop at each pair's own window end (load_round).
+template <int KR, bool AFFINE, bool COORDS, bool SPLIT, bool GEN = false, bool PLAN = false>
 __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint32_t* lds, uint64_t& t_loop) {
     const int lane = threadIdx.x;
     const int G = (int)p.group_lanes;
@@ -692,17 +729,33 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
     // move folds into one v_and_b32_dpp instead of becoming a v_cndmask.
     uint32_t top_mask = lg == 0 ? 0u : ~0u;
     asm volatile("" : "+v"(top_mask));
-    const PairMeta q = load_meta<SPLIT, GEN>(p, g, block, active);
-    // Staging.  The lengths, the read bytes and the first round of window
-    // chunks are all in flight before anything waits on the lengths (one
-    // memory round trip); 16-byte aligned batches under an f16 scheme stage
-    // selectors directly and fall back to integer codes only if some window
-    // byte of the wave is not A/C/G/T.
-    uint32_t rb_a[KR], rb_b[KR];
-    load_read_bytes<KR, SPLIT>(p, q.pa, q.pb, lg, rb_a, rb_b);
+    // Staging.  With the identity slot order (no p.order, no p.slot_lens) the
+    // length loads, the read-byte loads and the first round of window chunks
+    // are issued back to back and nothing waits before the last of them: one
+    // memory round trip.  An ordered launch first waits for its pair indices
+    // (p.order), the length-bucketed grid (PLAN) and the genome instances
+    // also for the lengths resp. window positions their window loads are
+    // clamped by; their read bytes still go out with the lengths.  16-byte
+    // aligned batches under an f16 scheme stage selectors directly and fall
+    // back to integer codes only if some window byte of the wave is not
+    // A/C/G/T.
+    constexpr bool kClamp = PLAN || GEN;
     const bool try_fast = p.f16_ok && p.win_vec;
+    PairMeta q;
+    uint32_t rb_a[KR], rb_b[KR];
     WinRound w0;
-    if (try_fast) load_round<SPLIT, GEN>(p, q, 0, lg, G, w0);
+    auto early = [&](auto ident) __attribute__((always_inline)) {
+        q = load_meta<SPLIT, GEN, decltype(ident)::value>(p, g, block, active);
+        load_read_bytes<KR, SPLIT>(p, q.pa, q.pb, lg, rb_a, rb_b);
+        if constexpr (kClamp) mask_meta<GEN>(q);
+        if (try_fast) load_round<SPLIT, GEN, kClamp>(p, q, 0, lg, G, w0);
+        // keeps the two variants' loads apart: merged behind the join, their
+        // addresses would wait for the ordered variant's index loads again
+        asm volatile("");
+    };
+    if (!PLAN && __builtin_expect(!p.order && !p.slot_lens, 1)) early(std::true_type{});
+    else early(std::false_type{});
+    if constexpr (!kClamp) mask_meta<GEN>(q);
     const int skew = SPLIT ? 2 * (G - 1) + 1 : G - 1;
     // wavefront steps, rounded up to a multiple of the steps per iteration
     // (the explicitly scheduled f16 loops of the pairs layout run four steps
@@ -710,8 +763,6 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
     constexpr int kUnroll = (!SPLIT && explicit_sched(AFFINE, COORDS)) ? 4 : step_unroll(AFFINE, COORDS);
     const int steps = (wave_max_nonneg(max(q.na, q.nb)) + skew + kUnroll - 1) & ~(kUnroll - 1);
     uint32_t* stream = lds + g * p.lds_stride;
-    uint32_t rc[KR];
-    read_codes<KR, SPLIT>(p, q, lg, rb_a, rb_b, rc);
     bool fast;
     if (try_fast) {
         const int nch = (int)((p.lds_stride - kLead) >> 4);  // chunks of the whole stream
@@ -721,7 +772,7 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
             bad = sel_round<SPLIT>(q, stream, 0, nch, lg, G, w0);
             for (int k0 = kRound * G; k0 < nch; k0 += kRound * G) {  // windows past 16 kRound G columns
                 WinRound w;
-                load_round<SPLIT, GEN>(p, q, k0, lg, G, w);
+                load_round<SPLIT, GEN, kClamp>(p, q, k0, lg, G, w);
                 bad |= sel_round<SPLIT>(q, stream, k0, nch, lg, G, w);
             }
         }
@@ -742,6 +793,12 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
     const uint32_t nj_lane = (uint32_t)(0xFFFF + (SPLIT ? 2 * lg : lg));
     const uint32_t lds_wp = (uint32_t)(uintptr_t)wp;  // LDS byte address of wp[0]
 
+    // First step of every DP loop below: an opaque scalar zero.  As the plain
+    // constant it shares one register with the zeros the loop's vector values
+    // start from, and the step counter then lives in a VGPR (a v_add and a
+    // v_cmp per iteration instead of their scalar forms).
+    int t_first = 0;
+    asm("" : "+s"(t_first));
     // The whole DP for one arithmetic domain: F16 = ACGT table lookups on f16
     // values, else xor/min on the byte codes with u16 integer values.
     auto run = [&](auto f16_tag) __attribute__((always_inline)) {
@@ -753,14 +810,20 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
         const uint32_t og2 = oe2 - bias2;                       // integer affine: go + ge
         // f16 path constants: -gap (linear) / -ge (affine), -(go + ge)
         const uint32_t nge = p.f16_ngap2, noe = p.f16_noe2;
-        uint32_t tab_lo[F16 ? KR : 1], tab_hi[F16 ? KR : 1];
+        // f16: the rows' tables, built from the read bytes; the integer
+        // codes are formed on the integer path only
+        uint32_t tab_lo[F16 ? KR : 1], tab_hi[F16 ? KR : 1], rc[F16 ? 1 : KR];
         if constexpr (F16) {
-            const uint32_t mis4 = (p.f16_hi >> 8) * 0x01010101u, match_hi = p.f16_hi & 0xFFu;
+            const uint32_t mis4 = (p.f16_hi >> 8) * 0x01010101u, d = (p.f16_hi ^ (p.f16_hi >> 8)) & 0xFFu;
 #pragma unroll
             for (int r = 0; r < KR; ++r) {
-                tab_lo[r] = row_table(rc[r] & 0xFFFFu, p.code_shift, mis4, match_hi);
-                tab_hi[r] = row_table(rc[r] >> 16, p.code_shift, mis4, match_hi);
+                const int ia = SPLIT ? lg * 2 * KR + r : lg * KR + r;
+                const int ib = SPLIT ? ia + KR : ia;
+                tab_lo[r] = row_table(rb_a[r], ia < q.ma, mis4, d);
+                tab_hi[r] = row_table(rb_b[r], ib < q.mb, mis4, d);
             }
+        } else {
+            read_codes<KR, SPLIT>(p, q, lg, rb_a, rb_b, rc);
         }
         // F16: the substitution score s; integer: the penalty a = match - s.
         auto sub = [&](int r, uint32_t w) __attribute__((always_inline)) -> uint32_t {
@@ -944,7 +1007,7 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
             uint2 wa = make_uint2(wp[1], wp[2]);
             uint2 wb;
             asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wb) : "v"(lds_wp));
-            for (int t = 0; t < steps; t += 4) {
+            for (int t = t_first; t < steps; t += 4) {
                 const uint32_t base = lds_wp + 4u * (uint32_t)t;
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wb));
                 sstep(t, wa.x, wa.y, t1a, t1b, P0{});
@@ -1075,7 +1138,7 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
             uint2 wa = make_uint2(wp[1], wp[2]);
             uint2 wb;
             asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wb) : "v"(lds_wp));
-            for (int t = 0; t < steps; t += 4) {
+            for (int t = t_first; t < steps; t += 4) {
                 const uint32_t base = lds_wp + 4u * (uint32_t)t;
                 step(t, wa.x, t1a, t1b, P0{});
                 step(t + 1, wa.y, t1b, t1a, P1{});
@@ -1091,7 +1154,7 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
             uint32_t w1 = wp[1], w2 = wp[2];
             uint2 wn;
             asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wn) : "v"(lds_wp));
-            for (int t = 0; t < steps; t += 2) {
+            for (int t = t_first; t < steps; t += 2) {
                 step(t, w1, t1a, t1b, P0{});
                 step(t + 1, w2, t1b, t1a, P1{});
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wn));
@@ -1167,6 +1230,7 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb) {
 template <int KR, bool AFFINE, bool COORDS, bool SPLIT, bool GEN = false>
 __global__ __launch_bounds__(64) void sw_kernel(SwParams p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    pin_args(p);
     const WaveClock wc = trace_begin(p);
     uint64_t t_loop = 0;
     // identity block order: the XCD-grouped map below cut config 2's fetched
@@ -1184,6 +1248,7 @@ __global__ __launch_bounds__(64) void sw_kernel(SwParams p) {
 template <int KRP, bool AFFINE, bool COORDS>
 __global__ __launch_bounds__(64) void sw_mixed_kernel(SwParams p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    pin_args(p);
     const WaveClock wc = trace_begin(p);
     uint64_t t_loop = 0;
     if (blockIdx.x < p.pairs_blocks) {
@@ -1210,7 +1275,7 @@ template <int KR, bool AFFINE, bool COORDS>
 __device__ __forceinline__ void multi_body(const SwParams& q, uint32_t blk, uint32_t* lds) {
     const WaveClock wc = trace_begin(q);
     uint64_t t_loop = 0;
-    const bool fast = sw_body<KR, AFFINE, COORDS, false>(q, blk, lds, t_loop);
+    const bool fast = sw_body<KR, AFFINE, COORDS, false, false, true>(q, blk, lds, t_loop);
     trace_end(q, wc, fast, false, KR, t_loop);
 }
 
@@ -1220,6 +1285,7 @@ __device__ __forceinline__ void multi_body(const SwParams& q, uint32_t blk, uint
 template <bool AFFINE, bool COORDS, bool WIDE = false>
 __global__ __launch_bounds__(64) void sw_multi_kernel(SwParams p, MultiTable t) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    pin_args(p);
     const uint32_t lb = xcd_block<4>(blockIdx.x, gridDim.x);
     uint32_t b = 0;
     while (b + 1 < t.n_buckets && lb >= t.block_end[b]) ++b;

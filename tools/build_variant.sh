@@ -10,7 +10,7 @@ mkdir -p "$OUT/o_$NAME"
 make -s msw_runtime.o msw_fastq.o msw_gfastq.o >/dev/null
 pids=()
 for f in msw_kernels.hip msw_launch_*.hip msw_long.hip msw_inflate.hip msw_parse.hip; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include "$@" -c "$f" \
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -falign-loops=32 --offload-arch=gfx950 -I../../include "$@" -c "$f" \
       -o "$OUT/o_$NAME/${f%.hip}.o" &
   pids+=($!)
 done

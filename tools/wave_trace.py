@@ -118,22 +118,26 @@ def main():
     ej = torch.zeros(b.n_pairs, dtype=torch.int16, device=dev)
     sc = Scoring(gap_open=3 if args.affine else 0, gap_extend=1 if args.affine else 2,
                  affine=args.affine, want_coords=args.coords)
+    # the library reads MSW_WAVE_TRACE once, when a context is made: every
+    # launch of this context is traced (the warm ones too), the last three
+    # records are reported
+    fd, path = tempfile.mkstemp(suffix=".trace")
+    os.close(fd)
+    os.environ["MSW_WAVE_TRACE"] = path
     ctx = Context(0)
+    os.environ.pop("MSW_WAVE_TRACE")
     stream = torch.cuda.Stream(dev)
     step = ctx.prepare_device_launch(reads.data_ptr(), rl.data_ptr(), wins.data_ptr(), wl.data_ptr(),
                                      b.reads.shape[1], b.wins.shape[1], b.n_pairs, score.data_ptr(),
                                      int(b.read_len.max()), int(b.win_len.max()), sc,
                                      ei.data_ptr(), ej.data_ptr(), stream.cuda_stream)
     for _ in range(5):
-        step()  # warm (untraced)
+        step()  # warm
     torch.cuda.synchronize()
-    fd, path = tempfile.mkstemp(suffix=".trace")
-    os.close(fd)
-    os.environ["MSW_WAVE_TRACE"] = path
     for _ in range(3):
         step()
-    os.environ.pop("MSW_WAVE_TRACE")
-    recs = decode(path)
+    torch.cuda.synchronize()
+    recs = decode(path)[-3:]
     os.unlink(path)
     res = []
     for lay, g, pb, blk in recs:
