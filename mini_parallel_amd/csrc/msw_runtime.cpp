@@ -180,8 +180,9 @@ bool f16_fits(const Scheme& s, uint32_t max_m, uint32_t max_n) {
 }
 
 // Length limits: pairs up to kMaxReadLen x kMaxWinLen run on the packed
-// 16-bit kernels (every cell value, <= match * (257 + 1) + bias < 0x7C00, is
-// a finite non-negative f16 bit pattern for v_pk_maximum3_f16); longer reads
+// 16-bit kernels (every cell value, <= match * (384 + 1) + bias <= 64 * 385 +
+// 1280 = 25920 < 0x7C00, is a finite non-negative f16 bit pattern for
+// v_pk_maximum3_f16; tests/test_gpu_ranges.py reaches it); longer reads
 // or windows, up to kMaxLongLen (the i16 coordinates), on the i32 long-pair
 // kernel (msw_long.hip).
 int check_bounds(const Scheme& s, uint32_t max_m, uint32_t max_n) {
