@@ -98,6 +98,23 @@ __device__ __forceinline__ uint32_t track_max3(uint32_t best, uint32_t a, uint32
 __device__ __forceinline__ uint32_t shr1_group(uint32_t src, uint32_t top_mask) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x138, 0xF, 0xF, true) & top_mask;
 }
+// The DPP move alone, for a caller that applies top_mask itself.
+__device__ __forceinline__ uint32_t shr1_wave(uint32_t src) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x138, 0xF, 0xF, true);
+}
+
+// Best-cell keys of the explicitly scheduled loops: (0xFFFF - column) & 0xFFFF
+// of step K of an iteration, from the iteration's running value.  Both ops in
+// their 8-byte encodings (VOP3 add with an inline constant, and with a literal):
+// a lone 4-byte one would put every 8-byte instruction behind it at 4 mod 8.
+// One asm statement: hipcc puts an s_nop between two dependent ones.
+template <int K>
+__device__ __forceinline__ uint32_t nj_step(uint32_t njv) {
+    uint32_t d;
+    if constexpr (K > 0) asm("v_add_u32_e64 %0, %1, %2\n\tv_and_b32_e32 %0, 0xffff, %0" : "=&v"(d) : "v"(njv), "n"(-K));
+    else asm("v_and_b32_e32 %0, 0xffff, %1" : "=v"(d) : "v"(njv));
+    return d;
+}
 
 // Packed (H + match): a full-rate v_add_u32 suffices -- each u16 half stays
 // below 0x7C00 + 64, so no carry crosses into the high half.
@@ -845,6 +862,10 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
         uint32_t t1a[KR], t1b[KR];
         using P0 = std::integral_constant<int, 0>;
         using P1 = std::integral_constant<int, 1>;
+        using S0 = P0;
+        using S1 = P1;
+        using S2 = std::integral_constant<int, 2>;
+        using S3 = std::integral_constant<int, 3>;
         if constexpr (F16 && !SPLIT && explicit_sched(AFFINE, COORDS)) {
             // The f16 loops of the pairs layout (every config's main kernel),
             // explicitly scheduled.  Every instruction is pinned by a
@@ -873,13 +894,40 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
 #pragma unroll
                 for (int r = 0; r < KR; ++r) t1a[r] = sub(r, w0);   // H_diag = 0
             }
-            uint32_t an0 = sub(0, wp[1]);  // row 0's substitution at step 1's column
+            // Alignment (kPaired: the linear kinds; the affine loops are as hipcc
+            // lays them out).  The loop is all 8-byte encodings but for a few
+            // 4-byte ones, and every 8-byte instruction behind a lone 4-byte one
+            // straddles an 8-byte boundary until the next 4-byte one; a lone wave
+            // pays for each.  So the 4-byte ones stand in pairs:
+            // the mid-loop wait with the LDS address add (a running address, kept
+            // by hand so the add has a fixed place), the step counter's add with
+            // its compare (nothing moves across the barrier behind the last
+            // read), the top-mask and of the last step's hand-off with the first
+            // wait; the column index of the best-cell keys takes 8-byte
+            // encodings (nj_step).  tools/loop_align.py reports the result,
+            // tests/test_loop_alignment.py holds it.
+            constexpr bool kPaired = !AFFINE;
+            uint2 wa, wb;
+            if constexpr (kPaired) {
+                // the words of steps 1..4, read like the loop's own (nothing of them
+                // is pending in hipcc's view, so it puts no wait of its own into the loop)
+                asm volatile("ds_read2_b32 %0, %1 offset0:1 offset1:2" : "=v"(wa) : "v"(lds_wp));
+                asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wb) : "v"(lds_wp));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wa));
+            } else {
+                wa = make_uint2(wp[1], wp[2]);
+                asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wb) : "v"(lds_wp));
+            }
+            uint32_t an0 = sub(0, wa.x);  // row 0's substitution at step 1's column
             uint32_t hpend = 0u, hkm2 = 0u;
-            uint32_t hu = shr1_group(h_bot, top_mask);                  // H of the row above
+            uint32_t njv = nj_lane - (uint32_t)t_first;                 // kPaired: 0xFFFF - column of step t (best cell)
+            // H of the row above (kPaired: before top_mask in front of an iteration)
+            uint32_t hu = kPaired ? 0u : shr1_group(h_bot, top_mask);
             uint32_t fu = AFFINE ? shr1_group(f_bot, top_mask) : 0u;   // F of the row above (affine)
+            // t = the iteration's first step, k = the step's place in it (0..3)
             auto sstep = [&](int t, uint32_t w1, uint32_t w2, const uint32_t (&t1)[KR], uint32_t (&t1n)[KR],
-                             auto parity) __attribute__((always_inline)) {
-                constexpr int kParity = decltype(parity)::value;
+                             auto k) __attribute__((always_inline)) {
+                constexpr int kStep = decltype(k)::value, kParity = kStep & 1;
                 // linear: up = E of the row above; affine: fsub = F_up - ge (the
                 // row's F needs G_up from the previous row's clamp), e_next = the
                 // next row's E = max(E_left - ge, G_left), both formed a row ahead
@@ -903,7 +951,8 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
                 }
                 uint32_t nja = 0u;
                 if constexpr (COORDS) {
-                    nja = (nj_lane - (uint32_t)t) & 0xFFFFu;
+                    if constexpr (kPaired) nja = nj_step<kStep>(njv);
+                    else nja = (nj_lane - (uint32_t)(t + kStep)) & 0xFFFFu;
                     MSW_SB;
                 } else if constexpr (KR & 1) {
                     // score fold left over from the previous step: odd KR pairs
@@ -1001,22 +1050,34 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
                 }
                 h_bot = hh[KR - 1];
                 if constexpr (!COORDS && (KR & 1) == 0) hkm2 = hh[KR - 2];
-                hu = shr1_group(h_bot, top_mask);
+                // an iteration's last hand-off is masked at the next one's start,
+                // beside its wait (hipcc splits the pair across the back edge anyway)
+                if constexpr (kPaired && kStep == 3) hu = shr1_wave(h_bot);
+                else hu = shr1_group(h_bot, top_mask);
                 MSW_SB;
             };
-            uint2 wa = make_uint2(wp[1], wp[2]);
-            uint2 wb;
-            asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wb) : "v"(lds_wp));
+            uint32_t addr = lds_wp;  // kPaired: LDS byte address of wp[t], of wp[t + 4] behind the mid-loop add
             for (int t = t_first; t < steps; t += 4) {
                 const uint32_t base = lds_wp + 4u * (uint32_t)t;
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wb));
-                sstep(t, wa.x, wa.y, t1a, t1b, P0{});
-                sstep(t + 1, wa.y, wb.x, t1b, t1a, P1{});
-                asm volatile("ds_read2_b32 %0, %1 offset0:5 offset1:6" : "=v"(wa) : "v"(base));
-                sstep(t + 2, wb.x, wb.y, t1a, t1b, P0{});
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wa));
-                sstep(t + 3, wb.y, wa.x, t1b, t1a, P1{});
-                asm volatile("ds_read2_b32 %0, %1 offset0:7 offset1:8" : "=v"(wb) : "v"(base));
+                if constexpr (kPaired) {
+                    hu &= top_mask;  // not in the asm: hipcc would put an s_nop in front of its consumer
+                    MSW_SB;
+                }
+                sstep(t, wa.x, wa.y, t1a, t1b, S0{});
+                sstep(t, wa.y, wb.x, t1b, t1a, S1{});
+                asm volatile("ds_read2_b32 %0, %1 offset0:5 offset1:6" : "=v"(wa) : "v"(kPaired ? addr : base));
+                sstep(t, wb.x, wb.y, t1a, t1b, S2{});
+                if constexpr (kPaired) asm volatile("s_waitcnt lgkmcnt(0)\n\tv_add_u32_e32 %1, 16, %1" : "+v"(wa), "+v"(addr));
+                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wa));
+                sstep(t, wb.y, wa.x, t1b, t1a, S3{});
+                if constexpr (kPaired) {
+                    asm volatile("ds_read2_b32 %0, %1 offset0:3 offset1:4" : "=v"(wb) : "v"(addr));
+                    if constexpr (COORDS) asm volatile("v_add_u32_e64 %0, %0, -4" : "+v"(njv));
+                    MSW_SB;
+                } else {
+                    asm volatile("ds_read2_b32 %0, %1 offset0:7 offset1:8" : "=v"(wb) : "v"(base));
+                }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wb));
             // the score pair still pending after the last (odd) step
