@@ -139,6 +139,61 @@ int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
                            msw_out_t* out, uint32_t max_read_len, uint32_t max_win_len,
                            void* stream);
 
+/* Traceback: the alignment itself -- its first cell and its CIGAR.
+ *
+ * The canonical alignment (unique, so a second implementation can be
+ * compared op for op):
+ *  - it ends at the best cell as defined above (max score, smallest i, then
+ *    smallest j); H, E, F are the recurrence of the scorer, byte-equality
+ *    substitution s(i,j), H[-1][*] = H[*][-1] = 0, E = F = -inf outside;
+ *  - the walk starts at (end_i, end_j) in state H.
+ *    Linear, at (i, j):  H == 0 -> stop (the cell is not part of the
+ *    alignment); H == H[i-1][j-1] + s(i,j) -> emit M, go to (i-1, j-1);
+ *    else H == H[i-1][j] - gap -> emit I (a read base against nothing), go to
+ *    (i-1, j); else emit D, go to (i, j-1).
+ *    Affine (goe = gap_open + gap_extend), state H:  H == 0 -> stop;
+ *    H == H[i-1][j-1] + s -> emit M, go to (i-1, j-1); else H == F[i][j] ->
+ *    state F at the same cell; else state E at the same cell.
+ *    State F: emit I, go to (i-1, j); the next state is H if
+ *    F[i][j] == H[i-1][j] - goe (opening preferred), else F.
+ *    State E: emit D, go to (i, j-1); the next state is H if
+ *    E[i][j] == H[i][j-1] - goe, else E.
+ *    Precedence: diagonal > I > D, open > extend.
+ *  - start_i / start_j: the cell of the last M emitted (the first aligned
+ *    cell); the CIGAR: the ops in forward order, run-length merged, encoded
+ *    like BAM as len << 4 | op with M = 0, I = 1, D = 2.  Score 0 or an empty
+ *    pair: start (-1, -1) and 0 ops.  The first and last ops are M, adjacent
+ *    ops differ, every length is >= 1.
+ *
+ * Range: traceback supports the packed kernels' range only, read <= 384 and
+ * window <= 4096; a longer pair (or bound) in a traceback call returns
+ * MSW_E_RANGE (scoring such pairs stays available through the calls above).
+ *
+ * Overflow: when a pair needs more than cigar_stride ops, n_cigar[p] still
+ * holds the count it needs, its cigar row is unspecified (nothing is written
+ * past the row), and start_i / start_j are valid. */
+typedef struct {
+    int16_t* start_i;      /* first aligned read base, -1 when score == 0 */
+    int16_t* start_j;
+    int32_t* n_cigar;      /* ops the pair needs */
+    uint32_t* cigar;       /* [n_pairs][cigar_stride], len << 4 | op, M=0 I=1 D=2 */
+    uint32_t cigar_stride;
+} msw_trace_t;
+
+/* Device-resident: every pointer in `batch`, `ends` and `tr` is device memory.
+ * `ends` holds the score / end_i / end_j already computed for this batch and
+ * scheme (msw_align_batch_device with want_coords = 1); the trace refills only
+ * rows 0..end_i and columns 0..end_j of each pair and does not search for the
+ * maximum again.  sc->want_coords is not read.  Enqueued on `stream` (NULL =
+ * the context's compute stream), no host synchronisation. */
+int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch, const msw_out_t* ends,
+                           msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream);
+/* Host memory, synchronous: scores with coordinates (want_coords is forced),
+ * then traces, in chunks of `chunk_pairs` (0 = 65536).  All of out->score,
+ * out->end_i and out->end_j are required. */
+int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch, msw_out_t* out,
+                          msw_trace_t* tr, uint64_t chunk_pairs);
+
 /* Length-bucketed plan for a device-resident batch of mixed lengths (BASELINE
  * config 5).  Built on the host from host copies of the length arrays (the
  * FASTQ loader has them): pairs are grouped by rows per lane (read length /

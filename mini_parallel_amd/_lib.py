@@ -30,7 +30,7 @@ EXPORTED = (
     "msw_genome_create", "msw_genome_destroy", "msw_genome_length", "msw_align_reads",
     "msw_align_reads_async", "msw_genome_cut_device", "msw_ctx_stats", "msw_align_reads_device",
     "msw_memcpy_d2h_async", "msw_fence_record", "msw_fence_wait", "msw_ctx_prepare",
-    "msw_stream_create", "msw_stream_destroy",
+    "msw_stream_create", "msw_stream_destroy", "msw_trace_batch_device", "msw_align_batch_trace",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -71,6 +71,11 @@ class OutT(ctypes.Structure):
                 ("end_j", ctypes.c_void_p)]
 
 
+class TraceT(ctypes.Structure):
+    _fields_ = [("start_i", ctypes.c_void_p), ("start_j", ctypes.c_void_p), ("n_cigar", ctypes.c_void_p),
+                ("cigar", ctypes.c_void_p), ("cigar_stride", ctypes.c_uint32)]
+
+
 class DevReadsT(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_void_p), ("read_len", ctypes.c_void_p), ("pos", ctypes.c_void_p),
                 ("read_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("first_read", ctypes.c_uint64),
@@ -108,6 +113,10 @@ def _declare(L):
         "msw_wait": (I, [P, ctypes.c_uint64]),
         "msw_align_batch_device": (I, [P, ctypes.POINTER(ScoringT), ctypes.POINTER(BatchT),
                                        ctypes.POINTER(OutT), ctypes.c_uint32, ctypes.c_uint32, P]),
+        "msw_trace_batch_device": (I, [P, ctypes.POINTER(ScoringT), ctypes.POINTER(BatchT), ctypes.POINTER(OutT),
+                                       ctypes.POINTER(TraceT), ctypes.c_uint32, ctypes.c_uint32, P]),
+        "msw_align_batch_trace": (I, [P, ctypes.POINTER(ScoringT), ctypes.POINTER(BatchT), ctypes.POINTER(OutT),
+                                      ctypes.POINTER(TraceT), ctypes.c_uint64]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, BatchT, DeviceInfoT, MswError, OutT, ReadBatchT, ScoringT, StatsT,
+from ._lib import (MSW_E_INVALID, BatchT, DeviceInfoT, MswError, OutT, ReadBatchT, ScoringT, StatsT, TraceT,
                    check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
@@ -210,6 +210,66 @@ class Context:
                                     ctypes.byref(out), chunk_pairs))
         return score, ei, ej
 
+    # -- full alignments: traceback ----------------------------------------------------
+    def align_batch_trace(self, reads: np.ndarray, read_len: np.ndarray, wins: np.ndarray,
+                          win_len: np.ndarray, scoring: Scoring = LINEAR,
+                          cigar_stride: Optional[int] = None, chunk_pairs: int = 0):
+        """Score a padded SoA batch and trace every pair's canonical alignment
+        (msw_align_batch_trace; include/msw.h states the rule).  Returns
+        (score int32[B], end_i, end_j, start_i, start_j int16[B], ops): ops[p]
+        is a uint32 array of BAM-encoded ops (len << 4 | op, M=0 I=1 D=2) in
+        forward order, empty when the score is 0.  Coordinates are always
+        computed.  With ``cigar_stride=None`` a stride is picked and the call
+        is repeated once with the largest count if a pair overflowed; with a
+        given stride an overflowing pair's ops are None.  ``ops.n_cigar``
+        holds every pair's op count either way.  Reads over 384 or windows
+        over 4096 bases raise :class:`MswError` (MSW_E_RANGE)."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        wins = np.ascontiguousarray(wins, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        win_len = np.ascontiguousarray(win_len, dtype=np.uint16)
+        B = reads.shape[0]
+        if wins.shape[0] != B or read_len.shape[0] != B or win_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of pairs")
+        batch = BatchT(_ptr(reads), _ptr(wins), _ptr(read_len), _ptr(win_len),
+                       reads.shape[1] if reads.ndim == 2 else 0,
+                       wins.shape[1] if wins.ndim == 2 else 0, B)
+        sc = _scoring_c(scoring)
+        stride = 32 if cigar_stride is None else int(cigar_stride)
+        while True:
+            (score, ei, ej), out = _outputs(B, True)
+            si, sj = np.empty(B, np.int16), np.empty(B, np.int16)
+            nc = np.zeros(B, np.int32)
+            cig = np.zeros((B, stride), np.uint32)
+            tr = TraceT(_fresh_ptr(si), _fresh_ptr(sj), _fresh_ptr(nc), _fresh_ptr(cig), stride)
+            check(lib().msw_align_batch_trace(self.handle, ctypes.byref(sc), ctypes.byref(batch),
+                                              ctypes.byref(out), ctypes.byref(tr), chunk_pairs))
+            need = int(nc.max()) if B else 0
+            if cigar_stride is None and need > stride:
+                stride = need  # once: the counts do not depend on the stride
+                continue
+            break
+        ops = CigarList(cig[p, :nc[p]].copy() if nc[p] <= stride else None for p in range(B))
+        ops.n_cigar = nc
+        return score, ei, ej, si, sj, ops
+
+    def trace_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int, win_len_ptr: int,
+                           read_stride: int, win_stride: int, n_pairs: int, score_ptr: int,
+                           end_i_ptr: int, end_j_ptr: int, start_i_ptr: int, start_j_ptr: int,
+                           n_cigar_ptr: int, cigar_ptr: int, cigar_stride: int, max_read_len: int,
+                           max_win_len: int, scoring: Scoring = LINEAR, stream: int = 0) -> None:
+        """Enqueue one traceback pass over device-resident arrays (raw device
+        pointers) on ``stream``: score / end_i / end_j are the outputs of
+        :meth:`align_batch_device` with coordinates for the same batch and
+        scheme (msw_trace_batch_device)."""
+        batch = BatchT(reads_ptr, wins_ptr, read_len_ptr, win_len_ptr, read_stride, win_stride, n_pairs)
+        ends = OutT(score_ptr, end_i_ptr, end_j_ptr)
+        tr = TraceT(start_i_ptr, start_j_ptr, n_cigar_ptr, cigar_ptr, cigar_stride)
+        sc = _scoring_c(scoring)
+        check(lib().msw_trace_batch_device(self.handle, ctypes.byref(sc), ctypes.byref(batch),
+                                           ctypes.byref(ends), ctypes.byref(tr), max_read_len, max_win_len,
+                                           ctypes.c_void_p(stream or None)))
+
     # -- reads against an HBM-resident genome ------------------------------------------
     def load_genome(self, seq) -> "Genome":
         """Upload a reference genome (bytes / str / uint8 array) once; windows
@@ -350,6 +410,20 @@ class Context:
         check(lib().msw_align_compat(self.handle, b1, len(s1), b2, len(s2), wg, max_groups,
                                      ctypes.byref(res)))
         return int(res.value)
+
+
+class CigarList(list):
+    """Per-pair op arrays of :meth:`Context.align_batch_trace`; ``n_cigar`` holds
+    the op count every pair needs (a pair over the stride has ``None`` ops)."""
+    n_cigar = None
+
+
+def cigar_string(ops) -> str:
+    """BAM-encoded ops (len << 4 | op) -> text, e.g. ``"12M1I30M"``; no ops
+    (score 0) -> ``"*"``."""
+    if ops is None or len(ops) == 0:
+        return "*"
+    return "".join(f"{int(o) >> 4}{'MID'[int(o) & 15]}" for o in ops)
 
 
 class Pending:

@@ -120,6 +120,7 @@ uint64_t get_chunk_size_reads() {
 struct Args {
     std::string seq1, seq2;
     bool has_seq1 = false, has_seq2 = false, files = false, gpu = false, test_wgs = false, full_wgs = false;
+    bool cigar = false;
     long chunk_size = 1, num_files = -1;
     std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;
@@ -139,6 +140,8 @@ void usage() {
         "  -t, --test-wgs               count bases of the first lane's files\n"
         "      --full-wgs               process the full WGS dataset\n"
         "      --score-mode <compat|sw> compat = reference kernel semantics (default), sw = Smith-Waterman\n"
+        "      --cigar                  --score-mode sw, one pair: also print the alignment's start and CIGAR\n"
+        "                               (read <= 384, window <= 4096; with -f the pair is the two files' bases)\n"
         "      --gap-model <linear|affine>\n"
         "      --match N --mismatch N --gap-open N --gap-extend N\n"
         "      --reference <FASTA>      reference genome for --full-wgs --score-mode sw\n"
@@ -172,6 +175,7 @@ Args parse_args(int argc, char** argv) {
         else if (s == "-t" || s == "--test-wgs") a.test_wgs = true;
         else if (s == "--full-wgs") a.full_wgs = true;
         else if (s == "--score-mode") a.score_mode = v();
+        else if (s == "--cigar") a.cigar = true;
         else if (s == "--gap-model") a.gap_model = v();
         else if (s == "--match") a.match = atoi(v().c_str());
         else if (s == "--mismatch") a.mismatch = atoi(v().c_str());
@@ -189,6 +193,8 @@ Args parse_args(int argc, char** argv) {
     if (a.score_mode != "compat" && a.score_mode != "sw") die("error: --score-mode must be compat or sw");
     if (a.gap_model != "linear" && a.gap_model != "affine") die("error: --gap-model must be linear or affine");
     if (a.gap_extend < 0) a.gap_extend = a.gap_model == "affine" ? 1 : 2;
+    if (a.cigar && (a.score_mode != "sw" || a.full_wgs || a.test_wgs))
+        die("error: --cigar needs --score-mode sw and one pair of sequences (-1 / -2, direct or with -f)");
     return a;
 }
 
@@ -1363,7 +1369,7 @@ long long unix_ns() {
 int main(int argc, char** argv) {
     const long long t_main_ns = unix_ns();
     load_dotenv();
-    const Args a = parse_args(argc, argv);
+    Args a = parse_args(argc, argv);
     // --full-wgs sw: the reference loads beside the HIP runtime init
     // (setup_phases.reference_load_ms is its own duration)
     ReferenceLoad ref;
@@ -1549,6 +1555,27 @@ int main(int argc, char** argv) {
     const Device& dev = devices[0];
     Ctx ctx(dev.ordinal);
 
+    if (a.files && a.cigar) {
+        // --cigar with -f: the pair is the bases of file 1 (its reads in file
+        // order, concatenated) against the bases of file 2; it then runs as a
+        // direct pair below.  Reading stops once a file is past every limit.
+        for (std::string* seq : {&a.seq1, &a.seq2}) {
+            const std::string path = *seq;
+            std::string bases;
+            const int rc = for_each_fastq_chunk(path, 64, [&](std::string& c) {
+                bases += c;
+                return bases.size() > 32767 ? 2 : 0;
+            });
+            if (rc != 0 && rc != 2) {
+                fprintf(stderr, "GPU alignment error: %s\n", msw_last_error());
+                return 1;
+            }
+            if (rc == 0) printf("Loaded %llu bases from %s\n", (unsigned long long)bases.size(), path.c_str());
+            *seq = bases;
+        }
+        a.files = false;
+    }
+
     if (a.files) {
         // gpu_align_pair (aligner.rs:376-407)
         uint64_t b1 = 0, b2 = 0, r = 0;
@@ -1601,12 +1628,32 @@ int main(int argc, char** argv) {
         int16_t ei = -1, ej = -1;
         msw_batch_t b{r.data(), w.data(), &rl, &wl, (uint32_t)rs, (uint32_t)ws, 1};
         msw_out_t o{&score, &ei, &ej};
-        if (msw_align_batch(ctx.h, &sc, &b, &o, 0) != MSW_OK) {
+        int16_t si = -1, sj = -1;
+        int32_t n_ops = 0;
+        std::vector<uint32_t> ops;
+        if (a.cigar) {
+            // one pass sized for the common case, a second with the count the pair needs
+            for (uint32_t stride = 64;; stride = (uint32_t)n_ops) {
+                ops.assign(stride, 0);
+                msw_trace_t tr{&si, &sj, &n_ops, ops.data(), stride};
+                if (msw_align_batch_trace(ctx.h, &sc, &b, &o, &tr, 0) != MSW_OK) {
+                    fprintf(stderr, "GPU alignment error: %s\n", msw_last_error());
+                    return 1;
+                }
+                if (n_ops <= (int32_t)stride) break;
+            }
+        } else if (msw_align_batch(ctx.h, &sc, &b, &o, 0) != MSW_OK) {
             fprintf(stderr, "GPU alignment error: %s\n", msw_last_error());
             return 1;
         }
         printf("GPU Alignment score: %d\n", score);
         printf("Best cell: read %d, window %d\n", ei, ej);
+        if (a.cigar) {
+            std::string text;
+            for (int32_t k = 0; k < n_ops; ++k) text += std::to_string(ops[k] >> 4) + "MID?"[std::min<uint32_t>(ops[k] & 15u, 3u)];
+            printf("Alignment start: read %d, window %d\n", si, sj);
+            printf("CIGAR: %s\n", n_ops ? text.c_str() : "*");
+        }
         return 0;
     }
     bool ok = false;

@@ -206,6 +206,48 @@ size_t long_lds_bytes(uint32_t max_win_len);
 hipError_t launch_sw_long(const SwParams& p, bool affine, bool coords, uint32_t max_read_len, uint32_t max_win_len,
                           uint32_t blocks, hipStream_t stream);
 
+// Traceback (sw_trace_kernel, msw_trace.hip): one wave per pair refills the
+// rectangle rows 0..end_i x columns 0..end_j with i32 cells, records a
+// direction code per cell (2 bits linear, 4 bits affine, packed into u32
+// words), and walks the codes back from the end cell.
+constexpr int kTraceMaxR = 6;                    // rows per lane: 64 * 6 = kMaxReadLen
+constexpr uint32_t kTraceLdsWords = 8192;        // direction words kept in LDS (32 KiB); larger rectangles: global slab
+struct TraceParams {
+    const uint8_t* reads;
+    const uint8_t* wins;
+    const uint16_t* read_len;
+    const uint16_t* win_len;
+    const int16_t* end_i;     // the scoring call's best cell per pair; < 0: no alignment
+    const int16_t* end_j;
+    int16_t* start_i;
+    int16_t* start_j;
+    int32_t* n_cigar;
+    uint32_t* cigar;          // [n_pairs][cigar_stride]
+    uint64_t read_stride;
+    uint64_t win_stride;
+    uint32_t cigar_stride;
+    uint32_t n_slots;
+    uint32_t max_rows;        // the call's length bounds: larger rectangles are not traced
+    uint32_t max_cols;
+    int32_t match, mismatch, gap, goe;  // gap: linear penalty / affine gap_extend; goe = gap_open + gap_extend
+    uint32_t win_bytes;       // LDS layout: [window | ops | direction words]
+    uint32_t ops_cap;         // run-length ops the LDS buffer holds (<= cigar_stride)
+    uint32_t lds_words;       // direction words in LDS
+    uint32_t* slab;           // per-block global direction words (slab_words each), or null
+    uint64_t slab_words;
+    uint32_t* next;           // work queue counter (zeroed), or null: one block per slot
+};
+int trace_rows_per_lane(uint32_t max_read_len);
+// direction words of a rows x cols rectangle (16 cells per word linear, 8 affine)
+__host__ __device__ inline uint64_t trace_words(bool affine, uint32_t rows, uint32_t cols) {
+    const uint32_t cpw = affine ? 8u : 16u;
+    return (uint64_t)rows * ((cols + cpw - 1) / cpw);
+}
+// fills p.win_bytes / ops_cap / lds_words from the bounds; returns the dynamic LDS bytes
+size_t trace_lds_layout(TraceParams& p, bool affine);
+int trace_blocks_per_cu(bool affine, uint32_t max_read_len, size_t lds_bytes);
+hipError_t launch_sw_trace(const TraceParams& p, bool affine, uint32_t blocks, size_t lds_bytes, hipStream_t stream);
+
 // smith_waterman_align restated: result must be zeroed before the launch.
 hipError_t launch_compat(const uint8_t* s1, const uint8_t* s2, int32_t* result, uint64_t L,
                          uint32_t W, uint64_t G, hipStream_t stream);

@@ -77,6 +77,7 @@ struct Options {
     bool no_f16 = false;          // MSW_NO_F16: the integer path for every launch
     bool force_long = false;      // MSW_FORCE_LONG=1: every pair on the long-pair kernel
     uint64_t long_blocks = 0;     // MSW_LONG_BLOCKS: a fixed long-pair block count (work-queue grids)
+    uint64_t trace_blocks = 0;    // MSW_TRACE_BLOCKS: a fixed traceback block count (work-queue grids)
     bool layout_set = false;      // MSW_LAYOUT given (per-bucket launches then)
     bool force_pairs = false, force_split = false, force_mixed = false;  // its value
     bool group_set = false;       // MSW_GROUP_LANES given
@@ -96,6 +97,8 @@ Options read_options() {
     o.force_long = fl && *fl == '1';
     const char* lb = getenv("MSW_LONG_BLOCKS");
     o.long_blocks = lb && atoll(lb) > 0 ? (uint64_t)atoll(lb) : 0;
+    const char* tb = getenv("MSW_TRACE_BLOCKS");
+    o.trace_blocks = tb && atoll(tb) > 0 ? (uint64_t)atoll(tb) : 0;
     const char* lay = getenv("MSW_LAYOUT");
     o.layout_set = lay != nullptr;
     o.force_pairs = lay && !strcmp(lay, "pairs");
@@ -1722,6 +1725,173 @@ int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     return launch_packed(ctx, sch, p, max_read_len, max_win_len, st);
 }
 
+// Traceback supports the packed kernels' range only.
+static int check_trace_bounds(uint32_t max_m, uint32_t max_n) {
+    if (max_m > (uint32_t)msw::kMaxReadLen)
+        return fail(MSW_E_RANGE, "traceback: read length %u > %d", max_m, msw::kMaxReadLen);
+    if (max_n > (uint32_t)msw::kMaxWinLen)
+        return fail(MSW_E_RANGE, "traceback: window length %u > %d", max_n, msw::kMaxWinLen);
+    return MSW_OK;
+}
+
+static int validate_trace(const msw_trace_t* tr) {
+    if (!tr) return fail(MSW_E_INVALID, "trace is NULL");
+    if (!tr->start_i || !tr->start_j || !tr->n_cigar) return fail(MSW_E_INVALID, "NULL array in trace");
+    if (tr->cigar_stride && !tr->cigar) return fail(MSW_E_INVALID, "cigar is NULL with cigar_stride > 0");
+    return MSW_OK;
+}
+
+int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
+                           msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    Scheme sch;
+    int rc;
+    if ((rc = make_scheme(sc, ctx->opt, &sch))) return rc;
+    sch.coords = true;  // want_coords is not read: the ends are an input here
+    if ((rc = validate_batch(b, ends, sch)) || (rc = validate_trace(tr))) return rc;
+    if (b->n_pairs == 0) return MSW_OK;
+    if ((rc = check_trace_bounds(max_read_len, max_win_len))) return rc;
+    // one block per pair: a 1-D grid holds 2^31 - 1 blocks
+    if (b->n_pairs > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
+    if (max_read_len > b->read_stride || max_win_len > b->win_stride)
+        return fail(MSW_E_INVALID, "max length exceeds stride");
+    if ((rc = set_device(ctx))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    msw::TraceParams p;
+    memset(&p, 0, sizeof(p));
+    p.reads = b->reads;
+    p.wins = b->wins;
+    p.read_len = b->read_len;
+    p.win_len = b->win_len;
+    p.end_i = ends->end_i;
+    p.end_j = ends->end_j;
+    p.start_i = tr->start_i;
+    p.start_j = tr->start_j;
+    p.n_cigar = tr->n_cigar;
+    p.cigar = tr->cigar;
+    p.cigar_stride = tr->cigar_stride;
+    p.read_stride = b->read_stride;
+    p.win_stride = b->win_stride;
+    p.n_slots = (uint32_t)b->n_pairs;
+    p.max_rows = max_read_len;
+    p.max_cols = max_win_len;
+    p.match = sc->match;
+    p.mismatch = sc->mismatch;
+    p.gap = sc->gap_extend;
+    p.goe = sc->gap_open + sc->gap_extend;
+    const size_t shm = msw::trace_lds_layout(p, sch.affine);
+    // One block per pair while the direction words fit LDS.  A bound whose
+    // rectangle does not fit needs a global slab per block: the grid is then
+    // capped (what the CUs hold at once, and 256 MiB of slabs) and finished
+    // blocks take the next pair from a queue.  Slab and counter are allocated
+    // stream-ordered on `st`, like the long-pair launch's scratch.
+    const uint64_t need = msw::trace_words(sch.affine, max_read_len, max_win_len);
+    const bool slab = need > p.lds_words;
+    const uint64_t slab_bytes = slab ? need * sizeof(uint32_t) : 0;
+    uint64_t blocks = b->n_pairs;
+    if (slab) {
+        const int per_cu = msw::trace_blocks_per_cu(sch.affine, max_read_len, shm);
+        if (per_cu <= 0) return fail(MSW_E_DEVICE, "traceback kernel does not fit a CU");
+        const uint64_t resident = (uint64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (uint64_t)per_cu;
+        blocks = std::min(blocks, std::min(resident, std::max<uint64_t>(1, (256ull << 20) / slab_bytes)));
+    }
+    if (ctx->opt.trace_blocks) blocks = std::min<uint64_t>(blocks, ctx->opt.trace_blocks);  // tests: a fixed block count
+    const bool queue = blocks < b->n_pairs;
+    uint8_t* mem = nullptr;
+    if (slab || queue) {
+        HIP_TRY(hipMallocAsync((void**)&mem, blocks * slab_bytes + 256, st));
+        if (slab) {
+            p.slab = reinterpret_cast<uint32_t*>(mem);
+            p.slab_words = need;
+        }
+        if (queue) {
+            p.next = reinterpret_cast<uint32_t*>(mem + blocks * slab_bytes);
+            const hipError_t em = hipMemsetAsync(p.next, 0, sizeof(uint32_t), st);
+            if (em != hipSuccess) {
+                (void)hipFreeAsync(mem, st);
+                HIP_TRY(em);
+            }
+        }
+    }
+    const hipError_t e = msw::launch_sw_trace(p, sch.affine, (uint32_t)blocks, shm, st);
+    if (mem) HIP_TRY(hipFreeAsync(mem, st));
+    HIP_TRY(e);
+    return MSW_OK;
+}
+
+int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
+                          msw_trace_t* tr, uint64_t chunk_pairs) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    if (!sc) return fail(MSW_E_INVALID, "scoring is NULL");
+    msw_scoring_t scc = *sc;
+    scc.want_coords = 1;
+    Scheme sch;
+    int rc;
+    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
+    if ((rc = validate_batch(b, out, sch)) || (rc = validate_trace(tr))) return rc;
+    const uint64_t n = b->n_pairs;
+    if (n == 0) return MSW_OK;
+    uint32_t max_m = 0, max_n = 0;
+    max_u16(b->read_len, n, max_m);
+    max_u16(b->win_len, n, max_n);
+    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    if (max_m > b->read_stride || max_n > b->win_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    // Simple and synchronous: per chunk upload, score with coordinates, trace,
+    // download (not part of the three-slot staging pipeline).
+    const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
+    const size_t rs = b->read_stride, ws = b->win_stride, cs = tr->cigar_stride;
+    // [reads | wins | cigar u32 | score i32 | n_cigar i32 | rlen wlen end_i end_j start_i start_j, 2 B each]
+    const size_t o_wins = (chunk * rs + 255) & ~(size_t)255, o_cig = (o_wins + chunk * ws + 255) & ~(size_t)255;
+    const size_t o_score = o_cig + chunk * cs * 4, o_nc = o_score + chunk * 4, o_h = o_nc + chunk * 4;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, o_h + chunk * 12 + 256);
+    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", o_h + chunk * 12, hipGetErrorString(e));
+    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
+    uint16_t* d_wl = d_rl + chunk;
+    int16_t *d_ei = reinterpret_cast<int16_t*>(d_wl + chunk), *d_ej = d_ei + chunk, *d_si = d_ej + chunk,
+            *d_sj = d_si + chunk;
+    hipStream_t st = ctx->compute;
+    rc = MSW_OK;
+    for (uint64_t lo = 0; lo < n && rc == MSW_OK; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        uint32_t cm = 0, cn = 0;
+        max_u16(b->read_len + lo, c, cm);
+        max_u16(b->win_len + lo, c, cn);
+        auto up = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+        };
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+        };
+        up(d, b->reads + lo * rs, c * rs);
+        up(d + o_wins, b->wins + lo * ws, c * ws);
+        up(d_rl, b->read_len + lo, c * 2);
+        up(d_wl, b->win_len + lo, c * 2);
+        if (e != hipSuccess) break;
+        msw_batch_t db = {d, d + o_wins, d_rl, d_wl, (uint32_t)rs, (uint32_t)ws, c};
+        msw_out_t dout = {reinterpret_cast<int32_t*>(d + o_score), d_ei, d_ej};
+        msw_trace_t dtr = {d_si, d_sj, reinterpret_cast<int32_t*>(d + o_nc), reinterpret_cast<uint32_t*>(d + o_cig),
+                           (uint32_t)cs};
+        if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) break;
+        // same stream: the trace reads the ends the scoring launch wrote
+        if ((rc = msw_trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st))) break;
+        down(out->score + lo, dout.score, c * 4);
+        down(out->end_i + lo, d_ei, c * 2);
+        down(out->end_j + lo, d_ej, c * 2);
+        down(tr->start_i + lo, d_si, c * 2);
+        down(tr->start_j + lo, d_sj, c * 2);
+        down(tr->n_cigar + lo, dtr.n_cigar, c * 4);
+        if (cs) down(tr->cigar + lo * cs, dtr.cigar, c * cs * 4);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "traceback: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
 }  // extern "C"
 
 struct msw_plan {
@@ -2185,6 +2355,12 @@ int msw_ctx_prepare(msw_ctx* ctx, const msw_scoring_t* sc) {
     p.win_src = nullptr;
     ok &= msw::long_blocks_per_cu(sch.affine, sch.coords, 600, 600) > 0;
     ok &= msw::cut_blocks_per_cu() > 0;
+    msw::TraceParams tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.max_rows = 150;
+    tp.max_cols = 300;
+    tp.cigar_stride = 64;
+    ok &= msw::trace_blocks_per_cu(sch.affine, tp.max_rows, msw::trace_lds_layout(tp, sch.affine)) > 0;  // traceback
     (void)hipGetLastError();
     return ok ? MSW_OK : fail(MSW_E_DEVICE, "kernel module load failed");
 }
