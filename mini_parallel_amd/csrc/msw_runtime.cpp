@@ -401,7 +401,9 @@ struct msw_ctx {
     // free_events and fences: msw_fence_wait may run on several threads at
     // once (--full-wgs settles its last two batches on two)
     std::mutex ev_mu;
-    msw::Layout last_layout = msw::Layout::kPairs;  // the last packed launch's plan (MSW_HOST_TRACE)
+    // the plan of the last single-bucket launch of a host chunk or of a
+    // planned call (issue_schedule; MSW_HOST_TRACE prints it)
+    msw::Layout last_layout = msw::Layout::kPairs;
     uint32_t last_group_lanes = 0, last_kr = 0;
     std::unordered_map<uint64_t, hipEvent_t> fences;  // msw_fence_record, not yet waited on
     uint64_t next_fence = 1;
@@ -428,6 +430,11 @@ int set_device(msw_ctx* ctx) {
     if (hipGetDevice(&cur) == hipSuccess && cur == ctx->device) return MSW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     return MSW_OK;
+}
+
+// The stream of a device-API call: the caller's, or the context's compute stream.
+inline hipStream_t call_stream(const msw_ctx* ctx, void* stream) {
+    return stream ? (hipStream_t)stream : ctx->compute;
 }
 
 // The streams a context creates on first use (compute is made with it).
@@ -763,24 +770,26 @@ void bucket_chunk(const uint16_t* rlen, const uint16_t* wlen, uint64_t n, uint32
     for (int k = 0; k < kKeys; ++k) hist[k + 1] += hist[k];
     std::vector<uint32_t> pos(hist.begin(), hist.end() - 1);
     for (uint64_t i = 0; i < n; ++i) order[pos[key_of(i)]++] = (uint32_t)i;
+    // max read / max window over the slots [b, e)
+    auto bounds = [&](uint32_t b, uint32_t e, uint32_t& mm, uint32_t& mn) {
+        mm = mn = 0;
+        for (uint32_t s = b; s < e; ++s) {
+            mm = std::max<uint32_t>(mm, rlen[order[s]]);
+            mn = std::max<uint32_t>(mn, wlen[order[s]]);
+        }
+    };
     // One bucket per KR value; the window bound is the bucket's max.
     for (int kr = 1; kr <= msw::kMaxRowsPerLane; ++kr) {
         const uint32_t b = hist[kr * 257], e = hist[kr * 257 + 257];
         if (e <= b) continue;
-        uint32_t mm = 0, mn = 0;
-        for (uint32_t s = b; s < e; ++s) {
-            mm = std::max<uint32_t>(mm, rlen[order[s]]);
-            mn = std::max<uint32_t>(mn, wlen[order[s]]);
-        }
+        uint32_t mm, mn;
+        bounds(b, e, mm, mn);
         buckets.push_back({b, e - b, mm, mn});
     }
     if (hist[kLongKey + 1] > hist[kLongKey]) {  // the long pairs: last in slot order
         const uint32_t b = hist[kLongKey], e = hist[kLongKey + 1];
-        uint32_t mm = 0, mn = 0;
-        for (uint32_t s = b; s < e; ++s) {
-            mm = std::max<uint32_t>(mm, rlen[order[s]]);
-            mn = std::max<uint32_t>(mn, wlen[order[s]]);
-        }
+        uint32_t mm, mn;
+        bounds(b, e, mm, mn);
         // heaviest first (strips x steps at the launch's rows per lane): the
         // kernel's work queue then schedules longest-job-first
         const uint32_t strip_rows = 64u * (uint32_t)msw::long_rows_per_lane(mm);
@@ -866,17 +875,128 @@ int join_side(msw_ctx* ctx, hipStream_t st, SideFork& f) {
     return MSW_OK;
 }
 
-// The KR 17..24 buckets as one launch (one launch per bucket measured slower:
-// 8.5 vs 12.7 TCUPS linear).
-bool use_wide_multi(size_t n_wide, const Options& o) { return use_multi(n_wide, o); }
+// What a bucket list launches: the long bucket on the long-pair kernel, the
+// KR <= 16 buckets as one sw_multi_kernel launch, the KR 17..24 buckets as one
+// launch of its wide instance, every other packed bucket on its own.  Made by
+// schedule_buckets (per host chunk; once per plan), issued by issue_schedule.
+struct BucketSchedule {
+    bool has_long = false;
+    Bucket longs{};  // pairs beyond the packed kernels (sw_long_kernel): the last slots
+    bool multi = false, wide = false;
+    msw::MultiTable table{};       // multi: the KR <= 16 buckets
+    msw::MultiTable wide_table{};  // wide: the KR 17..24 buckets
+    // packed-kernel buckets launched on their own (all of them without a
+    // multi table, else the KR 17..24 ones), each with its layout
+    std::vector<std::pair<Bucket, LaunchPlan>> singles;
+    bool packed() const { return multi || wide || !singles.empty(); }
+};
 
-// Where a launch's windows come from: the slot's cut slab (win_stride), or,
-// with a genome, straight from the resident genome at the slot's positions
-// (the packed kernels only; long pairs need the slab).
-void set_windows(msw::SwParams& p, const Slot& s, uint32_t win_stride, const msw_genome* g) {
+// ordered: the batch is launched through an order array (slot -> pair), which
+// the multi launches need.  A host chunk in input order has none: it is one
+// bucket with a launch of its own.
+BucketSchedule schedule_buckets(const std::vector<Bucket>& buckets, const Scheme& sch, int cu_count, bool ordered) {
+    BucketSchedule s;
+    const size_t n_short = short_buckets(buckets), n_multi = multi_buckets(buckets);
+    if (n_short < buckets.size()) {
+        s.has_long = true;
+        s.longs = buckets.back();
+    }
+    s.multi = ordered && use_multi(n_multi, *sch.opt);
+    if (s.multi) fill_multi(buckets, 0, n_multi, sch, s.table);
+    // The KR 17..24 buckets as one launch of the wide instance when there are
+    // several: one launch per bucket left each bucket's few waves running
+    // alone and measured slower (8.5 vs 12.7 TCUPS linear).
+    s.wide = ordered && use_multi(n_short - n_multi, *sch.opt);
+    if (s.wide) fill_multi(buckets, n_multi, n_short, sch, s.wide_table);
+    for (size_t bi = s.multi ? n_multi : 0; bi < (s.wide ? n_multi : n_short); ++bi) {
+        const Bucket& b = buckets[bi];
+        s.singles.push_back({b, choose_layout(b.count, b.max_m, b.max_n, sch, cu_count)});
+    }
+    return s;
+}
+
+// p narrowed to the slots [b.begin, b.begin + b.count) of its order array
+// (without one, slot k is pair k: the pairs from b.begin on) and of its
+// slot-ordered results.
+msw::SwParams bucket_slots(msw::SwParams p, const Bucket& b) {
+    if (p.order) p.order += b.begin;
+    else p.slot_base = b.begin;
+    p.out_slot_base = b.begin;
+    p.n_slots = b.count;
+    return p;
+}
+
+// One packed bucket's launch parameters under its plan (p: the batch's
+// pointers, strides / window source, order and output fields).
+msw::SwParams bucket_params(const msw::SwParams& p, const Scheme& sch, const Bucket& b, const LaunchPlan& plan) {
+    msw::SwParams q = bucket_slots(p, b);
+    q.lds_stride = msw::stream_stride(b.max_n);
+    q.f16_ok = f16_fits(sch, b.max_m, b.max_n) ? 1u : 0u;
+    q.pairs_blocks = plan.pairs_blocks;
+    q.group_lanes = plan.group_lanes;
+    q.groups = plan.groups;
+    return q;
+}
+
+// One packed bucket on its own launch.
+int launch_bucket(const msw::SwParams& p, const Scheme& sch, const Bucket& b, const LaunchPlan& plan, hipStream_t st) {
+    HIP_TRY(msw::launch_sw(bucket_params(p, sch, b, plan), sch.affine, sch.coords, b.max_m, plan.layout, st));
+    return MSW_OK;
+}
+
+// The launches of a schedule on `st`, in this order: the long launch (on the
+// side stream if and only if packed launches follow), the multi launch, the
+// wide multi launch, the single buckets in bucket order, the join back from
+// the side stream.  `base` carries what the caller knows -- data pointers and
+// strides, window source, outputs, the order array (or null: input order),
+// out_by_slot, slot_lens; the per-launch fields are derived here.
+int issue_schedule(msw_ctx* ctx, const Scheme& sch, const msw::SwParams& base, const BucketSchedule& s,
+                   hipStream_t st) {
+    int rc;
+    SideFork side;
+    if (s.has_long) {  // the long pairs: their own launch, beside any packed ones
+        const Bucket& b = s.longs;
+        msw::SwParams p = bucket_slots(base, b);
+        p.slot_lens = nullptr;  // the long kernel reads lengths per pair, never by slot
+        // only the order array puts slots of spread lengths heaviest first
+        const bool spread = base.order && b.spread;
+        if (s.packed() && (rc = fork_side(ctx, st, side))) return rc;
+        if ((rc = launch_long(sch, p, b.count, b.max_m, b.max_n, spread, ctx->cu_count, s.packed() ? ctx->side : st)))
+            return rc;
+    }
+    msw::SwParams m = base;  // the multi launches: slots and slot results from 0, buckets from the table
+    m.out_slot_base = 0;
+    m.group_lanes = 16;
+    m.groups = 4;
+    if (s.multi) HIP_TRY(msw::launch_sw_multi(m, s.table, sch.affine, sch.coords, st));
+    if (s.wide) HIP_TRY(msw::launch_sw_multi(m, s.wide_table, sch.affine, sch.coords, st));
+    for (const auto& sb : s.singles) {
+        const Bucket& b = sb.first;
+        const LaunchPlan& plan = sb.second;
+        ctx->last_layout = plan.layout;
+        ctx->last_group_lanes = plan.group_lanes;
+        ctx->last_kr = (uint32_t)msw::rows_per_lane(b.max_m, plan.layout == msw::Layout::kSplit, plan.group_lanes);
+        if ((rc = launch_bucket(base, sch, b, plan, st))) return rc;
+    }
+    if (side.ev) return join_side(ctx, st, side);
+    return MSW_OK;
+}
+
+// Base parameters of a staged chunk's launches.  Its windows come from the
+// slot's cut slab (win_stride), or, with a genome, straight from the resident
+// genome at the slot's positions (the packed kernels only; long pairs need
+// the slab).
+msw::SwParams slot_params(const Scheme& sch, const Slot& s, uint32_t read_stride, uint32_t win_stride,
+                          const msw_genome* g) {
+    msw::SwParams p = base_params(sch);
+    p.reads = s.d_reads;
+    p.read_len = s.d_rlen;
+    p.win_len = s.d_wlen;
+    p.score = s.k_score;
+    p.end_i = sch.coords ? s.k_ei : nullptr;
+    p.end_j = sch.coords ? s.k_ej : nullptr;
+    p.read_stride = read_stride;
     if (g) {
-        p.wins = nullptr;
-        p.win_stride = 0;
         p.win_src = g->d_seq;
         p.win_pos = s.d_pos;
         p.win_vec = 1;
@@ -885,115 +1005,38 @@ void set_windows(msw::SwParams& p, const Slot& s, uint32_t win_stride, const msw
         p.win_stride = win_stride;
         p.win_vec = msw::vec_ok(p.wins, p.win_stride);
     }
+    return p;
 }
 
-int launch_buckets(msw_ctx* ctx, const Scheme& sch, Slot& s, uint64_t n, const std::vector<Bucket>& buckets,
-                   bool use_order, uint32_t read_stride, uint32_t win_stride, hipStream_t cs,
-                   const msw_genome* g = nullptr) {
-    const size_t n_short = short_buckets(buckets);
-    SideFork side;
-    if (n_short < buckets.size()) {  // long pairs: their own launch, beside any packed ones
-        const Bucket& b = buckets.back();
-        msw::SwParams p = base_params(sch);
-        if (g) return fail(MSW_E_INVALID, "internal: long pairs need the window slab");
-        p.reads = s.d_reads;
-        p.wins = s.d_wins;
-        p.read_len = s.d_rlen;
-        p.win_len = s.d_wlen;
-        p.order = use_order ? s.d_order + b.begin : nullptr;
-        p.out_by_slot = use_order ? 1u : 0u;
-        p.out_slot_base = b.begin;
-        p.slot_base = use_order ? 0u : b.begin;
-        p.score = s.k_score;
-        p.end_i = sch.coords ? s.k_ei : nullptr;
-        p.end_j = sch.coords ? s.k_ej : nullptr;
-        p.read_stride = read_stride;
-        p.win_stride = win_stride;
-        int rc = n_short ? fork_side(ctx, cs, side) : MSW_OK;
-        if (!rc)
-            rc = launch_long(sch, p, b.count, b.max_m, b.max_n, use_order && b.spread, ctx->cu_count,
-                             n_short ? ctx->side : cs);
-        if (rc) return rc;
-        if (n_short == 0) return MSW_OK;
-    }
-    if (g && (use_order || buckets.size() != 1)) return fail(MSW_E_INVALID, "internal: genome windows need one bucket");
-    const size_t n_multi = multi_buckets(buckets);
-    size_t first_single = 0;
-    if (use_order && use_multi(n_multi, *sch.opt)) {
-        msw::SwParams p = base_params(sch);
-        p.reads = s.d_reads;
-        p.wins = s.d_wins;
-        p.read_len = s.d_rlen;
-        p.win_len = s.d_wlen;
-        p.order = s.d_order;
-        p.score = s.k_score;
-        p.end_i = sch.coords ? s.k_ei : nullptr;
-        p.end_j = sch.coords ? s.k_ej : nullptr;
-        p.read_stride = read_stride;
-        set_windows(p, s, win_stride, g);
-        p.group_lanes = 16;
-        p.groups = 4;
-        p.out_by_slot = 1;
-        p.out_slot_base = 0;
-        msw::MultiTable t;
-        fill_multi(buckets, 0, n_multi, sch, t);
-        HIP_TRY(msw::launch_sw_multi(p, t, sch.affine, sch.coords, cs));
-        first_single = n_multi;
-    }
-    // the KR 17..24 buckets: one launch of the wide instance when there are
-    // several (one launch each left each bucket's few waves running alone)
-    size_t single_end = n_short;
-    if (use_order && use_wide_multi(n_short - n_multi, *sch.opt)) {
-        msw::SwParams p = base_params(sch);
-        p.reads = s.d_reads;
-        p.wins = s.d_wins;
-        p.read_len = s.d_rlen;
-        p.win_len = s.d_wlen;
-        p.order = s.d_order;
-        p.score = s.k_score;
-        p.end_i = sch.coords ? s.k_ei : nullptr;
-        p.end_j = sch.coords ? s.k_ej : nullptr;
-        p.read_stride = read_stride;
-        set_windows(p, s, win_stride, g);
-        p.group_lanes = 16;
-        p.groups = 4;
-        p.out_by_slot = 1;
-        p.out_slot_base = 0;
-        msw::MultiTable t;
-        fill_multi(buckets, n_multi, n_short, sch, t);
-        HIP_TRY(msw::launch_sw_multi(p, t, sch.affine, sch.coords, cs));
-        single_end = n_multi;
-    }
-    for (size_t bi = first_single; bi < single_end; ++bi) {
-        const Bucket& b = buckets[bi];
-        msw::SwParams p = base_params(sch);
-        p.reads = s.d_reads;
-        p.wins = s.d_wins;
-        p.read_len = s.d_rlen;
-        p.win_len = s.d_wlen;
-        p.order = use_order ? s.d_order + b.begin : nullptr;
-        p.out_by_slot = use_order ? 1u : 0u;
-        p.out_slot_base = b.begin;
-        p.score = s.k_score;
-        p.end_i = sch.coords ? s.k_ei : nullptr;
-        p.end_j = sch.coords ? s.k_ej : nullptr;
-        p.read_stride = read_stride;
-        set_windows(p, s, win_stride, g);
-        p.n_slots = b.count;
-        p.lds_stride = msw::stream_stride(b.max_n);
-        p.f16_ok = f16_fits(sch, b.max_m, b.max_n) ? 1u : 0u;
-        const LaunchPlan plan = choose_layout(b.count, b.max_m, b.max_n, sch, ctx->cu_count);
-        p.pairs_blocks = plan.pairs_blocks;
-        p.group_lanes = plan.group_lanes;
-        p.groups = plan.groups;
-        ctx->last_layout = plan.layout;
-        ctx->last_group_lanes = plan.group_lanes;
-        ctx->last_kr = (uint32_t)msw::rows_per_lane(b.max_m, plan.layout == msw::Layout::kSplit, plan.group_lanes);
-        HIP_TRY(msw::launch_sw(p, sch.affine, sch.coords, b.max_m, plan.layout, cs));
-    }
-    if (side.ev) return join_side(ctx, cs, side);
-    (void)n;
-    return MSW_OK;
+// Base parameters of a device-memory batch (the device API and plans).
+msw::SwParams batch_params(const Scheme& sch, const msw_batch_t& b, const msw_out_t& out) {
+    msw::SwParams p = base_params(sch);
+    p.reads = b.reads;
+    p.wins = b.wins;
+    p.read_len = b.read_len;
+    p.win_len = b.win_len;
+    p.score = out.score;
+    p.end_i = sch.coords ? out.end_i : nullptr;
+    p.end_j = sch.coords ? out.end_j : nullptr;
+    p.read_stride = b.read_stride;
+    p.win_stride = b.win_stride;
+    p.win_vec = msw::vec_ok(p.wins, p.win_stride);
+    return p;
+}
+
+// The scoring launches of one staged chunk.  ordered: the chunk runs through
+// the slot's order array and leaves its results in slot order (the drain
+// scatters them); a chunk in input order needs neither.  g: the chunk's one
+// packed bucket reads its windows from the resident genome.
+int launch_buckets(msw_ctx* ctx, const Scheme& sch, const Slot& s, const std::vector<Bucket>& buckets, bool ordered,
+                   uint32_t read_stride, uint32_t win_stride, hipStream_t cs, const msw_genome* g = nullptr) {
+    if (g && short_buckets(buckets) < buckets.size())
+        return fail(MSW_E_INVALID, "internal: long pairs need the window slab");
+    if (g && (ordered || buckets.size() != 1)) return fail(MSW_E_INVALID, "internal: genome windows need one bucket");
+    msw::SwParams p = slot_params(sch, s, read_stride, win_stride, g);
+    p.order = ordered ? s.d_order : nullptr;
+    p.out_by_slot = ordered ? 1u : 0u;
+    return issue_schedule(ctx, sch, p, schedule_buckets(buckets, sch, ctx->cu_count, ordered), cs);
 }
 
 // Copy finished results of a slot into the caller's arrays; the chunk's
@@ -1042,6 +1085,12 @@ int validate_batch(const msw_batch_t* b, const msw_out_t* out, const Scheme& sch
     if (sch.coords && (!out->end_i || !out->end_j))
         return fail(MSW_E_INVALID, "want_coords set but end_i/end_j is NULL");
     if (b->n_pairs > 0xFFFFFFFFull) return fail(MSW_E_RANGE, "n_pairs > 2^32-1");
+    return MSW_OK;
+}
+
+// The length bounds a device-memory call states must fit the batch's rows.
+int check_strides(const msw_batch_t& b, uint32_t max_m, uint32_t max_n) {
+    if (max_m > b.read_stride || max_n > b.win_stride) return fail(MSW_E_INVALID, "max length exceeds stride");
     return MSW_OK;
 }
 
@@ -1403,7 +1452,7 @@ int run_batch_impl(msw_ctx* ctx, const msw_scoring_t* sc, const HostBatch& b, ms
         s.k_ei = direct_out ? s.h_ei : s.d_ei;
         s.k_ej = direct_out ? s.h_ej : s.d_ej;
         HIP_TRY(hipEventRecord(s.k_start, cs));
-        if ((rc = launch_buckets(ctx, sch, s, cnt, buckets, !uniform, rs, ws, cs, fused ? b.genome : nullptr)))
+        if ((rc = launch_buckets(ctx, sch, s, buckets, !uniform, rs, ws, cs, fused ? b.genome : nullptr)))
             return rc;
         HIP_TRY(hipEventRecord(s.k_end, cs));
         ctx->stats.launches += 1;
@@ -1678,19 +1727,15 @@ static int traced_launch(msw::SwParams p, const Scheme& sch, uint32_t max_read_l
     return MSW_OK;
 }
 
-// One packed-kernel launch of p (pointers, strides / window source and
-// n_slots set) under the given length bounds: layout from the makespan model.
-static int launch_packed(msw_ctx* ctx, const Scheme& sch, msw::SwParams& p, uint32_t max_read_len,
+// One packed-kernel launch of all n pairs of p (pointers and strides set,
+// input order) under the given length bounds: layout from the makespan model.
+static int launch_packed(msw_ctx* ctx, const Scheme& sch, const msw::SwParams& p, uint32_t n, uint32_t max_read_len,
                          uint32_t max_win_len, hipStream_t st) {
-    p.lds_stride = msw::stream_stride(max_win_len);
-    p.f16_ok = f16_fits(sch, max_read_len, max_win_len) ? 1u : 0u;
-    const LaunchPlan plan = choose_layout(p.n_slots, max_read_len, max_win_len, sch, ctx->cu_count);
-    p.pairs_blocks = plan.pairs_blocks;
-    p.group_lanes = plan.group_lanes;
-    p.groups = plan.groups;
-    if (!ctx->opt.wave_trace.empty()) return traced_launch(p, sch, max_read_len, plan, st, ctx->opt.wave_trace.c_str());
-    HIP_TRY(msw::launch_sw(p, sch.affine, sch.coords, max_read_len, plan.layout, st));
-    return MSW_OK;
+    const Bucket b{0, n, max_read_len, max_win_len};
+    const LaunchPlan plan = choose_layout(n, max_read_len, max_win_len, sch, ctx->cu_count);
+    if (!ctx->opt.wave_trace.empty())
+        return traced_launch(bucket_params(p, sch, b, plan), sch, max_read_len, plan, st, ctx->opt.wave_trace.c_str());
+    return launch_bucket(p, sch, b, plan, st);
 }
 
 int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
@@ -1702,27 +1747,14 @@ int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     if ((rc = validate_batch(b, out, sch))) return rc;
     if (b->n_pairs == 0) return MSW_OK;
     if ((rc = check_bounds(sch, max_read_len, max_win_len))) return rc;
-    if (max_read_len > b->read_stride || max_win_len > b->win_stride)
-        return fail(MSW_E_INVALID, "max length exceeds stride");
+    if ((rc = check_strides(*b, max_read_len, max_win_len))) return rc;
     if ((rc = set_device(ctx))) return rc;
-    msw::SwParams p = base_params(sch);
-    p.reads = b->reads;
-    p.wins = b->wins;
-    p.read_len = b->read_len;
-    p.win_len = b->win_len;
-    p.order = nullptr;
-    p.score = out->score;
-    p.end_i = sch.coords ? out->end_i : nullptr;
-    p.end_j = sch.coords ? out->end_j : nullptr;
-    p.read_stride = b->read_stride;
-    p.win_stride = b->win_stride;
-    p.n_slots = (uint32_t)b->n_pairs;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    const msw::SwParams p = batch_params(sch, *b, *out);  // input order: no order array
+    hipStream_t st = call_stream(ctx, stream);
     // bounds past the packed kernels: the whole batch on the long-pair kernel
     if (ctx->opt.force_long || is_long(max_read_len, max_win_len))
         return launch_long(sch, p, b->n_pairs, max_read_len, max_win_len, false, ctx->cu_count, st);
-    p.win_vec = msw::vec_ok(p.wins, p.win_stride);
-    return launch_packed(ctx, sch, p, max_read_len, max_win_len, st);
+    return launch_packed(ctx, sch, p, (uint32_t)b->n_pairs, max_read_len, max_win_len, st);
 }
 
 // Traceback supports the packed kernels' range only.
@@ -1753,10 +1785,9 @@ int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     if ((rc = check_trace_bounds(max_read_len, max_win_len))) return rc;
     // one block per pair: a 1-D grid holds 2^31 - 1 blocks
     if (b->n_pairs > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
-    if (max_read_len > b->read_stride || max_win_len > b->win_stride)
-        return fail(MSW_E_INVALID, "max length exceeds stride");
+    if ((rc = check_strides(*b, max_read_len, max_win_len))) return rc;
     if ((rc = set_device(ctx))) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    hipStream_t st = call_stream(ctx, stream);
     msw::TraceParams p;
     memset(&p, 0, sizeof(p));
     p.reads = b->reads;
@@ -1909,15 +1940,7 @@ struct msw_plan {
     uint32_t* d_inv = nullptr;
     uint8_t* d_tmp = nullptr;
     uint32_t* d_slot_lens = nullptr;  // read_len | win_len << 16 in slot order
-    bool multi = false;
-    msw::MultiTable table{};
-    bool wide = false;  // the KR 17..24 buckets as one launch (wide_table)
-    msw::MultiTable wide_table{};
-    // packed-kernel buckets launched on their own (all of them without a
-    // multi table, else the KR 17..24 ones), each with its layout
-    std::vector<std::pair<Bucket, LaunchPlan>> singles;
-    bool has_long = false;
-    Bucket longs{};                   // pairs beyond the packed kernels (sw_long_kernel)
+    BucketSchedule sched;             // the launches of one call
 };
 
 extern "C" {
@@ -1932,10 +1955,8 @@ int msw_plan_create(msw_ctx* ctx, const msw_scoring_t* sc, const uint16_t* read_
     if (n_pairs && (!read_len || !win_len)) return fail(MSW_E_INVALID, "NULL length array");
     if (n_pairs > 0xFFFFFFFFull) return fail(MSW_E_RANGE, "n_pairs > 2^32-1");
     uint32_t gm = 0, gn = 0;
-    for (uint64_t i = 0; i < n_pairs; ++i) {
-        gm = std::max<uint32_t>(gm, read_len[i]);
-        gn = std::max<uint32_t>(gn, win_len[i]);
-    }
+    max_u16(read_len, n_pairs, gm);
+    max_u16(win_len, n_pairs, gn);
     if ((rc = check_bounds(sch, gm, gn))) return rc;
     if ((rc = set_device(ctx))) return rc;
     msw_plan* pl = new msw_plan();
@@ -1950,19 +1971,7 @@ int msw_plan_create(msw_ctx* ctx, const msw_scoring_t* sc, const uint16_t* read_
         std::vector<Bucket> buckets;
         uint32_t lens[4];
         bucket_chunk(read_len, win_len, n_pairs, order.data(), buckets, lens, ctx->opt.force_long);
-        const size_t n_short = short_buckets(buckets);
-        if (n_short < buckets.size()) {
-            pl->has_long = true;
-            pl->longs = buckets.back();
-        }
-        const size_t n_multi = multi_buckets(buckets);
-        pl->multi = use_multi(n_multi, ctx->opt);
-        if (pl->multi) fill_multi(buckets, 0, n_multi, sch, pl->table);
-        pl->wide = use_wide_multi(n_short - n_multi, ctx->opt);
-        if (pl->wide) fill_multi(buckets, n_multi, n_short, sch, pl->wide_table);
-        for (size_t bi = pl->multi ? n_multi : 0; bi < (pl->wide ? n_multi : n_short); ++bi)
-            pl->singles.push_back({buckets[bi], choose_layout(buckets[bi].count, buckets[bi].max_m, buckets[bi].max_n,
-                                                              sch, ctx->cu_count)});
+        pl->sched = schedule_buckets(buckets, sch, ctx->cu_count, true);
         rc = grow_dev(&pl->d_order, n_pairs);
         hipError_t e = rc ? hipSuccess : hipMemcpy(pl->d_order, order.data(), n_pairs * sizeof(uint32_t),
                                                    hipMemcpyHostToDevice);
@@ -2001,73 +2010,24 @@ int msw_align_batch_planned(msw_ctx* ctx, const msw_plan* plan, const msw_batch_
         return fail(MSW_E_INVALID, "batch has %llu pairs, plan %llu", (unsigned long long)b->n_pairs,
                     (unsigned long long)plan->n);
     if (plan->n == 0) return MSW_OK;
-    if (plan->max_m > b->read_stride || plan->max_n > b->win_stride)
-        return fail(MSW_E_INVALID, "max length exceeds stride");
+    if ((rc = check_strides(*b, plan->max_m, plan->max_n))) return rc;
     if ((rc = set_device(ctx))) return rc;
     const Scheme& sch = plan->sch;
-    msw::SwParams p = base_params(sch);
-    p.reads = b->reads;
-    p.wins = b->wins;
-    p.read_len = b->read_len;
-    p.win_len = b->win_len;
-    p.order = plan->d_order;
-    p.score = out->score;
-    p.end_i = sch.coords ? out->end_i : nullptr;
-    p.end_j = sch.coords ? out->end_j : nullptr;
-    p.read_stride = b->read_stride;
-    p.win_stride = b->win_stride;
-    p.win_vec = msw::vec_ok(p.wins, p.win_stride);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    msw::SwParams p = batch_params(sch, *b, *out);
+    p.order = plan->d_order;  // also when it is the identity: the multi launches need one
+    hipStream_t st = call_stream(ctx, stream);
     const uint64_t n = plan->n;
     int32_t* t_score = reinterpret_cast<int32_t*>(plan->d_tmp);
     int16_t* t_i = reinterpret_cast<int16_t*>(plan->d_tmp + 4 * n);
     int16_t* t_j = reinterpret_cast<int16_t*>(plan->d_tmp + 6 * n);
     if (!plan->identity) {  // slot-ordered lengths and results, gathered below
         p.out_by_slot = 1;
-        p.out_slot_base = 0;
         p.slot_lens = plan->d_slot_lens;
         p.score = t_score;
         p.end_i = sch.coords ? t_i : nullptr;
         p.end_j = sch.coords ? t_j : nullptr;
     }
-    SideFork side;
-    if (plan->has_long) {  // the long pairs' slots come last: [longs.begin, n)
-        msw::SwParams q = p;
-        q.order = plan->d_order + plan->longs.begin;
-        q.out_slot_base = plan->longs.begin;
-        q.slot_lens = nullptr;
-        const bool beside = plan->multi || plan->wide || !plan->singles.empty();
-        if (beside && (rc = fork_side(ctx, st, side))) return rc;
-        if ((rc = launch_long(sch, q, plan->longs.count, plan->longs.max_m, plan->longs.max_n, plan->longs.spread,
-                              ctx->cu_count, beside ? ctx->side : st)))
-            return rc;
-    }
-    if (plan->multi) {
-        msw::SwParams q = p;
-        q.group_lanes = 16;
-        q.groups = 4;
-        HIP_TRY(msw::launch_sw_multi(q, plan->table, sch.affine, sch.coords, st));
-    }
-    if (plan->wide) {
-        msw::SwParams q = p;
-        q.group_lanes = 16;
-        q.groups = 4;
-        HIP_TRY(msw::launch_sw_multi(q, plan->wide_table, sch.affine, sch.coords, st));
-    }
-    for (const auto& sb : plan->singles) {  // slots [b.begin, b.begin + count)
-        const Bucket& b = sb.first;
-        msw::SwParams q = p;
-        q.order = plan->d_order + b.begin;
-        q.out_slot_base = b.begin;
-        q.n_slots = b.count;
-        q.lds_stride = msw::stream_stride(b.max_n);
-        q.f16_ok = f16_fits(sch, b.max_m, b.max_n) ? 1u : 0u;
-        q.pairs_blocks = sb.second.pairs_blocks;
-        q.group_lanes = sb.second.group_lanes;
-        q.groups = sb.second.groups;
-        HIP_TRY(msw::launch_sw(q, sch.affine, sch.coords, b.max_m, sb.second.layout, st));
-    }
-    if (side.ev && (rc = join_side(ctx, st, side))) return rc;
+    if ((rc = issue_schedule(ctx, sch, p, plan->sched, st))) return rc;
     if (!plan->identity)
         HIP_TRY(msw::launch_gather_results(plan->d_inv, t_score, t_i, t_j, out->score, sch.coords ? out->end_i : nullptr,
                                            sch.coords ? out->end_j : nullptr, n, st));
@@ -2176,7 +2136,7 @@ int msw_genome_cut_device(msw_ctx* ctx, const msw_genome* g, const int64_t* win_
         return fail(MSW_E_INVALID, "win_stride must be a non-zero multiple of 16 and wins 16-byte aligned");
     int rc = set_device(ctx);
     if (rc) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    hipStream_t st = call_stream(ctx, stream);
     HIP_TRY(msw::launch_cut_windows(g->d_seq, g->len, win_pos, win_len, wins, win_len_out, win_stride, n, st));
     return MSW_OK;
 }
@@ -2209,7 +2169,7 @@ int msw_align_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
     int rc = set_device(ctx);
     if (rc) return rc;
     const uint32_t max_win = window ? window : std::min<uint32_t>(2u * max_read_len, (uint32_t)msw::kMaxWinLen);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    hipStream_t st = call_stream(ctx, stream);
     harvest_dev_timings(ctx, false);
     const uint32_t ws = std::max<uint32_t>(16u, (max_win + 15u) & ~15u);
     const size_t wbytes = (size_t)n * ws;
@@ -2249,7 +2209,7 @@ int msw_memcpy_d2h_async(msw_ctx* ctx, void* dst, const void* src, size_t bytes,
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     int rc = set_device(ctx);
     if (rc) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->compute;
+    hipStream_t st = call_stream(ctx, stream);
     // Into pinned host memory the copy is a kernel on the caller's stream,
     // not a DMA: the copy engines serve every stream of the process from
     // shared in-order rings, so a DMA that waits on its stream's scoring
@@ -2380,7 +2340,7 @@ int msw_fence_record(msw_ctx* ctx, void* stream, uint64_t* fence) {
     hipEvent_t e = take_event(ctx);
     if (!e) return fail(MSW_E_DEVICE, "hipEventCreate failed");
     std::lock_guard<std::mutex> lk(ctx->ev_mu);
-    if (hipEventRecord(e, stream ? (hipStream_t)stream : ctx->compute) != hipSuccess) {
+    if (hipEventRecord(e, call_stream(ctx, stream)) != hipSuccess) {
         ctx->free_events.push_back(e);
         return fail(MSW_E_DEVICE, "hipEventRecord failed");
     }

@@ -237,37 +237,70 @@ def test_long_device_api(gpu_ctx, oracle, kind):
                 oracle_run(oracle, R, rl, W, wl, sc), sc.want_coords)
 
 
-@pytest.mark.parametrize("kind", ["linear_coords", "affine"])
-def test_long_planned(gpu_ctx, oracle, kind):
-    """A plan over short and long pairs: one length-bucketed launch, the long
-    launch, the slot-order gather; twice over the same plan."""
-    import torch
-    sc = scoring(kind)
-    rng = np.random.default_rng(9)
-    s = make_pairs(700, (75, 250), seed=8)
+def _short_and_long(n_short, seed, longs, short_seed):
+    """make_pairs reads of 75..250 bases with the (m, n) pairs of `longs`
+    inserted at random places, as lists of byte strings."""
+    rng = np.random.default_rng(seed)
+    s = make_pairs(n_short, (75, 250), seed=short_seed)
     reads = [bytes(s.reads[k, :s.read_len[k]]) for k in range(s.n_pairs)]
     wins = [bytes(s.wins[k, :s.win_len[k]]) for k in range(s.n_pairs)]
-    for m, n in EDGE:
+    for m, n in longs:
         r, w = related(rng, m, n)
         at = int(rng.integers(0, len(reads) + 1))
         reads.insert(at, r)
         wins.insert(at, w)
-    R, rl, W, wl = mpa.pack_batch(reads, wins)
+    return reads, wins
+
+
+def _planned_twice(ctx, oracle, sc, R, rl, W, wl):
+    """One plan over the batch, launched twice; each run against the oracle."""
     n = R.shape[0]
     dR, dW, drl, dwl = _device([R, W, rl.view(np.int16), wl.view(np.int16)])
     score, ei, ej = _device([np.zeros(n, np.int32), np.zeros(n, np.int16), np.zeros(n, np.int16)])
-    launch = gpu_ctx.prepare_planned_launch(dR.data_ptr(), drl.data_ptr(), dW.data_ptr(), dwl.data_ptr(),
-                                            R.shape[1], W.shape[1], rl, wl, score.data_ptr(), sc,
-                                            ei.data_ptr(), ej.data_ptr())
+    launch = ctx.prepare_planned_launch(dR.data_ptr(), drl.data_ptr(), dW.data_ptr(), dwl.data_ptr(),
+                                        R.shape[1], W.shape[1], rl, wl, score.data_ptr(), sc,
+                                        ei.data_ptr(), ej.data_ptr())
     want = oracle_run(oracle, R, rl, W, wl, sc)
     try:
         for _ in range(2):
             score.zero_()
             launch()
-            gpu_ctx.synchronize()
+            ctx.synchronize()
             assert_same((score.cpu().numpy(), ei.cpu().numpy(), ej.cpu().numpy()), want, sc.want_coords)
     finally:
         launch.close()
+
+
+@pytest.mark.parametrize("kind", ["linear_coords", "affine"])
+def test_long_planned(gpu_ctx, oracle, kind):
+    """A plan over short and long pairs: one length-bucketed launch, the long
+    launch, the slot-order gather; twice over the same plan."""
+    reads, wins = _short_and_long(700, 9, EDGE, short_seed=8)
+    _planned_twice(gpu_ctx, oracle, scoring(kind), *mpa.pack_batch(reads, wins))
+
+
+@pytest.mark.parametrize("env", [{}, {"MSW_NO_MULTI": "1"}], ids=["multi", "no_multi"])
+@pytest.mark.parametrize("kind", ["linear_coords", "affine"])
+def test_long_planned_in_bucket_order(fresh_ctx, oracle, monkeypatch, kind, env):
+    """The same kind of batch, with reads of 257..384 bases (several KR 17..24
+    buckets), already in the plan's slot order: stable-sorted by (long, rows
+    per lane, 16-column window blocks), the long pairs of one shape, which the
+    heaviest-first sort leaves in place.  The plan's order is then the
+    identity: results straight into pair order, no slot-ordered lengths, no
+    gather, but still an order array under the length-bucketed launch, its
+    wide instance, the long launch and (MSW_NO_MULTI) one launch per bucket."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    reads, wins = _short_and_long(300, 19, [(513, 1030)] * 12, short_seed=18)
+    wide = make_pairs(40, (257, 384), seed=28)
+    reads += [bytes(wide.reads[k, :wide.read_len[k]]) for k in range(wide.n_pairs)]
+    wins += [bytes(wide.wins[k, :wide.win_len[k]]) for k in range(wide.n_pairs)]
+    R, rl, W, wl = mpa.pack_batch(reads, wins)
+    kr, nb = (rl.astype(np.int64) + 15) // 16, (wl.astype(np.int64) + 15) // 16
+    long_pair = (rl > 384) | (wl > 4096)
+    assert np.unique(kr[~long_pair & (kr > 16)]).size >= 2 and int(long_pair.sum()) == 12
+    at = np.lexsort((nb, kr, long_pair))  # stable; the last key is the primary one
+    _planned_twice(fresh_ctx, oracle, scoring(kind), R[at], rl[at], W[at], wl[at])
 
 
 @pytest.mark.parametrize("kind", ["linear", "linear_coords", "affine_coords"])
