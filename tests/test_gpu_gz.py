@@ -4,6 +4,11 @@ Oracles: zlib (the reference implementation of RFC 1951 inflate, via Python's
 zlib / gzip modules) for the inflated bytes, and the host reader
 (msw_fastq.cpp, itself checked against a restatement of aligner.rs:107-178 in
 tests/test_fastq.py) for the parsed reads.  Bit-exact comparisons throughout.
+
+Every stream here is zlib's own compressor's output (or that with a byte
+changed).  Hand-built streams -- match geometry at chosen positions, dynamic
+headers zlib never writes, one stream per error status -- are in
+tests/test_gpu_inflate_streams.py (corpus: tests/deflate_writer.py).
 """
 import gzip
 import os
