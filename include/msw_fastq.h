@@ -3,8 +3,9 @@
  *
  * Replaces process_fastq_file_in_chunks (smith_waterman/src/aligner.rs:107-178)
  * and count_bases_in_fastq (:535-544).  Same record semantics:
- *   - a line is the bytes up to '\n' with a trailing "\r" stripped (Rust
- *     BufRead::lines, :133);
+ *   - a line is the bytes up to '\n', without the '\r' of a "\r\n" (Rust
+ *     BufRead::lines, :133: a file's final line without '\n' keeps a
+ *     trailing '\r');
  *   - a line that is not valid UTF-8 is a read error: it is skipped and not
  *     counted (:155-158); more than 10 errors abort the file (:160-162);
  *   - the sequence line is the 1-based line number with line % 4 == 2 (:138);

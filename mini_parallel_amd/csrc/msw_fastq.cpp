@@ -210,8 +210,9 @@ int64_t parse_pos(const char* s, size_t n) {
 }
 
 // Next raw line (without '\n'); false at end of data or on an I/O error
-// (*io_err set).  The pointer stays valid until the next call.
-bool next_line(msw_fastq* fq, const char** line, size_t* len, int* io_err) {
+// (*io_err set).  *had_nl: the line ended at a '\n' (false only for a file's
+// final line without one).  The pointer stays valid until the next call.
+bool next_line(msw_fastq* fq, const char** line, size_t* len, int* io_err, bool* had_nl) {
     for (;;) {
         if (fq->head < fq->tail) {
             const char* start = fq->buf.data() + fq->head;
@@ -229,6 +230,7 @@ bool next_line(msw_fastq* fq, const char** line, size_t* len, int* io_err) {
                     *line = start;
                     *len = n;
                 }
+                *had_nl = true;
                 return true;
             }
             fq->carry.append(start, fq->tail - fq->head);
@@ -240,6 +242,7 @@ bool next_line(msw_fastq* fq, const char** line, size_t* len, int* io_err) {
             fq->carry.clear();
             *line = fq->last.data();
             *len = fq->last.size();
+            *had_nl = false;
             return true;
         }
         const long got = fq->raw ? bgzf_fill(fq, fq->buf.data(), kBlock)
@@ -261,7 +264,8 @@ int next_sequence(msw_fastq* fq, const char** seq, size_t* len, int64_t* pos, bo
         const char* line;
         size_t n;
         int io_err = 0;
-        if (!next_line(fq, &line, &n, &io_err)) {
+        bool had_nl = false;
+        if (!next_line(fq, &line, &n, &io_err, &had_nl)) {
             if (!io_err) return 0;
             int zerr = 0;
             const char* msg = fq->raw ? fq->io_msg.c_str() : gzerror(fq->gz, &zerr);
@@ -270,7 +274,9 @@ int next_sequence(msw_fastq* fq, const char** seq, size_t* len, int64_t* pos, bo
                                  (unsigned long long)fq->lines);
             return set_error(MSW_E_INVALID, "Error reading %s: %s", fq->path.c_str(), msg ? msg : "");
         }
-        if (n && line[n - 1] == '\r') --n;  // CRLF, as BufRead::lines
+        // CRLF, as BufRead::lines: a '\r' goes only with the '\n' after it (a
+        // file's final line without '\n' keeps a trailing '\r')
+        if (had_nl && n && line[n - 1] == '\r') --n;
         if (!valid_utf8((const unsigned char*)line, n)) {
             if (++fq->errors > 10)
                 return set_error(MSW_E_INVALID, "Too many read errors (>10), stopping at line %llu",

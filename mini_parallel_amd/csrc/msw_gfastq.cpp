@@ -892,7 +892,10 @@ int next_span(msw_gfastq* g) {
                 g->path.c_str(), g->mem.size(), used / 1e6, obytes / 1e6, t_read - t0, t_join - t0, t_reg - t_join,
                 t_read - t_reg, t_a - t_read, t_run - t_read, pre ? "uploaded ahead" : (in_place ? "in place" : "upload"),
                 now_ms() - t_a, t_unpin - t_a, (unsigned long long)o.reads);
-    if (o.err_over)
+    // both in one span: whichever comes first in the file, as the host reader
+    // (the too-long read is valid line too_long_line; err_line valid lines
+    // precede the 11th invalid one)
+    if (o.err_over && !(o.too_long && o.too_long_line <= o.err_line))
         return set_error(MSW_E_INVALID, "Too many read errors (>10), stopping at line %llu",
                          (unsigned long long)o.err_line);
     if (o.too_long)

@@ -64,7 +64,7 @@ hipError_t parse_preload();
 // ---------------------------------------------------------------------------
 // FASTQ parse of an inflated span (msw_parse.hip).  The span buffer holds the
 // previous span's unfinished line, then this span's bytes.  Semantics of
-// aligner.rs:128-170: lines end at '\n', one trailing '\r' stripped; a line
+// aligner.rs:128-170: lines end at '\n', the '\r' of a "\r\n" stripped; a line
 // that is not valid UTF-8 is skipped and not counted (an error); valid line
 // number (1-based, over the whole file) % 4 == 2 is a sequence.
 // ---------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 // msw_parse.hip -- FASTQ record parse of an inflated span on gfx950.
 //
 // Semantics of process_fastq_file_in_chunks (smith_waterman/src/aligner.rs:
-// 107-178, as restated by msw_fastq.cpp): a line is the bytes up to '\n' with
-// one trailing '\r' stripped; a line that is not valid UTF-8 is skipped and
+// 107-178, as restated by msw_fastq.cpp): a line is the bytes up to '\n'
+// without the '\r' of a "\r\n"; a line that is not valid UTF-8 is skipped and
 // not counted (:155-163, an error; more than 10 abort the file); the valid
 // line whose 1-based number % 4 == 2 is a sequence; the "pos=" tag of the
 // header before it gives the read's window position (synthetic datasets).
@@ -71,11 +71,13 @@ __device__ __forceinline__ uint32_t line_start(const ParseBufs& b, uint64_t k) {
     return k ? b.line_end[k - 1] + 1u : b.begin;
 }
 
-// [start, end) of line k without its trailing '\r'
+// [start, end) of line k without the '\r' of its "\r\n".  As BufRead::lines,
+// a '\r' goes only with the '\n' after it: the file's final line without
+// '\n' (the one line whose end is len, not a newline's offset) keeps it.
 __device__ __forceinline__ void line_bounds(const ParseBufs& b, uint64_t k, uint32_t& st, uint32_t& en) {
     st = line_start(b, k);
     en = b.line_end[k];
-    if (en > st && b.buf[en - 1] == '\r') --en;
+    if (en > st && en != (uint32_t)b.len && b.buf[en - 1] == '\r') --en;
 }
 
 // Strict UTF-8 (what Rust's String conversion in BufRead::lines checks).

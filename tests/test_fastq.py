@@ -14,11 +14,12 @@ def reference_chunks(data: bytes, n: int):
     UTF-8 lines are errors that are skipped and not counted, line % 4 == 2 is
     the sequence, chunks of n then a final partial one; >10 errors -> Err."""
     lines = data.split(b"\n")
+    unterminated = len(lines) - 1 if lines[-1] != b"" else -1  # a final line without \n keeps its \r
     if lines and lines[-1] == b"":
         lines.pop()
     chunks, chunk, count, errors = [], [], 0, 0
-    for raw in lines:
-        if raw.endswith(b"\r"):
+    for k, raw in enumerate(lines):
+        if raw.endswith(b"\r") and k != unterminated:
             raw = raw[:-1]
         try:
             s = raw.decode("utf-8")

@@ -8,7 +8,10 @@ tests/test_fastq.py) for the parsed reads.  Bit-exact comparisons throughout.
 Every stream here is zlib's own compressor's output (or that with a byte
 changed).  Hand-built streams -- match geometry at chosen positions, dynamic
 headers zlib never writes, one stream per error status -- are in
-tests/test_gpu_inflate_streams.py (corpus: tests/deflate_writer.py).
+tests/test_gpu_inflate_streams.py (corpus: tests/deflate_writer.py).  The
+record parse against a reference of its own (not the host reader), with chosen
+bytes at the span cuts, is in tests/test_gpu_parse_cases.py (corpus:
+tests/fastq_cases.py).
 """
 import gzip
 import os
