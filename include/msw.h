@@ -282,6 +282,63 @@ int msw_align_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
                            uint32_t window, uint32_t max_read_len, msw_out_t* out, uint16_t* win_len_out,
                            void* stream);
 
+/* The window of a pair in the device-resident genome calls
+ * (msw_align_reads_device, msw_trace_reads_device): window p is
+ * genome[win_pos[p], win_pos[p] + W), W = `window`, or 2 x read_len[p] capped
+ * at 4096 when `window` is 0, clipped at the genome end; win_pos[p] < 0 or
+ * >= the genome length is an empty window.
+ *
+ * Traceback straight from the genome: arguments and windows are those of
+ * msw_align_reads_device, `ends` is what that call wrote with want_coords = 1
+ * for the same arguments, and `tr` is filled as by msw_trace_batch_device
+ * (overflow contract included; start_j and end_j are window-relative).  The
+ * windows are read from the genome itself: the call needs no cut slab and
+ * nothing an earlier call left behind.  Range as for traceback:
+ * max_read_len <= 384 and the window bound (window, or 2 x max_read_len capped
+ * at 4096) <= 4096, else MSW_E_RANGE.  Enqueued on `stream`, no host
+ * synchronisation. */
+int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                           uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
+                           void* stream);
+
+/* Alignment records: what a consumer of alignments needs beside the trace,
+ * and the CIGARs packed into one stream instead of [n][cigar_stride] rows.
+ * Per read with score > 0 whose trace did not overflow:
+ *  - ops: S start_i when start_i > 0, the traced ops, S (read_len - 1 - end_i)
+ *    when that is > 0, so a packed CIGAR consumes exactly read_len read bases;
+ *  - nm (SAM's NM): the I lengths plus the D lengths plus the M columns whose
+ *    read byte differs from the genome byte (byte equality, as the scorer),
+ *    walking the ops from (start_i, ref_pos).
+ * Score 0 or an empty pair: ref_pos -1, nm 0, no ops.  A read whose trace
+ * overflowed (n_cigar > cigar_stride): nm -1, no ops, counted in n_overflow;
+ * its ref_pos is valid.  When the total exceeds cigar_cap, cigar_off is still
+ * complete and nothing is written at or past cigar + cigar_cap. */
+typedef struct {
+    int64_t*  ref_pos;    /* [n]   genome coordinate of the first aligned base = win_pos + start_j; -1 when score == 0 */
+    int32_t*  nm;         /* [n]   edit distance; 0 when score == 0; -1 when the read's trace overflowed */
+    uint32_t* cigar_off;  /* [n+1] exclusive prefix sum of ops per read, soft clips included; [n] = total */
+    uint32_t* cigar;      /* packed ops, len << 4 | op, M=0 I=1 D=2 S=4 (BAM codes) */
+    uint64_t  cigar_cap;  /* ops `cigar` holds */
+    uint32_t* n_overflow; /* [1] reads with n_cigar > cigar_stride in the trace: they contribute 0 ops */
+} msw_aln_t;
+
+/* Device-resident: every array is device memory; `ends` and `tr` are the
+ * scoring and trace results of these reads (n <= 2^31 - 1).  Enqueued on
+ * `stream` with no host synchronisation; temporaries are stream-ordered. */
+int msw_aln_pack_device(msw_ctx* ctx, const msw_genome* g, const uint8_t* reads, const uint16_t* read_len,
+                        uint32_t read_stride, const int64_t* win_pos, uint64_t n, const msw_out_t* ends,
+                        const msw_trace_t* tr, msw_aln_t* aln, void* stream);
+
+/* Host memory, synchronous (like msw_align_batch_trace): scores batch (as
+ * msw_align_reads, coordinates forced), traces and packs, in chunks of
+ * `chunk_pairs` (0 = 65536); cigar_off is one prefix sum over the whole
+ * batch.  The trace stride used inside is exact, so *n_overflow is 0.  A
+ * cigar_cap below cigar_off[n] still returns MSW_OK with cigar_off complete;
+ * `cigar` is then unspecified.  Reads <= 384, requested windows <= 4096. */
+int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* batch,
+                          msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

@@ -31,6 +31,7 @@ EXPORTED = (
     "msw_align_reads_async", "msw_genome_cut_device", "msw_ctx_stats", "msw_align_reads_device",
     "msw_memcpy_d2h_async", "msw_fence_record", "msw_fence_wait", "msw_ctx_prepare",
     "msw_stream_create", "msw_stream_destroy", "msw_trace_batch_device", "msw_align_batch_trace",
+    "msw_trace_reads_device", "msw_aln_pack_device", "msw_align_reads_trace",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -76,6 +77,11 @@ class TraceT(ctypes.Structure):
                 ("cigar", ctypes.c_void_p), ("cigar_stride", ctypes.c_uint32)]
 
 
+class AlnT(ctypes.Structure):
+    _fields_ = [("ref_pos", ctypes.c_void_p), ("nm", ctypes.c_void_p), ("cigar_off", ctypes.c_void_p),
+                ("cigar", ctypes.c_void_p), ("cigar_cap", ctypes.c_uint64), ("n_overflow", ctypes.c_void_p)]
+
+
 class DevReadsT(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_void_p), ("read_len", ctypes.c_void_p), ("pos", ctypes.c_void_p),
                 ("read_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("first_read", ctypes.c_uint64),
@@ -117,6 +123,13 @@ def _declare(L):
                                        ctypes.POINTER(TraceT), ctypes.c_uint32, ctypes.c_uint32, P]),
         "msw_align_batch_trace": (I, [P, ctypes.POINTER(ScoringT), ctypes.POINTER(BatchT), ctypes.POINTER(OutT),
                                       ctypes.POINTER(TraceT), ctypes.c_uint64]),
+        "msw_trace_reads_device": (I, [P, ctypes.POINTER(ScoringT), P, P, P, ctypes.c_uint32, P, ctypes.c_uint64,
+                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(OutT),
+                                       ctypes.POINTER(TraceT), P]),
+        "msw_aln_pack_device": (I, [P, P, P, P, ctypes.c_uint32, P, ctypes.c_uint64, ctypes.POINTER(OutT),
+                                    ctypes.POINTER(TraceT), ctypes.POINTER(AlnT), P]),
+        "msw_align_reads_trace": (I, [P, ctypes.POINTER(ScoringT), P, ctypes.POINTER(ReadBatchT),
+                                      ctypes.POINTER(OutT), ctypes.POINTER(AlnT), ctypes.c_uint64]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, BatchT, DeviceInfoT, MswError, OutT, ReadBatchT, ScoringT, StatsT, TraceT,
+from ._lib import (MSW_E_INVALID, AlnT, BatchT, DeviceInfoT, MswError, OutT, ReadBatchT, ScoringT, StatsT, TraceT,
                    check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
@@ -304,6 +304,81 @@ class Context:
                                     ctypes.byref(out), chunk_pairs))
         return score, ei, ej
 
+    # -- alignment records: reads against the genome, traced and packed ----------------
+    def align_reads_trace(self, genome: "Genome", reads: np.ndarray, read_len: np.ndarray,
+                          win_pos: np.ndarray, win_len: np.ndarray, scoring: Scoring = LINEAR,
+                          chunk_pairs: int = 0, cigar_cap: Optional[int] = None):
+        """Score read p against genome[win_pos[p] : win_pos[p] + win_len[p]]
+        like :meth:`align_reads` and trace it (msw_align_reads_trace).  Returns
+        (score, end_i, end_j, ref_pos int64[B], nm int32[B], cigars):
+        ``ref_pos`` is the genome coordinate of the first aligned base (-1
+        when the score is 0), ``nm`` the edit distance, ``cigars[p]`` a uint32
+        array of BAM-encoded ops with soft clips (S = 4), so that it consumes
+        the whole read; ``cigars.n_cigar`` holds the op counts.  ``cigar_cap``
+        is the first guess at the total number of ops (default 4 per read);
+        when it is too small the call is repeated once with the exact size."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        win_pos = np.ascontiguousarray(win_pos, dtype=np.int64)
+        win_len = np.ascontiguousarray(win_len, dtype=np.uint16)
+        B = reads.shape[0]
+        if read_len.shape[0] != B or win_pos.shape[0] != B or win_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of pairs")
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0,
+                           _ptr(win_pos), _ptr(win_len), B)
+        sc = _scoring_c(scoring)
+        cap = 4 * B if cigar_cap is None else int(cigar_cap)
+        while True:
+            (score, ei, ej), out = _outputs(B, True)
+            ref_pos, nm = np.empty(B, np.int64), np.empty(B, np.int32)
+            off = np.zeros(B + 1, np.uint32)
+            cig = np.zeros(max(cap, 1), np.uint32)
+            ovf = np.zeros(1, np.uint32)
+            aln = AlnT(_fresh_ptr(ref_pos), _fresh_ptr(nm), _fresh_ptr(off), _fresh_ptr(cig), cap, _fresh_ptr(ovf))
+            check(lib().msw_align_reads_trace(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch),
+                                              ctypes.byref(out), ctypes.byref(aln), chunk_pairs))
+            total = int(off[B])
+            if total > cap:
+                cap = total  # once: the offsets do not depend on the capacity
+                continue
+            break
+        cigars = CigarList(cig[off[p]:off[p + 1]].copy() for p in range(B))
+        cigars.n_cigar = np.diff(off.astype(np.int64)).astype(np.int32)
+        return score, ei, ej, ref_pos, nm, cigars
+
+    def trace_reads_device(self, genome: "Genome", reads_ptr: int, read_len_ptr: int, read_stride: int,
+                           win_pos_ptr: int, n: int, window: int, max_read_len: int, score_ptr: int,
+                           end_i_ptr: int, end_j_ptr: int, start_i_ptr: int, start_j_ptr: int,
+                           n_cigar_ptr: int, cigar_ptr: int, cigar_stride: int, scoring: Scoring = LINEAR,
+                           stream: int = 0) -> None:
+        """Enqueue one traceback pass over device-resident reads against
+        windows read straight from the genome (msw_trace_reads_device): the
+        arguments of msw_align_reads_device, whose outputs with coordinates
+        are score / end_i / end_j."""
+        ends = OutT(score_ptr, end_i_ptr, end_j_ptr)
+        tr = TraceT(start_i_ptr, start_j_ptr, n_cigar_ptr, cigar_ptr, cigar_stride)
+        sc = _scoring_c(scoring)
+        check(lib().msw_trace_reads_device(self.handle, ctypes.byref(sc), genome.handle, ctypes.c_void_p(reads_ptr),
+                                           ctypes.c_void_p(read_len_ptr), read_stride, ctypes.c_void_p(win_pos_ptr),
+                                           n, window, max_read_len, ctypes.byref(ends), ctypes.byref(tr),
+                                           ctypes.c_void_p(stream or None)))
+
+    def aln_pack_device(self, genome: "Genome", reads_ptr: int, read_len_ptr: int, read_stride: int,
+                        win_pos_ptr: int, n: int, score_ptr: int, end_i_ptr: int, end_j_ptr: int,
+                        start_i_ptr: int, start_j_ptr: int, n_cigar_ptr: int, cigar_ptr: int, cigar_stride: int,
+                        ref_pos_ptr: int, nm_ptr: int, cigar_off_ptr: int, packed_ptr: int, cigar_cap: int,
+                        n_overflow_ptr: int, stream: int = 0) -> None:
+        """Enqueue the alignment records of a traced device-resident batch
+        (msw_aln_pack_device): ref_pos, nm, the offsets and the packed,
+        soft-clipped ops."""
+        ends = OutT(score_ptr, end_i_ptr, end_j_ptr)
+        tr = TraceT(start_i_ptr, start_j_ptr, n_cigar_ptr, cigar_ptr, cigar_stride)
+        aln = AlnT(ref_pos_ptr, nm_ptr, cigar_off_ptr, packed_ptr or None, cigar_cap, n_overflow_ptr)
+        check(lib().msw_aln_pack_device(self.handle, genome.handle, ctypes.c_void_p(reads_ptr),
+                                        ctypes.c_void_p(read_len_ptr), read_stride, ctypes.c_void_p(win_pos_ptr), n,
+                                        ctypes.byref(ends), ctypes.byref(tr), ctypes.byref(aln),
+                                        ctypes.c_void_p(stream or None)))
+
     # -- HBM-resident batches ----------------------------------------------------------
     def align_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int,
                            win_len_ptr: int, read_stride: int, win_stride: int, n_pairs: int,
@@ -419,11 +494,14 @@ class CigarList(list):
 
 
 def cigar_string(ops) -> str:
-    """BAM-encoded ops (len << 4 | op) -> text, e.g. ``"12M1I30M"``; no ops
-    (score 0) -> ``"*"``."""
+    """BAM-encoded ops (len << 4 | op, M=0 I=1 D=2 S=4) -> text, e.g.
+    ``"3S12M1I30M"``; no ops (score 0) -> ``"*"``."""
     if ops is None or len(ops) == 0:
         return "*"
-    return "".join(f"{int(o) >> 4}{'MID'[int(o) & 15]}" for o in ops)
+    return "".join(f"{int(o) >> 4}{_CIGAR_CHARS[int(o) & 15]}" for o in ops)
+
+
+_CIGAR_CHARS = {0: "M", 1: "I", 2: "D", 4: "S"}
 
 
 class Pending:

@@ -122,7 +122,7 @@ struct Args {
     bool has_seq1 = false, has_seq2 = false, files = false, gpu = false, test_wgs = false, full_wgs = false;
     bool cigar = false;
     long chunk_size = 1, num_files = -1;
-    std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out;
+    std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out, alignments_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;
 };
 
@@ -150,6 +150,10 @@ void usage() {
         "      --checkpoint-dir DIR     where checkpoint_<run_id>.json lives (default .)\n"
         "      --scores-out DIR         --full-wgs sw: per-read results, one <lane file>.scores per file\n"
         "                               (8 bytes per read in file order: i32 score, i16 end_i, i16 end_j)\n"
+        "      --alignments-out DIR     --full-wgs sw, BGZF lane files read on the GPU: per-read alignments, one\n"
+        "                               <lane file>.aln per file (genome position, score, NM, CIGAR with soft\n"
+        "                               clips; blocks of reads, see DESIGN.md 4.10).  Reads <= 384 and windows\n"
+        "                               <= 4096 bases.  Not available with the host (gzip) lane reader.\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -187,6 +191,7 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--checkpoint-dir") a.checkpoint_dir = v();
         else if (s == "--json") a.json = v();
         else if (s == "--scores-out") a.scores_out = v();
+        else if (s == "--alignments-out") a.alignments_out = v();
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -195,6 +200,15 @@ Args parse_args(int argc, char** argv) {
     if (a.gap_extend < 0) a.gap_extend = a.gap_model == "affine" ? 1 : 2;
     if (a.cigar && (a.score_mode != "sw" || a.full_wgs || a.test_wgs))
         die("error: --cigar needs --score-mode sw and one pair of sequences (-1 / -2, direct or with -f)");
+    if (!a.alignments_out.empty()) {
+        // traceback's range (include/msw.h): refused here, before any file is opened
+        if (!a.full_wgs || a.score_mode != "sw") die("error: --alignments-out needs --full-wgs --score-mode sw");
+        if (a.window > 4096) die("error: --alignments-out traces windows of at most 4096 bases (--window)");
+        if (atol(env_or("MSW_MAX_READ_LEN", "256").c_str()) > 384)
+            die("error: --alignments-out traces reads of at most 384 bases (MSW_MAX_READ_LEN)");
+        if (env_or("MSW_GPU_INFLATE", "1") == "0")
+            die("error: --alignments-out needs the GPU lane reader (MSW_GPU_INFLATE=0 selects the host reader)");
+    }
     return a;
 }
 
@@ -540,6 +554,7 @@ struct FileState {
     std::atomic<int> outstanding{0};
     std::atomic<bool> reader_done{false}, failed{false}, finished{false};
     int scores_fd = -1;  // --scores-out: per-read records, written at the read's offset
+    int aln_fd = -1;     // --alignments-out: blocks appended as the batches settle
     Clock::time_point t0;
     double ms = 0;
     std::string error;
@@ -739,6 +754,10 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
             close(f.scores_fd);
             f.scores_fd = -1;
         }
+        if (f.aln_fd >= 0) {
+            close(f.aln_fd);
+            f.aln_fd = -1;
+        }
         FileCheckpoint c;
         c.file_path = f.path;
         c.file_index = gidx[fi];
@@ -762,6 +781,12 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
     // the host for the i64 sums and --scores-out, one batch behind the GPU.
     bool gpu_reader = sw && env_or("MSW_GPU_INFLATE", "1") != "0" && !todo.empty();
     for (size_t fi : todo) gpu_reader = gpu_reader && msw_is_bgzf(files[fi].c_str());
+    const bool aln = !a.alignments_out.empty();
+    if (aln && !todo.empty() && !gpu_reader)
+        die("error: --alignments-out needs BGZF lane files (the GPU lane reader); the host reader does not write "
+            "alignments");
+    // per-read output of either kind: best cells, 256k-read batches, two streams
+    const bool per_read = !a.scores_out.empty() || aln;
     if (gpu_reader) {
         std::atomic<unsigned long long> gz_in{0}, gz_out{0};
         // reads per scoring launch; wide slabs (MSW_MAX_READ_LEN) keep a batch's
@@ -770,7 +795,7 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
         // 256k reads, so one batch's records are written while the next one
         // scores (config 3 from FASTQ: 17.4-18.0 -> 16.3-16.4 ms per 1 M reads,
         // profiles/r05/c3f/c3f_batch_ab.jsonl); sums only: 1 M-read batches
-        const uint64_t batch_default = a.scores_out.empty() ? (1u << 20) : (1u << 18);
+        const uint64_t batch_default = per_read ? (1u << 18) : (1u << 20);
         const uint64_t batch = std::max<uint64_t>(
             chunk, std::min<uint64_t>(strtoull(env_or("MSW_GFASTQ_BATCH", std::to_string(batch_default)).c_str(),
                                                nullptr, 10),
@@ -806,7 +831,7 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                 // batches that fill the GPU alone) keep one stream: config 4
                 // measured 3 % slower on two.
                 void* st2 = nullptr;
-                if (!a.scores_out.empty() && msw_stream_create(ctx.h, &st2) != MSW_OK)
+                if (per_read && msw_stream_create(ctx.h, &st2) != MSW_OK)
                     die(std::string("GPU stream: ") + msw_last_error());
                 void* const streams[2] = {nullptr, st2};
                 const double t_ctx = ms_since(ts0);
@@ -829,7 +854,7 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                 // timed region: profiles/r06/c3f/setup_ab.jsonl)
                 pending = claim();
                 if (pending != kNone) (void)msw_gfastq_prefetch(gr, st[pending]->path.c_str());
-                const msw_scoring_t sc = scoring_of(a, !a.scores_out.empty());
+                const msw_scoring_t sc = scoring_of(a, per_read);
                 msw_genome* gen = nullptr;
                 const auto tg0 = Clock::now();
                 const std::string& ref_seq = genome();
@@ -852,7 +877,28 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                     uint64_t fence = 0;  // after the batch's copy-back (msw_fence_record)
                     bool live = false;
                     uint64_t* rec = nullptr;  // --scores-out: the batch's records (recbuf)
+                    // --alignments-out: the batch's trace, its records and packed ops
+                    int16_t *d_si = nullptr, *d_sj = nullptr;
+                    int32_t *d_nc = nullptr, *d_nm = nullptr;
+                    int64_t* d_ref = nullptr;
+                    uint32_t* d_off = nullptr;    // [batch + 2]: offsets, then the overflow count at [batch + 1]
+                    uint32_t* d_rows = nullptr;   // [batch][aln_stride]
+                    uint32_t* d_exact = nullptr;  // rows at the exact stride, made by the first batch that needs them
+                    uint64_t exact_words = 0;
+                    uint32_t *d_ops = nullptr, *h_ops = nullptr;  // packed ops, device / pinned
+                    uint64_t ops_cap = 0;
+                    uint8_t* ha = nullptr;  // pinned: ref_pos i64 | nm i32 | off u32 [batch + 2]
+                    msw_dev_reads_t d{};    // the batch's device arrays (valid until the reader's call after next)
+                    void* stream = nullptr;
+                    uint32_t stride = 0;           // of the rows the offsets on the host were packed from
+                    const uint32_t* rows = nullptr;
+                    uint64_t aln_fence = 0, n_ops = 0;
+                    bool aln_pending = false, aln_ok = false;
+                    std::vector<uint8_t> block;    // the .aln block of the batch
                 } res[2];
+                // ops per read the first trace's rows hold (tests set 1 to force the second trace)
+                const uint32_t aln_stride =
+                    aln ? (uint32_t)std::min(4480L, std::max(1L, atol(env_or("MSW_CLI_CIGAR_STRIDE", "16").c_str()))) : 16u;
                 const size_t rec = 4 + 2 + 2 + 2 + 2;
                 for (Res& r : res) {
                     r.d_score = (int32_t*)msw_dev_alloc(ctx.h, batch * 4);
@@ -873,6 +919,112 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                     res[0].rec = recbuf.get();
                     res[1].rec = recbuf.get() + batch;
                 }
+                if (aln) {
+                    for (Res& r : res) {
+                        r.d_si = (int16_t*)msw_dev_alloc(ctx.h, batch * 2);
+                        r.d_sj = (int16_t*)msw_dev_alloc(ctx.h, batch * 2);
+                        r.d_nc = (int32_t*)msw_dev_alloc(ctx.h, batch * 4);
+                        r.d_nm = (int32_t*)msw_dev_alloc(ctx.h, batch * 4);
+                        r.d_ref = (int64_t*)msw_dev_alloc(ctx.h, batch * 8);
+                        r.d_off = (uint32_t*)msw_dev_alloc(ctx.h, (batch + 2) * 4);
+                        r.d_rows = (uint32_t*)msw_dev_alloc(ctx.h, batch * aln_stride * 4);
+                        // every read within the stride: at most stride + 2 ops each
+                        r.ops_cap = batch * ((uint64_t)aln_stride + 2);
+                        r.d_ops = (uint32_t*)msw_dev_alloc(ctx.h, r.ops_cap * 4);
+                        r.h_ops = (uint32_t*)msw_host_alloc(r.ops_cap * 4);
+                        r.ha = (uint8_t*)msw_host_alloc(batch * 12 + (batch + 2) * 4);
+                        if (!r.d_si || !r.d_sj || !r.d_nc || !r.d_nm || !r.d_ref || !r.d_off || !r.d_rows || !r.d_ops ||
+                            !r.h_ops || !r.ha)
+                            die(std::string("GPU lane reader alignment buffers: ") + msw_last_error());
+                        r.block.reserve(32 + batch * 24 + batch * 12);
+                    }
+                }
+                // --alignments-out, GPU side of a batch on its stream: trace
+                // straight from the genome (or only pack again, into grown
+                // buffers), pack, and copy back the records and offsets -- the
+                // packed ops follow once the host knows how many there are.
+                auto aln_run = [&](Res& r, uint32_t stride, uint32_t* rows, bool trace) -> bool {
+                    const msw_dev_reads_t& d = r.d;
+                    const msw_out_t o{r.d_score, r.d_ei, r.d_ej};
+                    msw_trace_t tr{r.d_si, r.d_sj, r.d_nc, rows, stride};
+                    msw_aln_t al{r.d_ref, r.d_nm, r.d_off, r.d_ops, r.ops_cap, r.d_off + batch + 1};
+                    r.stride = stride;
+                    r.rows = rows;
+                    return (!trace || msw_trace_reads_device(ctx.h, &sc, gen, d.reads, d.read_len, d.read_stride, d.pos,
+                                                             d.n, a.window > 0 ? (uint32_t)a.window : 0u, d.max_len,
+                                                             &o, &tr, r.stream) == MSW_OK) &&
+                           msw_aln_pack_device(ctx.h, gen, d.reads, d.read_len, d.read_stride, d.pos, d.n, &o, &tr, &al,
+                                               r.stream) == MSW_OK &&
+                           msw_memcpy_d2h_async(ctx.h, r.ha, r.d_ref, d.n * 8, r.stream) == MSW_OK &&
+                           msw_memcpy_d2h_async(ctx.h, r.ha + batch * 8, r.d_nm, d.n * 4, r.stream) == MSW_OK &&
+                           msw_memcpy_d2h_async(ctx.h, r.ha + batch * 12, r.d_off, (d.n + 1) * 4, r.stream) == MSW_OK &&
+                           msw_memcpy_d2h_async(ctx.h, r.ha + batch * 12 + (batch + 1) * 4, r.d_off + batch + 1, 4,
+                                                r.stream) == MSW_OK &&
+                           msw_fence_record(ctx.h, r.stream, &r.aln_fence) == MSW_OK;
+                };
+                // Host side, while the batch's reads are still on the device
+                // (before the reader's call after next): a batch with reads
+                // past the stride is traced and packed once more at the exact
+                // stride, so the file's alignments are always complete; then
+                // the packed ops actually used are copied back and r.fence
+                // covers everything settle_work reads.
+                auto aln_finish = [&](Res& r) {
+                    if (!r.live || !r.aln_pending) return;
+                    r.aln_pending = false;
+                    r.aln_ok = false;
+                    r.n_ops = 0;
+                    FileState& f = *st[r.fi];
+                    const uint32_t* off = (const uint32_t*)(r.ha + batch * 12);
+                    bool ok = true, exact = false;
+                    for (;;) {
+                        if (!(ok = msw_fence_wait(ctx.h, r.aln_fence) == MSW_OK)) break;
+                        if (off[batch + 1] != 0 && !exact) {
+                            exact = true;  // no alignment has more ops than rows + columns
+                            const uint32_t max_win =
+                                a.window > 0 ? (uint32_t)a.window : std::min<uint32_t>(2u * r.d.max_len, 4096u);
+                            const uint32_t stride = r.d.max_len + max_win;
+                            if (r.n * stride > r.exact_words) {
+                                if (r.d_exact) msw_dev_free(ctx.h, r.d_exact);
+                                r.exact_words = r.n * stride;
+                                r.d_exact = (uint32_t*)msw_dev_alloc(ctx.h, r.exact_words * 4);
+                                if (!(ok = r.d_exact != nullptr)) {
+                                    r.exact_words = 0;
+                                    break;
+                                }
+                            }
+                            if (!(ok = aln_run(r, stride, r.d_exact, true))) break;
+                            continue;
+                        }
+                        if (off[r.n] > r.ops_cap) {  // after an exact trace only: grow, pack again
+                            msw_dev_free(ctx.h, r.d_ops);
+                            msw_host_free(r.h_ops);
+                            r.ops_cap = off[r.n];
+                            r.d_ops = (uint32_t*)msw_dev_alloc(ctx.h, r.ops_cap * 4);
+                            r.h_ops = (uint32_t*)msw_host_alloc(r.ops_cap * 4);
+                            if (!r.d_ops || !r.h_ops) die(std::string("GPU lane reader alignment buffers: ") + msw_last_error());
+                            if (!(ok = aln_run(r, r.stride, const_cast<uint32_t*>(r.rows), false))) break;
+                            continue;
+                        }
+                        break;
+                    }
+                    if (ok) {
+                        r.n_ops = off[r.n];
+                        ok = (r.n_ops == 0 ||
+                              msw_memcpy_d2h_async(ctx.h, r.h_ops, r.d_ops, r.n_ops * 4, r.stream) == MSW_OK);
+                    }
+                    if (!ok) {
+                        fprintf(stderr, "  GPU %d alignment records error: %s\n", gi, msw_last_error());
+                        f.failed = true;
+                        (void)msw_synchronize(ctx.h);
+                    }
+                    r.aln_ok = ok;
+                    // what settle_work waits on
+                    if (msw_fence_record(ctx.h, r.stream, &r.fence) != MSW_OK) {
+                        f.failed = true;
+                        r.aln_ok = false;
+                        r.fence = 0;
+                    }
+                };
                 const double t_res = ms_since(tres0);
                 unsigned long long alg_local = 0;
                 // per file this worker has open: batches in flight, reader done
@@ -926,6 +1078,40 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                         fprintf(stderr, "  error writing scores for %s\n", f.path.c_str());
                         f.failed = true;
                     }
+                    if (f.aln_fd >= 0 && r.aln_ok) {
+                        // one self-contained block: header, records, packed ops
+                        const int64_t* ref = (const int64_t*)r.ha;
+                        const int32_t* nm = (const int32_t*)(r.ha + batch * 8);
+                        const uint32_t* off = (const uint32_t*)(r.ha + batch * 12);
+                        r.block.resize(32 + r.n * 24 + r.n_ops * 4);
+                        uint8_t* b = r.block.data();
+                        const uint32_t head[4] = {0x4157534Du /* "MSWA" */, 1u, (uint32_t)r.n, (uint32_t)r.n_ops};
+                        memset(b, 0, 32);
+                        memcpy(b, head, 8);
+                        memcpy(b + 8, &r.first, 8);
+                        memcpy(b + 16, head + 2, 8);
+                        uint8_t* q = b + 32;
+                        for (uint64_t i = 0; i < r.n; ++i, q += 24) {
+                            const uint32_t n_ops = off[i + 1] - off[i];
+                            memcpy(q, ref + i, 8);
+                            memcpy(q + 8, sc32 + i, 4);
+                            memcpy(q + 12, nm + i, 4);
+                            memcpy(q + 16, &n_ops, 4);
+                            memcpy(q + 20, ei + i, 2);
+                            memcpy(q + 22, ej + i, 2);
+                        }
+                        if (r.n_ops) memcpy(q, r.h_ops, r.n_ops * 4);
+                        size_t done = 0;
+                        while (done < r.block.size()) {
+                            const ssize_t w = write(f.aln_fd, b + done, r.block.size() - done);
+                            if (w <= 0) break;
+                            done += (size_t)w;
+                        }
+                        if (done != r.block.size()) {
+                            fprintf(stderr, "  error writing alignments for %s\n", f.path.c_str());
+                            f.failed = true;
+                        }
+                    }
                     return out;
                 };
                 auto settle_book = [&](Res& r, const Settled& o) {
@@ -936,6 +1122,7 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                 };
                 auto settle = [&](Res& r) {
                     if (!r.live) return;
+                    if (aln) aln_finish(r);
                     r.live = false;
                     settle_book(r, settle_work(r));
                 };
@@ -981,6 +1168,14 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                             f.scores_fd = open(out.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
                             if (f.scores_fd < 0) die("error: cannot create " + out);
                         }
+                        if (aln) {
+                            const size_t slash = f.path.find_last_of('/');
+                            const std::string out = a.alignments_out + "/" +
+                                                    (slash == std::string::npos ? f.path : f.path.substr(slash + 1)) +
+                                                    ".aln";
+                            f.aln_fd = open(out.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+                            if (f.aln_fd < 0) die("error: cannot create " + out);
+                        }
                         printf("  Processing file %zu/%zu: %s (GPU inflate)\n", gidx[fi] + 1, n_lane_files,
                                f.path.c_str());
                         fflush(stdout);
@@ -1008,6 +1203,8 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                     FileState& f = *st[fi];
                     msw_dev_reads_t d;
                     void* const bs = streams[cur];  // this batch's stream
+                    // the reader's next batch reuses the slab of the batch before last
+                    if (aln) aln_finish(res[cur]);
                     if (msw_gfastq_next(gr, bs, &d) != MSW_OK) {
                         f.error = msw_last_error();
                         fprintf(stderr, "  Error reading %s: %s\n", f.path.c_str(), f.error.c_str());
@@ -1035,10 +1232,14 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                           msw_memcpy_d2h_async(ctx.h, r.h + batch * 6, r.d_ej, d.n * 2, bs) != MSW_OK)) ||
                         msw_memcpy_d2h_async(ctx.h, r.h + batch * 8, d.read_len, d.n * 2, bs) != MSW_OK ||
                         msw_memcpy_d2h_async(ctx.h, r.h + batch * 10, r.d_wlen, d.n * 2, bs) != MSW_OK ||
-                        msw_fence_record(ctx.h, bs, &r.fence) != MSW_OK) {
+                        // --alignments-out: the trace and pack follow on the same
+                        // stream; aln_finish records r.fence after the packed ops
+                        (aln ? (r.d = d, r.stream = bs, !aln_run(r, aln_stride, r.d_rows, true))
+                             : msw_fence_record(ctx.h, bs, &r.fence) != MSW_OK)) {
                         fprintf(stderr, "  GPU %d alignment error: %s\n", gi, msw_last_error());
                         f.failed = true;
                         (void)msw_synchronize(ctx.h);
+                        if (aln) aln_finish(res[cur ^ 1]);  // the other batch, while its reads are in place
                         reader_done(fi);
                         have = open_next(&fi);
                         continue;
@@ -1048,6 +1249,7 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
                     r.first = d.first_read;
                     r.fi = fi;
                     r.live = true;
+                    r.aln_pending = aln;
                     open_files[fi].first += 1;
                     cur ^= 1;
                 }

@@ -161,6 +161,20 @@ hipError_t launch_sw_multi(const SwParams& p, const MultiTable& t, bool affine, 
 // out_len[p] = len when out_len != nullptr.  ws % 16 == 0, genome allocation
 // padded by >= 20 bytes past its end.
 constexpr uint32_t kGenomePad = 64;
+// The window rule (include/msw.h, "The window of a pair"), in one place:
+// window p is genome[pos, pos + len), len = the requested length clipped at
+// the genome end; a position outside [0, glen) -- negative ones wrap past
+// glen -- is an empty window.
+__host__ __device__ inline uint32_t genome_window_len(uint64_t glen, int64_t pos, uint32_t want) {
+    const uint64_t start = (uint64_t)pos;
+    const uint64_t room = start < glen ? glen - start : 0;
+    return (uint32_t)(want < room ? want : room);
+}
+// The requested length of a device-resident read's window: `window`, or
+// 2 x read length capped at kMaxWinLen when window is 0.
+__host__ __device__ inline uint32_t reads_window_want(uint32_t window, uint32_t rlen) {
+    return window ? window : (2u * rlen < (uint32_t)kMaxWinLen ? 2u * rlen : (uint32_t)kMaxWinLen);
+}
 hipError_t launch_cut_windows(const uint8_t* genome, uint64_t glen, const int64_t* pos, const uint16_t* want,
                               uint8_t* out, uint16_t* out_len, uint32_t ws, uint64_t n, hipStream_t stream);
 // Same, for device-resident reads: want = window, or 2 x rlen[p] capped at
@@ -236,6 +250,13 @@ struct TraceParams {
     uint32_t* slab;           // per-block global direction words (slab_words each), or null
     uint64_t slab_words;
     uint32_t* next;           // work queue counter (zeroed), or null: one block per slot
+    // Windows straight from the genome (msw_trace_reads_device): genome != null
+    // replaces wins / win_len / win_stride by genome + win_pos[p] and the
+    // window rule (genome_window_len over reads_window_want).
+    const uint8_t* genome;
+    uint64_t glen;
+    const int64_t* win_pos;
+    uint32_t window;
 };
 int trace_rows_per_lane(uint32_t max_read_len);
 // direction words of a rows x cols rectangle (16 cells per word linear, 8 affine)
@@ -247,6 +268,38 @@ __host__ __device__ inline uint64_t trace_words(bool affine, uint32_t rows, uint
 size_t trace_lds_layout(TraceParams& p, bool affine);
 int trace_blocks_per_cu(bool affine, uint32_t max_read_len, size_t lds_bytes);
 hipError_t launch_sw_trace(const TraceParams& p, bool affine, uint32_t blocks, size_t lds_bytes, hipStream_t stream);
+
+// Alignment records (msw_aln.hip, msw_aln_pack_device): per read the genome
+// coordinate, the edit distance and the soft-clipped op count; an exclusive
+// prefix sum of the counts; a gather of the ops into one packed stream.
+struct AlnParams {
+    const uint8_t* genome;
+    uint64_t glen;
+    const uint8_t* reads;
+    const uint16_t* read_len;
+    uint64_t read_stride;
+    const int64_t* win_pos;
+    uint64_t n;
+    const int32_t* score;
+    const int16_t* end_i;
+    const int16_t* start_i;
+    const int16_t* start_j;
+    const int32_t* n_cigar;
+    const uint32_t* rows;     // the trace's [n][cigar_stride] op rows
+    uint32_t cigar_stride;
+    int64_t* ref_pos;
+    int32_t* nm;
+    uint32_t* cigar_off;      // [n + 1]
+    uint32_t* cigar;
+    uint64_t cigar_cap;
+    uint32_t* n_overflow;
+};
+// Items one scan block covers: a scan of `count` items has one level per
+// factor of kAlnScanTile (1 level up to the tile, 2 up to its square, ...).
+constexpr uint32_t kAlnScanTile = 1024;
+// Everything enqueued on `stream`; the scan's block sums are allocated and
+// freed stream-ordered.
+hipError_t launch_aln_pack(const AlnParams& p, hipStream_t stream);
 
 // smith_waterman_align restated: result must be zeroed before the launch.
 hipError_t launch_compat(const uint8_t* s1, const uint8_t* s2, int32_t* result, uint64_t L,

@@ -62,11 +62,10 @@ __global__ __launch_bounds__(256) void cut_windows_kernel(const uint8_t* __restr
     const uint64_t p = t / chunks;
     if (p >= n) return;
     const uint32_t c = (uint32_t)(t - p * chunks);
-    const uint64_t start = (uint64_t)pos[p];  // negative positions wrap past glen
-    const uint64_t room = start < glen ? glen - start : 0;
+    const uint64_t start = (uint64_t)pos[p];
     // requested length: want[p], or (device-resident reads) --window / 2 x read length (capped)
-    const uint64_t wl = want ? want[p] : (window ? window : min(2u * rlen[p], (uint32_t)kMaxWinLen));
-    const int len = (int)min(min(wl, room), ws);
+    const uint32_t wl = want ? want[p] : reads_window_want(window, rlen[p]);
+    const int len = (int)min((uint64_t)genome_window_len(glen, pos[p], wl), ws);
     if (out_len && c == 0) out_len[p] = (uint16_t)len;
     const int rem = len - 16 * (int)c;
     uint32_t w[4] = {0u, 0u, 0u, 0u};

@@ -1773,6 +1773,68 @@ static int validate_trace(const msw_trace_t* tr) {
     return MSW_OK;
 }
 
+// The launch both traceback entry points share: LDS layout, LDS / slab switch,
+// grid cap and work queue.  p holds the call's inputs and outputs (windows
+// from a slab or from the genome); the bounds and scoring are filled here.
+static int run_trace(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, msw::TraceParams p, uint64_t n_pairs,
+                     uint32_t max_read_len, uint32_t max_win_len, hipStream_t st) {
+    p.n_slots = (uint32_t)n_pairs;
+    p.max_rows = max_read_len;
+    p.max_cols = max_win_len;
+    p.match = sc->match;
+    p.mismatch = sc->mismatch;
+    p.gap = sc->gap_extend;
+    p.goe = sc->gap_open + sc->gap_extend;
+    const size_t shm = msw::trace_lds_layout(p, sch.affine);
+    // One block per pair while the direction words fit LDS.  A bound whose
+    // rectangle does not fit needs a global slab per block: the grid is then
+    // capped (what the CUs hold at once, and 256 MiB of slabs) and finished
+    // blocks take the next pair from a queue.  Slab and counter are allocated
+    // stream-ordered on `st`, like the long-pair launch's scratch.
+    const uint64_t need = msw::trace_words(sch.affine, max_read_len, max_win_len);
+    const bool slab = need > p.lds_words;
+    const uint64_t slab_bytes = slab ? need * sizeof(uint32_t) : 0;
+    uint64_t blocks = n_pairs;
+    if (slab) {
+        const int per_cu = msw::trace_blocks_per_cu(sch.affine, max_read_len, shm);
+        if (per_cu <= 0) return fail(MSW_E_DEVICE, "traceback kernel does not fit a CU");
+        const uint64_t resident = (uint64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (uint64_t)per_cu;
+        blocks = std::min(blocks, std::min(resident, std::max<uint64_t>(1, (256ull << 20) / slab_bytes)));
+    }
+    if (ctx->opt.trace_blocks) blocks = std::min<uint64_t>(blocks, ctx->opt.trace_blocks);  // tests: a fixed block count
+    const bool queue = blocks < n_pairs;
+    uint8_t* mem = nullptr;
+    if (slab || queue) {
+        HIP_TRY(hipMallocAsync((void**)&mem, blocks * slab_bytes + 256, st));
+        if (slab) {
+            p.slab = reinterpret_cast<uint32_t*>(mem);
+            p.slab_words = need;
+        }
+        if (queue) {
+            p.next = reinterpret_cast<uint32_t*>(mem + blocks * slab_bytes);
+            const hipError_t em = hipMemsetAsync(p.next, 0, sizeof(uint32_t), st);
+            if (em != hipSuccess) {
+                (void)hipFreeAsync(mem, st);
+                HIP_TRY(em);
+            }
+        }
+    }
+    const hipError_t e = msw::launch_sw_trace(p, sch.affine, (uint32_t)blocks, shm, st);
+    if (mem) HIP_TRY(hipFreeAsync(mem, st));
+    HIP_TRY(e);
+    return MSW_OK;
+}
+
+static void trace_outputs(msw::TraceParams& p, const msw_out_t* ends, const msw_trace_t* tr) {
+    p.end_i = ends->end_i;
+    p.end_j = ends->end_j;
+    p.start_i = tr->start_i;
+    p.start_j = tr->start_j;
+    p.n_cigar = tr->n_cigar;
+    p.cigar = tr->cigar;
+    p.cigar_stride = tr->cigar_stride;
+}
+
 int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
                            msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
@@ -1794,59 +1856,93 @@ int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     p.wins = b->wins;
     p.read_len = b->read_len;
     p.win_len = b->win_len;
-    p.end_i = ends->end_i;
-    p.end_j = ends->end_j;
-    p.start_i = tr->start_i;
-    p.start_j = tr->start_j;
-    p.n_cigar = tr->n_cigar;
-    p.cigar = tr->cigar;
-    p.cigar_stride = tr->cigar_stride;
     p.read_stride = b->read_stride;
     p.win_stride = b->win_stride;
-    p.n_slots = (uint32_t)b->n_pairs;
-    p.max_rows = max_read_len;
-    p.max_cols = max_win_len;
-    p.match = sc->match;
-    p.mismatch = sc->mismatch;
-    p.gap = sc->gap_extend;
-    p.goe = sc->gap_open + sc->gap_extend;
-    const size_t shm = msw::trace_lds_layout(p, sch.affine);
-    // One block per pair while the direction words fit LDS.  A bound whose
-    // rectangle does not fit needs a global slab per block: the grid is then
-    // capped (what the CUs hold at once, and 256 MiB of slabs) and finished
-    // blocks take the next pair from a queue.  Slab and counter are allocated
-    // stream-ordered on `st`, like the long-pair launch's scratch.
-    const uint64_t need = msw::trace_words(sch.affine, max_read_len, max_win_len);
-    const bool slab = need > p.lds_words;
-    const uint64_t slab_bytes = slab ? need * sizeof(uint32_t) : 0;
-    uint64_t blocks = b->n_pairs;
-    if (slab) {
-        const int per_cu = msw::trace_blocks_per_cu(sch.affine, max_read_len, shm);
-        if (per_cu <= 0) return fail(MSW_E_DEVICE, "traceback kernel does not fit a CU");
-        const uint64_t resident = (uint64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (uint64_t)per_cu;
-        blocks = std::min(blocks, std::min(resident, std::max<uint64_t>(1, (256ull << 20) / slab_bytes)));
+    trace_outputs(p, ends, tr);
+    return run_trace(ctx, sch, sc, p, b->n_pairs, max_read_len, max_win_len, st);
+}
+
+int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                           uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
+                           void* stream) {
+    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    Scheme sch;
+    int rc;
+    if ((rc = make_scheme(sc, ctx->opt, &sch))) return rc;
+    if ((rc = validate_trace(tr))) return rc;
+    if (n == 0) return MSW_OK;
+    if (!reads || !read_len || !win_pos) return fail(MSW_E_INVALID, "NULL array");
+    if (!ends || !ends->end_i || !ends->end_j) return fail(MSW_E_INVALID, "traceback needs end_i / end_j");
+    // the window bound of msw_align_reads_device
+    const uint32_t max_win = window ? window : std::min<uint32_t>(2u * max_read_len, (uint32_t)msw::kMaxWinLen);
+    if ((rc = check_trace_bounds(max_read_len, max_win))) return rc;
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n > 2^31-1 in one call");
+    if (max_read_len > read_stride) return fail(MSW_E_INVALID, "max_read_len exceeds read_stride");
+    if ((rc = set_device(ctx))) return rc;
+    hipStream_t st = call_stream(ctx, stream);
+    msw::TraceParams p;
+    memset(&p, 0, sizeof(p));
+    p.reads = reads;
+    p.read_len = read_len;
+    p.read_stride = read_stride;
+    p.genome = g->d_seq;
+    p.glen = g->len;
+    p.win_pos = win_pos;
+    p.window = window;
+    trace_outputs(p, ends, tr);
+    return run_trace(ctx, sch, sc, p, n, max_read_len, max_win, st);
+}
+
+static int validate_aln(const msw_aln_t* a) {
+    if (!a) return fail(MSW_E_INVALID, "aln is NULL");
+    if (!a->ref_pos || !a->nm || !a->cigar_off || !a->n_overflow) return fail(MSW_E_INVALID, "NULL array in aln");
+    if (a->cigar_cap && !a->cigar) return fail(MSW_E_INVALID, "cigar is NULL with cigar_cap > 0");
+    return MSW_OK;
+}
+
+int msw_aln_pack_device(msw_ctx* ctx, const msw_genome* g, const uint8_t* reads, const uint16_t* read_len,
+                        uint32_t read_stride, const int64_t* win_pos, uint64_t n, const msw_out_t* ends,
+                        const msw_trace_t* tr, msw_aln_t* aln, void* stream) {
+    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    int rc;
+    if ((rc = validate_aln(aln))) return rc;
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "aln pack: n > 2^31-1 in one call");
+    if (n) {
+        if ((rc = validate_trace(tr))) return rc;
+        if (!reads || !read_len || !win_pos) return fail(MSW_E_INVALID, "NULL array");
+        if (!ends || !ends->score || !ends->end_i || !ends->end_j)
+            return fail(MSW_E_INVALID, "aln pack needs score / end_i / end_j");
     }
-    if (ctx->opt.trace_blocks) blocks = std::min<uint64_t>(blocks, ctx->opt.trace_blocks);  // tests: a fixed block count
-    const bool queue = blocks < b->n_pairs;
-    uint8_t* mem = nullptr;
-    if (slab || queue) {
-        HIP_TRY(hipMallocAsync((void**)&mem, blocks * slab_bytes + 256, st));
-        if (slab) {
-            p.slab = reinterpret_cast<uint32_t*>(mem);
-            p.slab_words = need;
-        }
-        if (queue) {
-            p.next = reinterpret_cast<uint32_t*>(mem + blocks * slab_bytes);
-            const hipError_t em = hipMemsetAsync(p.next, 0, sizeof(uint32_t), st);
-            if (em != hipSuccess) {
-                (void)hipFreeAsync(mem, st);
-                HIP_TRY(em);
-            }
-        }
+    if ((rc = set_device(ctx))) return rc;
+    hipStream_t st = call_stream(ctx, stream);
+    msw::AlnParams p;
+    memset(&p, 0, sizeof(p));
+    p.genome = g->d_seq;
+    p.glen = g->len;
+    p.reads = reads;
+    p.read_len = read_len;
+    p.read_stride = read_stride;
+    p.win_pos = win_pos;
+    p.n = n;
+    if (n) {
+        p.score = ends->score;
+        p.end_i = ends->end_i;
+        p.start_i = tr->start_i;
+        p.start_j = tr->start_j;
+        p.n_cigar = tr->n_cigar;
+        p.rows = tr->cigar;
+        p.cigar_stride = tr->cigar_stride;
     }
-    const hipError_t e = msw::launch_sw_trace(p, sch.affine, (uint32_t)blocks, shm, st);
-    if (mem) HIP_TRY(hipFreeAsync(mem, st));
-    HIP_TRY(e);
+    p.ref_pos = aln->ref_pos;
+    p.nm = aln->nm;
+    p.cigar_off = aln->cigar_off;
+    p.cigar = aln->cigar;
+    p.cigar_cap = aln->cigar_cap;
+    p.n_overflow = aln->n_overflow;
+    HIP_TRY(msw::launch_aln_pack(p, st));
     return MSW_OK;
 }
 
@@ -2202,6 +2298,121 @@ int msw_align_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
     if ((rc = msw_align_batch_device(ctx, sc, &b, out, max_read_len, max_win, stream))) return rc;
     HIP_TRY(hipEventRecord(t.k1, st));
     ctx->dev_timings.push_back(t);
+    return MSW_OK;
+}
+
+int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
+                          msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
+    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
+    msw_scoring_t scc = *sc;
+    scc.want_coords = 1;
+    Scheme sch;
+    int rc;
+    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
+    if ((rc = validate_aln(aln))) return rc;
+    const uint64_t n = b->n_pairs;
+    *aln->n_overflow = 0;
+    aln->cigar_off[0] = 0;
+    if (n == 0) return MSW_OK;
+    if (!b->reads || !b->read_len || !b->win_pos || !b->win_len) return fail(MSW_E_INVALID, "NULL array in batch");
+    if (!out || !out->score || !out->end_i || !out->end_j)
+        return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
+    uint32_t max_m = 0, max_n = 0;
+    max_u16(b->read_len, n, max_m);
+    max_u16(b->win_len, n, max_n);
+    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    if (max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    // Simple and synchronous, like msw_align_batch_trace: per chunk upload,
+    // cut, score with coordinates, trace, pack, download.  The trace stride is
+    // exact (no alignment has more ops than rows + columns), so no read
+    // overflows; the packed ops of a chunk are pulled once its total is known.
+    const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
+    const size_t rs = b->read_stride, ws = std::max<size_t>(16, (max_n + 15u) & ~15u), cs = (size_t)max_m + max_n;
+    auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // [reads | wins | rows u32 | pos i64 | ref i64 | score nc nm i32 | off u32 [c+1] + ovf | 7 x 2 B arrays]
+    const size_t o_wins = up256(chunk * rs), o_rows = up256(o_wins + chunk * ws), o_pos = up256(o_rows + chunk * cs * 4);
+    const size_t o_ref = o_pos + chunk * 8, o_score = o_ref + chunk * 8, o_nc = o_score + chunk * 4,
+                 o_nm = o_nc + chunk * 4, o_off = o_nm + chunk * 4, o_h = o_off + (chunk + 2) * 4;
+    const size_t total_bytes = o_h + chunk * 14 + 256;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total_bytes);
+    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
+    uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
+    uint64_t ops_cap = chunk * 8;
+    e = hipMalloc((void**)&d_ops, ops_cap * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
+    }
+    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
+    uint16_t *d_want = d_rl + chunk, *d_wl = d_want + chunk;
+    int16_t *d_ei = reinterpret_cast<int16_t*>(d_wl + chunk), *d_ej = d_ei + chunk, *d_si = d_ej + chunk,
+            *d_sj = d_si + chunk;
+    int64_t *d_pos = reinterpret_cast<int64_t*>(d + o_pos), *d_ref = reinterpret_cast<int64_t*>(d + o_ref);
+    uint32_t* d_off = reinterpret_cast<uint32_t*>(d + o_off);
+    hipStream_t st = ctx->compute;
+    std::vector<uint32_t> off(chunk + 1);
+    uint64_t base = 0;  // ops of the chunks before this one
+    rc = MSW_OK;
+    for (uint64_t lo = 0; lo < n && rc == MSW_OK && e == hipSuccess; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        uint32_t cm = 0, cn = 0;
+        max_u16(b->read_len + lo, c, cm);
+        max_u16(b->win_len + lo, c, cn);
+        auto up = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+        };
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+        };
+        up(d, b->reads + lo * rs, c * rs);
+        up(d_rl, b->read_len + lo, c * 2);
+        up(d_want, b->win_len + lo, c * 2);
+        up(d_pos, b->win_pos + lo, c * 8);
+        if (e != hipSuccess) break;
+        if ((rc = msw_genome_cut_device(ctx, g, d_pos, d_want, c, d + o_wins, (uint32_t)ws, d_wl, st))) break;
+        msw_batch_t db = {d, d + o_wins, d_rl, d_wl, (uint32_t)rs, (uint32_t)ws, c};
+        msw_out_t dout = {reinterpret_cast<int32_t*>(d + o_score), d_ei, d_ej};
+        msw_trace_t dtr = {d_si, d_sj, reinterpret_cast<int32_t*>(d + o_nc), reinterpret_cast<uint32_t*>(d + o_rows),
+                           (uint32_t)cs};
+        if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) break;
+        if ((rc = msw_trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st))) break;
+        uint64_t total = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            msw_aln_t da = {d_ref, reinterpret_cast<int32_t*>(d + o_nm), d_off, d_ops, ops_cap, d_off + c + 1};
+            if ((rc = msw_aln_pack_device(ctx, g, d, d_rl, (uint32_t)rs, d_pos, c, &dout, &dtr, &da, st))) break;
+            down(off.data(), d_off, (c + 1) * 4);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) break;
+            total = off[c];
+            if (total <= ops_cap) break;
+            (void)hipFree(d_ops);
+            d_ops = nullptr;
+            ops_cap = total;
+            e = hipMalloc((void**)&d_ops, ops_cap * 4);
+        }
+        if (rc || e != hipSuccess) break;
+        down(out->score + lo, dout.score, c * 4);
+        down(out->end_i + lo, d_ei, c * 2);
+        down(out->end_j + lo, d_ej, c * 2);
+        down(aln->ref_pos + lo, d_ref, c * 8);
+        down(aln->nm + lo, d + o_nm, c * 4);
+        const uint64_t room = aln->cigar_cap > base ? aln->cigar_cap - base : 0;
+        down(aln->cigar + base, d_ops, std::min(total, room) * 4);
+        // one prefix sum over the whole batch: this chunk's offsets start at `base`
+        for (uint64_t k = 0; k <= c; ++k) aln->cigar_off[lo + k] = (uint32_t)(base + off[k]);
+        base += total;
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (d_ops) (void)hipFree(d_ops);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "alignment records: %s", hipGetErrorString(e));
     return MSW_OK;
 }
 

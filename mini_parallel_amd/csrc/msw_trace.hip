@@ -210,7 +210,19 @@ __global__ __launch_bounds__(64) void sw_trace_kernel(TraceParams p) {
         return gridDim.x + (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
     };
     for (uint32_t pair = blockIdx.x; pair < p.n_slots; pair = next_slot(pair)) {
-        const int m = p.read_len[pair], n = p.win_len[pair];
+        const int m = p.read_len[pair];
+        // the pair's window: its row of the caller's slab, or (wave-uniform
+        // select) the genome at win_pos[pair] under the window rule
+        const uint8_t* wn;
+        int n;
+        if (p.genome) {
+            const int64_t pos = p.win_pos[pair];
+            n = (int)genome_window_len(p.glen, pos, reads_window_want(p.window, (uint32_t)m));
+            wn = p.genome + pos;  // read only below n bytes: never when the position is outside the genome
+        } else {
+            n = p.win_len[pair];
+            wn = p.wins + (size_t)pair * p.win_stride;
+        }
         // wave-uniform; a best cell outside the pair or the call's bounds is not traced
         int rows = (int)p.end_i[pair] + 1, cols = (int)p.end_j[pair] + 1;
         rows = __builtin_amdgcn_readfirstlane(rows);
@@ -224,7 +236,6 @@ __global__ __launch_bounds__(64) void sw_trace_kernel(TraceParams p) {
         __syncthreads();  // the previous pair's LDS reads are done
         if (traced) {
             const uint8_t* rd = p.reads + (size_t)pair * p.read_stride;
-            const uint8_t* wn = p.wins + (size_t)pair * p.win_stride;
             for (int k = lane; k < cols; k += 64) lds_win[64 + k] = wn[k];
             __syncthreads();
             r = in_lds ? trace_pair<R, AFFINE, false>(p, rd, lds_win, lds_ops, lds_dirs, rows, cols)
