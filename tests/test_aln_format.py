@@ -1,12 +1,15 @@
 """The .aln file format (mini_parallel_amd/alnfile.py): round trip with blocks
 out of order, rejection of damaged files, and cigar_string with soft clips."""
+import os
 import struct
+import subprocess
 
 import numpy as np
 import pytest
 
 from mini_parallel_amd import AlnBlock, cigar_string, read_alignments, write_alignments
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = 4
 
 
@@ -98,6 +101,33 @@ def test_rejects_gap_overlap_magic_truncation(tmp_path):
     path.write_bytes(good[:20] + struct.pack("<I", n_ops - 1) + good[24:])
     with pytest.raises(ValueError):
         read_alignments(path)
+
+
+def test_cli_encoder_writes_the_format(tmp_path):
+    """The CLI's C++ encoder (csrc/cli_aln_block.h, driven by tests/c/aln_block_dump.cpp
+    with the arrays repeated here) against write_alignments / read_alignments:
+    a block out of order, a read without ops, an empty block, values at the
+    fields' limits."""
+    M, I, D = 0, 1, 2
+    a = AlnBlock(0, [1000, 2001, 3002], [300, 251, 12], [0, 3, 1], [149, 148, 9], [149, 299, 30],
+                 [[150 << 4 | M], [100 << 4 | M, 2 << 4 | I, 47 << 4 | M], [6 << 4 | M, 144 << 4 | S]])
+    b = AlnBlock(3, [70000, -1], [77, 0], [2, 0], [149, -1], [290, -1], [[5 << 4 | S, 140 << 4 | M, 5 << 4 | S], []])
+    c = AlnBlock(5, [], [], [], [], [], [])
+    d = AlnBlock(5, [(1 << 40) + 12345, (1 << 40) - 1], [2**31 - 1, -2**31], [-1, 2**31 - 1], [-1, 32767],
+                 [-1, -32768], [[4095 << 4 | D, 1 << 4 | M], [0xFFFFFFFF]])
+    exe = str(tmp_path / "aln_block_dump")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I",
+                    os.path.join(ROOT, "mini_parallel_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "c", "aln_block_dump.cpp"), "-o", exe], check=True)
+    subprocess.run([exe, str(tmp_path / "cli.aln")], check=True)
+    write_alignments(tmp_path / "py.aln", [b, a, c, d])
+    assert (tmp_path / "cli.aln").read_bytes() == (tmp_path / "py.aln").read_bytes()
+    got = read_alignments(tmp_path / "cli.aln")
+    ref, score, nm, ei, ej, cigars = joined([a, b, d])
+    for x, y in ((got.ref_pos, ref), (got.score, score), (got.nm, nm), (got.end_i, ei), (got.end_j, ej)):
+        assert np.array_equal(x, y)
+    assert len(got.cigars) == 7 and all(np.array_equal(x, np.asarray(y, np.uint32)) for x, y in zip(got.cigars, cigars))
+    assert int(got.ref_pos[5]) == (1 << 40) + 12345 and int(got.cigars[5][0]) >> 4 == 4095
 
 
 def test_cigar_string_soft_clips():

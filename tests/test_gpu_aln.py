@@ -569,6 +569,43 @@ def test_cli_alignments_out(tmp_path, scheme):
     assert multi_op > 0      # the stride-1 run did trace reads again
 
 
+def test_cli_alignments_out_file_switch(tmp_path):
+    """Four BGZF lane files of 250 reads over the two workers of one GPU, in
+    batches of 100 (two full, one of 50): a worker goes from one file to the
+    next while a result set still holds the first file's last batch, and at
+    MSW_CLI_CIGAR_STRIDE=1 that batch is traced again before it settles.
+    Every .aln equals the oracle read for read, every .scores file equals its
+    .aln's scores and end cells, and the checkpoint completes all four files."""
+    import json
+    from mini_parallel_amd import read_alignments
+    from mini_parallel_amd.synthetic import write_wgs_dataset
+    ds = write_wgs_dataset(str(tmp_path / "wgs"), lanes=2, reads_per_lane=2, reads_per_file=250, bgzf=True)
+    assert len(ds["files"]) == 4
+    for d in ("aln", "scores"):
+        (tmp_path / d).mkdir()
+    r = run_cli(wgs_args(tmp_path, ds, "lin", "sw4") + ["--alignments-out", tmp_path / "aln", "--scores-out",
+                                                        tmp_path / "scores"],
+                wgs_env(tmp_path, "sw4", WGS_LANES="2", MSW_GFASTQ_BATCH="100", MSW_CLI_CIGAR_STRIDE="1"), tmp_path)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rec_t = np.dtype([("score", "<i4"), ("end_i", "<i2"), ("end_j", "<i2")])
+    for f, b in zip(ds["files"], ds["batches"]):
+        name = os.path.basename(f)
+        got = read_alignments(tmp_path / "aln" / (name + ".aln"))
+        assert len(got.score) == b.n_pairs == 250
+        for p in range(b.n_pairs):
+            want = ao.record(b.reads[p, :b.read_len[p]], b.wins[p, :b.win_len[p]], int(b.pos[p]), *LIN)
+            have = (int(got.score[p]), int(got.end_i[p]), int(got.end_j[p]), int(got.ref_pos[p]), int(got.nm[p]),
+                    [int(o) for o in got.cigars[p]])
+            assert have == tuple(want), (name, p, ao.cigar_text(have[5]), ao.cigar_text(want.ops))
+        scores = np.fromfile(tmp_path / "scores" / (name + ".scores"), dtype=rec_t)
+        assert np.array_equal(scores["score"], got.score) and np.array_equal(scores["end_i"], got.end_i)
+        assert np.array_equal(scores["end_j"], got.end_j)
+    ck = json.load(open(tmp_path / "sw4" / "checkpoint_sw4.json"))
+    assert ck["completed_files"] == ck["total_files"] == 4
+    assert sorted(f["file_path"] for f in ck["files"] if f["completed"]) == sorted(ds["files"])
+    assert all(f["total_reads"] == 250 for f in ck["files"])
+
+
 def test_cli_alignments_out_refused(tmp_path):
     """The host reader, reads over 384 and windows over 4096 are refused with
     status 1 and one line, and no .aln appears."""
