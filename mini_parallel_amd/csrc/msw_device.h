@@ -166,7 +166,7 @@ struct PairMeta {
 __device__ __forceinline__ void pin_args(const SwParams& p) {
     asm volatile("" ::"s"(p.reads), "s"(p.wins), "s"(p.read_len), "s"(p.win_len), "s"(p.order), "s"(p.slot_lens),
                  "s"(p.read_stride), "s"(p.win_stride), "s"(p.n_slots), "s"(p.lds_stride), "s"(p.code_shift),
-                 "s"(p.win_vec), "s"(p.slot_base), "s"(p.group_lanes), "s"(p.groups), "s"(p.f16_ok), "s"(p.f16_hi),
+                 "s"(p.win_vec), "s"(p.read_vec), "s"(p.slot_base), "s"(p.group_lanes), "s"(p.groups), "s"(p.f16_ok), "s"(p.f16_hi),
                  "s"(p.f16_ngap2), "s"(p.out_by_slot), "s"(p.out_slot_base), "s"(p.score), "s"(p.match2),
                  "s"(p.delta2), "s"(p.gap2), "s"(p.open_ext2), "s"(p.bias2), "s"(p.f16_noe2), "s"(p.end_i),
                  "s"(p.end_j));
@@ -383,40 +383,121 @@ __device__ __forceinline__ void stage_window(const SwParams& p, const PairMeta& 
     }
 }
 
+// A lane's KR consecutive read bytes, as loaded and as used:
+//  loads: KR bytes from any byte offset touch at most read_loads(KR) dwords;
+//  rows:  realigned to the lane's first row, row r is byte r & 3 of dword
+//         r >> 2 (read_words(KR) dwords per half).
+constexpr int read_words(int kr) { return (kr + 3) / 4; }
+constexpr int read_loads(int kr) { return (kr + 6) / 4; }
+
+// Whether a launch reads its rows as dwords (wave-uniform).
+__device__ __forceinline__ bool read_vec(const SwParams& p) { return !MSW_PROBE_NO_READ && p.read_vec; }
+
+// Instances that have the dword arm at all.  The affine score-only loops are
+// hipcc's own schedule, and the instances that read genome windows or run in
+// the length-bucketed grid sit at 124-126 VGPRs with them, four waves per
+// SIMD: with the row dwords in the function (either arm) hipcc gives their
+// integer loops 134-135 and the fourth wave is gone (the whole-genome driver
+// lost 2-3 %).  They keep one byte load per row, byte
+// registers straight into the tables and codes, as before.
+constexpr bool read_dwords(bool affine, bool coords, bool gen, bool plan) {
+    return !(affine && !coords && (gen || plan));
+}
+
+// First row of this lane in each half.
+template <int KR, bool SPLIT>
+__device__ __forceinline__ int first_row_a(int lg) { return SPLIT ? lg * 2 * KR : lg * KR; }
+template <int KR, bool SPLIT>
+__device__ __forceinline__ int first_row_b(int lg) { return SPLIT ? lg * 2 * KR + KR : lg * KR; }
+
 // Read bytes of this lane's packed rows: unconditional loads with clamped
 // addresses (all in flight at once, issued before the pair lengths arrive).
-template <int KR, bool SPLIT>
+// VEC (rows 4-byte aligned and a whole number of dwords long, p.read_vec):
+// the aligned dwords round the lane's bytes, each dword index clamped to the
+// row's last whole dword, never past the row.  Otherwise one byte load per
+// row, clamped to the row's last byte (pack_read_bytes makes dwords of them).
+template <int KR, bool SPLIT, bool VEC>
 __device__ __forceinline__ void load_read_bytes(const SwParams& p, uint32_t pa, uint32_t pb, int lg,
-                                                uint32_t (&ba)[KR], uint32_t (&bb)[KR]) {
+                                                uint32_t (&xa)[VEC ? read_loads(KR) : KR],
+                                                uint32_t (&xb)[VEC ? read_loads(KR) : KR]) {
     const uint8_t* ra = p.reads + (uint64_t)pa * p.read_stride;
     const uint8_t* rb = p.reads + (uint64_t)pb * p.read_stride;
-    const int last = (int)p.read_stride - 1;
+    const int ia0 = first_row_a<KR, SPLIT>(lg), ib0 = first_row_b<KR, SPLIT>(lg);
+    if constexpr (VEC) {
+        const uint32_t* wa = reinterpret_cast<const uint32_t*>(ra);
+        const uint32_t* wb = reinterpret_cast<const uint32_t*>(rb);
+        const int last = (int)(p.read_stride >> 2) - 1;  // the row's last whole dword
 #pragma unroll
-    for (int r = 0; r < KR; ++r) {
-        const int ia = SPLIT ? lg * 2 * KR + r : lg * KR + r;
-        const int ib = SPLIT ? ia + KR : ia;
+        for (int j = 0; j < read_loads(KR); ++j) {
+            xa[j] = wa[min((ia0 >> 2) + j, last)];
+            xb[j] = wb[min((ib0 >> 2) + j, last)];
+        }
+    } else {
+        const int last = (int)p.read_stride - 1;
+#pragma unroll
+        for (int r = 0; r < KR; ++r) {
 #if MSW_PROBE_NO_READ
-        ba[r] = (uint32_t)(ia + pa) & 3u;
-        bb[r] = (uint32_t)(ib + pb) & 3u;
-        (void)ra; (void)rb; (void)last;
+            xa[r] = (uint32_t)(ia0 + r + pa) & 3u;
+            xb[r] = (uint32_t)(ib0 + r + pb) & 3u;
+            (void)ra; (void)rb; (void)last;
 #else
-        ba[r] = ra[min(ia, last)];
-        bb[r] = rb[min(ib, last)];
+            xa[r] = ra[min(ia0 + r, last)];
+            xb[r] = rb[min(ib0 + r, last)];
 #endif
+        }
     }
+}
+
+// Byte loads packed into dwords, as if loaded from a lane start at a dword
+// boundary.  Called behind the window loads of the first round, so those do
+// not wait for the read bytes.
+template <int KR>
+__device__ __forceinline__ void pack_read_bytes(const uint32_t (&b)[KR], uint32_t (&w)[read_loads(KR)]) {
+#pragma unroll
+    for (int j = 0; j < read_loads(KR); ++j) {
+        w[j] = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (4 * j + e < KR) w[j] |= (b[4 * j + e] & 0xFFu) << (8 * e);
+    }
+}
+
+// The loaded dwords as row dwords: realigned by the lane's start offset, one
+// v_alignbyte_b32 each (offset 0 for packed byte loads).  A byte that would
+// come from a dword past read_loads belongs to no row of this lane.  Bytes of
+// rows past the read (clamped loads) hold anything.
+template <int KR, bool SPLIT>
+__device__ __forceinline__ void read_rows(const SwParams& p, int lg, const uint32_t (&xa)[read_loads(KR)],
+                                          const uint32_t (&xb)[read_loads(KR)], uint32_t (&wa)[read_words(KR)],
+                                          uint32_t (&wb)[read_words(KR)]) {
+    constexpr int NW = read_words(KR), NL = read_loads(KR);
+    const uint32_t oa = read_vec(p) ? (uint32_t)first_row_a<KR, SPLIT>(lg) & 3u : 0u;
+    const uint32_t ob = read_vec(p) ? (uint32_t)first_row_b<KR, SPLIT>(lg) & 3u : 0u;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        wa[j] = __builtin_amdgcn_alignbyte(xa[j + 1 < NL ? j + 1 : j], xa[j], oa);
+        wb[j] = __builtin_amdgcn_alignbyte(xb[j + 1 < NL ? j + 1 : j], xb[j], ob);
+    }
+}
+
+// Row r's byte of the row dwords.
+template <int NW>
+__device__ __forceinline__ uint32_t row_byte(const uint32_t (&w)[NW], int r) {
+    return (w[r >> 2] >> (8 * (r & 3))) & 0xFFu;
 }
 
 // Read codes (byte << code_shift, or the sentinel past the read) of this
 // lane's packed rows, pair a in the low and pair b in the high half.
-template <int KR, bool SPLIT>
-__device__ __forceinline__ void read_codes(const SwParams& p, const PairMeta& q, int lg, const uint32_t (&ba)[KR],
-                                           const uint32_t (&bb)[KR], uint32_t (&rc)[KR]) {
+// byte_a(r) / byte_b(r): row r's read byte of either half.
+template <int KR, bool SPLIT, class BA, class BB>
+__device__ __forceinline__ void read_codes(const SwParams& p, const PairMeta& q, int lg, BA byte_a, BB byte_b,
+                                           uint32_t (&rc)[KR]) {
 #pragma unroll
     for (int r = 0; r < KR; ++r) {
-        const int ia = SPLIT ? lg * 2 * KR + r : lg * KR + r;
-        const int ib = SPLIT ? ia + KR : ia;
-        const uint32_t ca = ia < q.ma ? (ba[r] << p.code_shift) : kReadSentinel;
-        const uint32_t cb = ib < q.mb ? (bb[r] << p.code_shift) : kReadSentinel;
+        const int ia = first_row_a<KR, SPLIT>(lg) + r;
+        const int ib = first_row_b<KR, SPLIT>(lg) + r;
+        const uint32_t ca = ia < q.ma ? (byte_a(r) << p.code_shift) : kReadSentinel;
+        const uint32_t cb = ib < q.mb ? (byte_b(r) << p.code_shift) : kReadSentinel;
         rc[r] = ca | (cb << 16);
     }
 }
@@ -759,19 +840,39 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
     constexpr bool kClamp = PLAN || GEN;
     const bool try_fast = p.f16_ok && p.win_vec;
     PairMeta q;
-    uint32_t rb_a[KR], rb_b[KR];
+    constexpr bool kDwords = read_dwords(AFFINE, COORDS, GEN, PLAN);
+    uint32_t rd_a[kDwords ? read_loads(KR) : 1], rd_b[kDwords ? read_loads(KR) : 1];  // the read loads, as dwords
+    uint32_t rb_a[kDwords ? 1 : KR], rb_b[kDwords ? 1 : KR];                          // !kDwords: as bytes
     WinRound w0;
-    auto early = [&](auto ident) __attribute__((always_inline)) {
+    // ident: see above; vec: the rows are read as dwords (p.read_vec).  A
+    // variant of its own per combination, so neither arm's load registers
+    // cross a join.
+    auto early = [&](auto ident, auto vec) __attribute__((always_inline)) {
+        constexpr bool kVec = decltype(vec)::value;
         q = load_meta<SPLIT, GEN, decltype(ident)::value>(p, g, block, active);
-        load_read_bytes<KR, SPLIT>(p, q.pa, q.pb, lg, rb_a, rb_b);
+        uint32_t by_a[kVec || !kDwords ? 1 : KR], by_b[kVec || !kDwords ? 1 : KR];
+        if constexpr (!kDwords) load_read_bytes<KR, SPLIT, false>(p, q.pa, q.pb, lg, rb_a, rb_b);
+        else if constexpr (kVec) load_read_bytes<KR, SPLIT, true>(p, q.pa, q.pb, lg, rd_a, rd_b);
+        else load_read_bytes<KR, SPLIT, false>(p, q.pa, q.pb, lg, by_a, by_b);
         if constexpr (kClamp) mask_meta<GEN>(q);
         if (try_fast) load_round<SPLIT, GEN, kClamp>(p, q, 0, lg, G, w0);
-        // keeps the two variants' loads apart: merged behind the join, their
+        if constexpr (kDwords && !kVec) {
+            pack_read_bytes<KR>(by_a, rd_a);
+            pack_read_bytes<KR>(by_b, rd_b);
+        }
+        // keeps the variants' loads apart: merged behind the join, their
         // addresses would wait for the ordered variant's index loads again
         asm volatile("");
     };
-    if (!PLAN && __builtin_expect(!p.order && !p.slot_lens, 1)) early(std::true_type{});
-    else early(std::false_type{});
+    const bool ident = !PLAN && __builtin_expect(!p.order && !p.slot_lens, 1);
+    const bool dwords = kDwords && read_vec(p);
+    if (dwords) {
+        if (ident) early(std::true_type{}, std::true_type{});
+        else early(std::false_type{}, std::true_type{});
+    } else {
+        if (ident) early(std::true_type{}, std::false_type{});
+        else early(std::false_type{}, std::false_type{});
+    }
     if constexpr (!kClamp) mask_meta<GEN>(q);
     const int skew = SPLIT ? 2 * (G - 1) + 1 : G - 1;
     // wavefront steps, rounded up to a multiple of the steps per iteration
@@ -816,10 +917,22 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
     // v_cmp per iteration instead of their scalar forms).
     int t_first = 0;
     asm("" : "+s"(t_first));
+    // this lane's read bytes as row dwords: formed behind the staging, where
+    // the read loads have long landed
+    uint32_t rw_a[kDwords ? read_words(KR) : 1], rw_b[kDwords ? read_words(KR) : 1];
+    auto byte_a = [&](int r) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (kDwords) return row_byte(rw_a, r);
+        else return rb_a[r];
+    };
+    auto byte_b = [&](int r) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (kDwords) return row_byte(rw_b, r);
+        else return rb_b[r];
+    };
     // The whole DP for one arithmetic domain: F16 = ACGT table lookups on f16
     // values, else xor/min on the byte codes with u16 integer values.
     auto run = [&](auto f16_tag) __attribute__((always_inline)) {
         constexpr bool F16 = decltype(f16_tag)::value;
+        if constexpr (kDwords) read_rows<KR, SPLIT>(p, lg, rd_a, rd_b, rw_a, rw_b);
         // integer path constants
         const uint32_t match2 = p.match2, delta2 = p.delta2, ext2 = p.gap2, oe2 = p.open_ext2;
         const uint32_t bias2 = (AFFINE && !F16) ? p.bias2 : 0u;  // K in both halves (integer affine)
@@ -836,11 +949,11 @@ __device__ __forceinline__ bool sw_body(const SwParams& p, uint32_t block, uint3
             for (int r = 0; r < KR; ++r) {
                 const int ia = SPLIT ? lg * 2 * KR + r : lg * KR + r;
                 const int ib = SPLIT ? ia + KR : ia;
-                tab_lo[r] = row_table(rb_a[r], ia < q.ma, mis4, d);
-                tab_hi[r] = row_table(rb_b[r], ib < q.mb, mis4, d);
+                tab_lo[r] = row_table(byte_a(r), ia < q.ma, mis4, d);
+                tab_hi[r] = row_table(byte_b(r), ib < q.mb, mis4, d);
             }
         } else {
-            read_codes<KR, SPLIT>(p, q, lg, rb_a, rb_b, rc);
+            read_codes<KR, SPLIT>(p, q, lg, byte_a, byte_b, rc);
         }
         // F16: the substitution score s; integer: the penalty a = match - s.
         auto sub = [&](int r, uint32_t w) __attribute__((always_inline)) -> uint32_t {
@@ -1253,7 +1366,7 @@ __device__ __forceinline__ WaveClock trace_begin(const SwParams& p) {
     return w;
 }
 __device__ __forceinline__ void trace_end(const SwParams& p, const WaveClock& w, bool fast, bool split,
-                                          int kr, uint64_t t_loop) {
+                                          int kr, uint64_t t_loop, bool dwords) {
     if (!p.trace) return;
     const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
     const uint64_t c1 = __builtin_amdgcn_s_memtime();
@@ -1263,8 +1376,9 @@ __device__ __forceinline__ void trace_end(const SwParams& p, const WaveClock& w,
         uint64_t* o = p.trace + 4ull * blockIdx.x;
         o[0] = w.t0;
         o[1] = t1;
+        // bit 42: the read rows were loaded as dwords (p.read_vec, in an instance with that arm)
         o[2] = (uint64_t)hw_id | ((uint64_t)xcc << 32) | ((uint64_t)fast << 40) | ((uint64_t)split << 41) |
-               ((uint64_t)kr << 48);
+               ((uint64_t)dwords << 42) | ((uint64_t)kr << 48);
         // shader cycles (40 bits) | constant-clock ticks before the DP loop << 40
         o[3] = ((c1 - w.c0) & 0xFFFFFFFFFFull) | ((t_loop - w.t0) << 40);
     }
@@ -1298,7 +1412,7 @@ __global__ __launch_bounds__(64) void sw_kernel(SwParams p) {
     // bytes 5.36 -> 4.99 MB per launch but slowed it 46.2 -> 50.2 us
     // (profiles/r03/traffic/xcd_remap_ab.jsonl); kept for the bucketed grid
     const bool fast = sw_body<KR, AFFINE, COORDS, SPLIT, GEN>(p, blockIdx.x, lds, t_loop);
-    trace_end(p, wc, fast, SPLIT, KR, t_loop);
+    trace_end(p, wc, fast, SPLIT, KR, t_loop, read_dwords(AFFINE, COORDS, GEN, false) && read_vec(p));
 }
 
 // Mixed grid for small batches: blocks [0, p.pairs_blocks) run the pairs
@@ -1314,7 +1428,7 @@ __global__ __launch_bounds__(64) void sw_mixed_kernel(SwParams p) {
     uint64_t t_loop = 0;
     if (blockIdx.x < p.pairs_blocks) {
         const bool fast = sw_body<KRP, AFFINE, COORDS, false>(p, blockIdx.x, lds, t_loop);
-        trace_end(p, wc, fast, false, KRP, t_loop);
+        trace_end(p, wc, fast, false, KRP, t_loop, read_dwords(AFFINE, COORDS, false, false) && read_vec(p));
     } else {
         SwParams q = p;
         const uint32_t done = p.pairs_blocks * pairs_per_wave(false, p.groups);
@@ -1324,7 +1438,7 @@ __global__ __launch_bounds__(64) void sw_mixed_kernel(SwParams p) {
         q.out_slot_base = p.out_slot_base + done;
         const bool fast = sw_body<(KRP + 1) / 2, AFFINE, COORDS, true>(q, blockIdx.x - p.pairs_blocks, lds,
                                                                       t_loop);
-        trace_end(p, wc, fast, true, (KRP + 1) / 2, t_loop);
+        trace_end(p, wc, fast, true, (KRP + 1) / 2, t_loop, read_dwords(AFFINE, COORDS, false, false) && read_vec(p));
     }
 }
 
@@ -1337,7 +1451,7 @@ __device__ __forceinline__ void multi_body(const SwParams& q, uint32_t blk, uint
     const WaveClock wc = trace_begin(q);
     uint64_t t_loop = 0;
     const bool fast = sw_body<KR, AFFINE, COORDS, false, false, true>(q, blk, lds, t_loop);
-    trace_end(q, wc, fast, false, KR, t_loop);
+    trace_end(q, wc, fast, false, KR, t_loop, read_dwords(AFFINE, COORDS, false, true) && read_vec(q));
 }
 
 // WIDE: the table's buckets have 17..24 rows per lane (reads of 257..384

@@ -51,6 +51,7 @@ struct SwParams {
     uint32_t lds_stride;      // u32 words per lane-group window stream
     uint32_t code_shift;
     uint32_t win_vec;         // 1: win_stride % 16 == 0 and wins 16-byte aligned
+    uint32_t read_vec;        // 1: read_stride % 4 == 0 and reads 4-byte aligned
     uint32_t pairs_blocks;    // mixed grid: leading blocks that use the pairs layout
     uint32_t slot_base;       // first slot index of this (sub)grid when order == nullptr
     uint32_t match2;          // match, duplicated into both u16 halves
@@ -116,6 +117,12 @@ __host__ __device__ inline uint32_t pairs_per_wave(bool split, uint32_t groups) 
 // 16-byte vector loads of the window rows are legal.
 inline uint32_t vec_ok(const void* base, uint64_t stride) {
     return (stride >= 16 && stride % 16 == 0 && ((uintptr_t)base & 15) == 0) ? 1u : 0u;
+}
+
+// Dword loads of the read rows are legal (every row starts 4-byte aligned
+// and holds a whole number of dwords).
+inline uint32_t read_vec_ok(const void* base, uint64_t stride) {
+    return (stride >= 4 && stride % 4 == 0 && ((uintptr_t)base & 3) == 0) ? 1u : 0u;
 }
 
 // Dynamic LDS bytes for one 64-lane block (one window stream per group).

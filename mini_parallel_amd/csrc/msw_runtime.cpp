@@ -996,6 +996,7 @@ msw::SwParams slot_params(const Scheme& sch, const Slot& s, uint32_t read_stride
     p.end_i = sch.coords ? s.k_ei : nullptr;
     p.end_j = sch.coords ? s.k_ej : nullptr;
     p.read_stride = read_stride;
+    p.read_vec = msw::read_vec_ok(p.reads, p.read_stride);
     if (g) {
         p.win_src = g->d_seq;
         p.win_pos = s.d_pos;
@@ -1021,6 +1022,7 @@ msw::SwParams batch_params(const Scheme& sch, const msw_batch_t& b, const msw_ou
     p.read_stride = b.read_stride;
     p.win_stride = b.win_stride;
     p.win_vec = msw::vec_ok(p.wins, p.win_stride);
+    p.read_vec = msw::read_vec_ok(p.reads, p.read_stride);
     return p;
 }
 

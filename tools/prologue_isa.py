@@ -11,8 +11,19 @@ reports
     lookups): conditional branches on EXEC are taken as "some lane active"
     and loop bodies are counted once; wave-uniform branches (and EXEC
     branches round a region no lane of a fast-path wave runs) are not taken
-    unless their target is listed in --taken (the walk prints each one it
-    meets, so the list is found by reading the ISA beside it);
+    unless their target is listed in --taken, as LABEL or, for the branch
+    at one line alone, LABEL@LINE (-v prints each one the walk
+    meets, so the list is found by reading the ISA beside it).  Without
+    --taken the walk is the one with the fewest instructions, among all
+    choices at the wave-uniform forward branches, that issues in this order
+    a length load, a read load, a 16-byte window load, a v_perm_b32 (the
+    window bytes' canonical form) and a 16-byte LDS write -- the fast path's
+    arms are the short ones: identity order, dword reads, selectors straight
+    from the window bytes, no later round, no trace stamp -- and "taken" in
+    the result lists the branches it took, to check against the ISA and to
+    pin with --taken;
+  * the same counts on the shortest way from that loop's exit to s_endpgm
+    (the epilogue: the group maximum, the convert, the store);
   * VALU per iteration of that loop, NumVgprs, ScratchSize, code bytes.
 
 Usage: python tools/prologue_isa.py [--kr 13] [--taken LBB0_2,LBB0_73,...] [--asm out.s]
@@ -82,49 +93,113 @@ def parse(path):
 
 
 def find_f16_loop(rows):
-    """(header index, back-edge index) of the last loop holding v_perm_b32."""
+    """(header index, back-edge index) of the loop holding v_perm_b32 table
+    lookups beside its three-way maxima: the shortest such span (a cold
+    block laid out behind the loops and branching back in front of them
+    spans them all)."""
     labels = {lab: i for i, (_, lab, _, _) in enumerate(rows) if lab}
     best = None
     for i, (_, _, op, args) in enumerate(rows):
         if op and op.startswith("s_cbranch") and args in labels and labels[args] < i:
             body = rows[labels[args]:i]
             if sum(1 for r in body if r[2] == "v_pk_maximum3_f16") > 8 and any(r[2] == "v_perm_b32" for r in body):
-                best = (labels[args], i)
+                if best is None or i - labels[args] < best[1] - best[0]:
+                    best = (labels[args], i)
     return best
 
 
-def walk(rows, stop, taken, verbose):
+def successors(rows, labels, i, taken, staged=False):
+    """Rows that may follow row i: [(row, branch was taken)].  taken None:
+    wave-uniform forward branches go either way, and so does, once the walk
+    has written selectors (staged), an EXEC branch round a region with vector
+    loads: a fast-path wave issues every load before it stages, only the
+    integer fallback loads again."""
+    _, _, op, args = rows[i]
+    if op is None or kind(op) != "branch":
+        return [(i + 1, False)]
+    tgt = labels.get(args)
+    back = tgt is not None and tgt <= i
+    if op == "s_branch":
+        return [(tgt, True)]
+    if tgt is None or back:
+        return [(i + 1, False)]
+    if op == "s_cbranch_execnz":
+        return [(tgt, True)]
+    listed = taken is not None and (args.lstrip(".") in taken or f"{args.lstrip('.')}@{rows[i][0]}" in taken)
+    if op == "s_cbranch_execz" and taken is None and staged and any(
+            r[2] and r[2].startswith("global_load") for r in rows[i + 1:tgt]):
+        return [(i + 1, False), (tgt, True)]
+    if op == "s_cbranch_execz" or taken is not None:
+        return [(tgt, True)] if listed else [(i + 1, False)]
+    return [(i + 1, False), (tgt, True)]
+
+
+# What the default walk issues before the loop, in this order.
+MARKS = (("global_load_ushort",), ("global_load_dword", "global_load_ubyte"), ("global_load_dwordx4",),
+         ("v_perm_b32",), ("ds_write_b128",))
+
+
+def shortest_walk(rows, stop, marks=MARKS, start=0):
+    """The wave-uniform branches taken (LABEL@LINE) on the walk from row
+    `start` to row `stop` that runs the fewest instructions and issues one
+    opcode of each entry of `marks` in order; or None."""
+    import heapq
     labels = {lab: i for i, (_, lab, _, _) in enumerate(rows) if lab}
-    counts = {"valu": 0, "salu": 0, "branch": 0, "vmem": 0, "lds": 0}
-    i, seen = 0, set()
+    start, goal = (start, 0), (stop, len(marks))
+    dist, prev, heap = {start: 0}, {}, [(0, start)]
+    while heap:
+        d, node = heapq.heappop(heap)
+        i, seen = node
+        if node == goal:
+            break
+        if d > dist.get(node, 1 << 60) or i >= len(rows) or i == stop:
+            continue
+        op = rows[i][2]
+        cost = 1 if op and kind(op) != "other" else 0
+        if seen < len(marks) and rows[i][2] in marks[seen]:
+            seen += 1
+        for j, took in successors(rows, labels, i, None, seen == len(marks)):
+            nxt = (j, seen)
+            if d + cost < dist.get(nxt, 1 << 60):
+                dist[nxt] = d + cost
+                prev[nxt] = (node, took)
+                heapq.heappush(heap, (d + cost, nxt))
+    if goal not in dist:
+        return None
+    out, node = [], goal
+    while node in prev:
+        node, took = prev[node]
+        n, _, op, args = rows[node[0]]
+        if took and op not in ("s_branch", "s_cbranch_execnz"):
+            out.append(f"{args.lstrip('.')}@{n}")  # the branch at that line alone: a label may have several
+    return out[::-1]
+
+
+def walk(rows, stop, taken, verbose, start=0):
+    """The rows run from row `start` to row `stop` with the listed branches
+    taken, or a message where that walk leaves the path."""
+    labels = {lab: i for i, (_, lab, _, _) in enumerate(rows) if lab}
+    i, seen, path = start, set(), []
     while i != stop:
         if i in seen or i >= len(rows):
-            return f"left the path at line {rows[min(i, len(rows) - 1)][0]}: adjust --taken (-v lists the branches met)"
+            return (f"left the path at line {rows[min(i, len(rows) - 1)][0]}: adjust --taken "
+                    "(-v lists the branches met)"), path
         seen.add(i)
-        n, lab, op, args = rows[i]
-        if op is None:
-            i += 1
-            continue
-        k = kind(op)
+        path.append(i)
+        n, _, op, args = rows[i]
+        (j, took), = successors(rows, labels, i, taken)
+        if verbose and op and op.startswith("s_cbranch") and not op.startswith("s_cbranch_exec"):
+            print(f"  line {n}: {op} {args} -> {'taken' if took else 'falls through'}", file=sys.stderr)
+        i = j
+    return None, path
+
+
+def count(rows, path):
+    counts = {"valu": 0, "salu": 0, "branch": 0, "vmem": 0, "lds": 0}
+    for i in path:
+        k = kind(rows[i][2]) if rows[i][2] else "other"
         if k in counts:
             counts[k] += 1
-        if k == "branch":
-            tgt = labels.get(args)
-            back = tgt is not None and tgt <= i
-            if op == "s_branch":
-                go = True
-            elif op == "s_cbranch_execz":  # skipped region (no lane active): only where listed
-                go = args.lstrip(".") in taken and not back
-            elif op == "s_cbranch_execnz":
-                go = not back
-            else:
-                go = args.lstrip(".") in taken and not back
-                if verbose:
-                    print(f"  line {n}: {op} {args} -> {'taken' if go else 'falls through'}", file=sys.stderr)
-            if go:
-                i = tgt
-                continue
-        i += 1
     return counts
 
 
@@ -173,7 +248,37 @@ def main():
     loop = find_f16_loop(rows)
     if loop:
         res["f16_loop_valu_per_iteration"] = sum(1 for r in rows[loop[0]:loop[1]] if r[2] and kind(r[2]) == "valu")
-        res["prologue_path"] = walk(rows, loop[0], set(filter(None, args.taken.split(","))), args.verbose)
+        taken = list(filter(None, args.taken.split(",")))
+        if not taken:
+            taken = shortest_walk(rows, loop[0]) or []
+        res["taken"] = taken
+        left, steps = walk(rows, loop[0], set(taken), args.verbose)
+        res["prologue_path"] = left or count(rows, steps)
+        on = [rows[i] for i in steps if rows[i][2]]
+        loads = [k for k, r in enumerate(on) if r[2].startswith("global_load")]
+        waits = [k for k, r in enumerate(on) if r[2] == "s_waitcnt" and "vmcnt" in r[3]]
+        lds = [k for k, r in enumerate(on) if r[2].startswith("ds_write")]
+        if loads:
+            first_wait = next((k for k in waits if k > loads[0]), len(on))
+            x4 = [k for k in loads if on[k][2] == "global_load_dwordx4" and (not lds or k < lds[0])]
+            # along the walk, not in the text's order: the arms of the early
+            # loads are laid out one behind the other
+            res["vector_loads"] = len(loads)
+            res["vector_loads_before_first_vmcnt_wait"] = sum(1 for k in loads if k < first_wait)
+            res["vmcnt_waits_between_first_vector_load_and_last_first_round_window_load"] = \
+                [on[k][0] for k in waits if x4 and loads[0] < k < x4[-1]]
+        # behind the loop: the fewest instructions from its exit to s_endpgm
+        # (every lane-masked region run, no trace record)
+        ends = [i for i, r in enumerate(rows) if r[2] == "s_endpgm" and i > loop[1]]
+        best = None
+        for e in ends:
+            t = shortest_walk(rows, e, (), loop[1] + 1)
+            if t is not None:
+                left, tail = walk(rows, e, set(t), False, loop[1] + 1)
+                if not left and (best is None or len(tail) < best[0]):
+                    best = (len(tail), count(rows, tail))
+        if best:
+            res["epilogue_path"] = best[1]
     for key in ("NumVgprs", "ScratchSize", "TotalNumSgprs", "codeLenInByte"):
         m = re.search(rf"; {key}[:=]? *=? *(\d+)", text)
         if m:
