@@ -339,6 +339,56 @@ int msw_aln_pack_device(msw_ctx* ctx, const msw_genome* g, const uint8_t* reads,
 int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* batch,
                           msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs);
 
+/* Both strands.
+ *
+ * Reverse complement of a read of length L: rc[k] = comp(read[L-1-k]), where
+ * comp maps A<->T, C<->G, a<->t, c<->g and leaves every other byte value as
+ * it is ('N' included): the scorer compares bytes, so comp is defined on bytes.
+ *
+ * Both-strand scoring of read p against its window: score_f is the result
+ * for the read as given, score_r the result for rc(read) against the same
+ * window; strand[p] = 1 exactly when score_r > score_f, else 0 (ties go to
+ * the forward strand, 0 == 0 and empty reads and windows included).  The
+ * reported score and end cell are the winner's.  end_i, the later start_i and
+ * the CIGAR are in the coordinates of the ORIENTED read: the read itself for
+ * strand 0, its reverse complement for strand 1.  end_j, start_j and ref_pos
+ * are window and genome coordinates as in the one-strand calls, so for strand
+ * 1 ref_pos is still the leftmost genome base of the alignment and the CIGAR
+ * runs left to right along the genome (what SAM stores with flag 0x10).
+ *
+ * Oriented slab: row p of oriented[n][oriented_stride] holds the oriented
+ * read in bytes [0, read_len[p]) and zeros up to the stride;
+ * msw_trace_reads_device and msw_aln_pack_device then run unchanged with
+ * `oriented` / oriented_stride in place of reads / read_stride. */
+
+/* out[p * out_stride ..] = rc(reads[p * read_stride ..][0, read_len[p])),
+ * zeros up to out_stride (every byte of every output row is written).  Device
+ * arrays; the read rows at any alignment and any stride >= the longest read;
+ * `out` 16-byte aligned and out_stride a non-zero multiple of 16, else
+ * MSW_E_INVALID.  Enqueued on `stream`, no host synchronisation. */
+int msw_revcomp_device(msw_ctx* ctx, const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
+                       uint64_t n, uint8_t* out, uint32_t out_stride, void* stream);
+
+/* msw_align_reads_device on both strands: same arguments, window rule and
+ * errors; strand is u8[n], oriented the slab above (16-byte aligned,
+ * oriented_stride a multiple of 16 and >= max_read_len, else MSW_E_INVALID,
+ * as for a NULL strand or oriented).  On the one stream: one window cut shared
+ * by both orientations, the reverse complements, forward scoring into `out`,
+ * reverse scoring into scratch the context keeps per stream, the choice.  With
+ * want_coords = 0, end_i / end_j may be NULL. */
+int msw_align_reads_strands_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                                   const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                                   uint32_t window, uint32_t max_read_len, msw_out_t* out, uint16_t* win_len_out,
+                                   uint8_t* strand, uint8_t* oriented, uint32_t oriented_stride, void* stream);
+
+/* Host memory, synchronous, chunked like msw_align_reads_trace (requested
+ * window lengths from batch->win_len); strand is u8[n_pairs].  aln == NULL:
+ * scores only, coordinates as sc says.  With aln: coordinates are forced, the
+ * oriented rows are traced at the exact stride and packed; ranges and
+ * MSW_E_RANGE as for msw_align_reads_trace. */
+int msw_align_reads_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* batch,
+                            msw_out_t* out, uint8_t* strand, msw_aln_t* aln, uint64_t chunk_pairs);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

@@ -32,6 +32,7 @@ EXPORTED = (
     "msw_memcpy_d2h_async", "msw_fence_record", "msw_fence_wait", "msw_ctx_prepare",
     "msw_stream_create", "msw_stream_destroy", "msw_trace_batch_device", "msw_align_batch_trace",
     "msw_trace_reads_device", "msw_aln_pack_device", "msw_align_reads_trace",
+    "msw_revcomp_device", "msw_align_reads_strands_device", "msw_align_reads_strands",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -130,6 +131,12 @@ def _declare(L):
                                     ctypes.POINTER(TraceT), ctypes.POINTER(AlnT), P]),
         "msw_align_reads_trace": (I, [P, ctypes.POINTER(ScoringT), P, ctypes.POINTER(ReadBatchT),
                                       ctypes.POINTER(OutT), ctypes.POINTER(AlnT), ctypes.c_uint64]),
+        "msw_revcomp_device": (I, [P, P, P, ctypes.c_uint32, ctypes.c_uint64, P, ctypes.c_uint32, P]),
+        "msw_align_reads_strands_device": (I, [P, ctypes.POINTER(ScoringT), P, P, P, ctypes.c_uint32, P,
+                                               ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.POINTER(OutT), P, P, P, ctypes.c_uint32, P]),
+        "msw_align_reads_strands": (I, [P, ctypes.POINTER(ScoringT), P, ctypes.POINTER(ReadBatchT),
+                                        ctypes.POINTER(OutT), P, ctypes.POINTER(AlnT), ctypes.c_uint64]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

@@ -379,6 +379,78 @@ class Context:
                                         ctypes.byref(ends), ctypes.byref(tr), ctypes.byref(aln),
                                         ctypes.c_void_p(stream or None)))
 
+    # -- both strands (include/msw.h, "Both strands") -----------------------------------
+    def revcomp_device(self, reads_ptr: int, read_len_ptr: int, read_stride: int, n: int, out_ptr: int,
+                       out_stride: int, stream: int = 0) -> None:
+        """Enqueue the reverse complement of n device-resident read rows into
+        ``out[n][out_stride]``, zero padded (msw_revcomp_device)."""
+        check(lib().msw_revcomp_device(self.handle, ctypes.c_void_p(reads_ptr), ctypes.c_void_p(read_len_ptr),
+                                       read_stride, n, ctypes.c_void_p(out_ptr), out_stride,
+                                       ctypes.c_void_p(stream or None)))
+
+    def align_reads_strands_device(self, genome: "Genome", reads_ptr: int, read_len_ptr: int, read_stride: int,
+                                   win_pos_ptr: int, n: int, window: int, max_read_len: int, score_ptr: int,
+                                   strand_ptr: int, oriented_ptr: int, oriented_stride: int,
+                                   scoring: Scoring = LINEAR, end_i_ptr: int = 0, end_j_ptr: int = 0,
+                                   win_len_out_ptr: int = 0, stream: int = 0) -> None:
+        """Enqueue both-strand scoring of device-resident reads against their
+        genome windows (msw_align_reads_strands_device): the winner's score
+        and end cell, the strand byte and the oriented row per read."""
+        out = OutT(score_ptr, end_i_ptr or None, end_j_ptr or None)
+        sc = _scoring_c(scoring)
+        check(lib().msw_align_reads_strands_device(
+            self.handle, ctypes.byref(sc), genome.handle, ctypes.c_void_p(reads_ptr), ctypes.c_void_p(read_len_ptr),
+            read_stride, ctypes.c_void_p(win_pos_ptr), n, window, max_read_len, ctypes.byref(out),
+            ctypes.c_void_p(win_len_out_ptr or None), ctypes.c_void_p(strand_ptr or None),
+            ctypes.c_void_p(oriented_ptr or None), oriented_stride, ctypes.c_void_p(stream or None)))
+
+    def align_reads_strands(self, genome: "Genome", reads: np.ndarray, read_len: np.ndarray,
+                            win_pos: np.ndarray, win_len: np.ndarray, scoring: Scoring = LINEAR,
+                            trace: bool = False, chunk_pairs: int = 0, cigar_cap: Optional[int] = None):
+        """:meth:`align_reads` on both strands (msw_align_reads_strands).
+        Returns (score, end_i, end_j, strand): the better of the read and its
+        reverse complement per read, ``strand`` uint8[B] 1 where the reverse
+        complement won (ties: 0); end_i is in the oriented read's coordinates.
+        With ``trace`` it also returns ref_pos, nm and cigars as
+        :meth:`align_reads_trace` does, for the oriented read (coordinates are
+        then always returned), with the same capacity retry."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        win_pos = np.ascontiguousarray(win_pos, dtype=np.int64)
+        win_len = np.ascontiguousarray(win_len, dtype=np.uint16)
+        B = reads.shape[0]
+        if read_len.shape[0] != B or win_pos.shape[0] != B or win_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of pairs")
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0,
+                           _ptr(win_pos), _ptr(win_len), B)
+        sc = _scoring_c(scoring)
+        strand = np.zeros(B, np.uint8)
+        if not trace:
+            (score, ei, ej), out = _outputs(B, scoring.want_coords)
+            check(lib().msw_align_reads_strands(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch),
+                                                ctypes.byref(out), ctypes.c_void_p(_fresh_ptr(strand) or None),
+                                                None, chunk_pairs))
+            return score, ei, ej, strand
+        cap = 4 * B if cigar_cap is None else int(cigar_cap)
+        while True:
+            (score, ei, ej), out = _outputs(B, True)
+            ref_pos, nm = np.empty(B, np.int64), np.empty(B, np.int32)
+            off = np.zeros(B + 1, np.uint32)
+            cig = np.zeros(max(cap, 1), np.uint32)
+            ovf = np.zeros(1, np.uint32)
+            aln = AlnT(_fresh_ptr(ref_pos), _fresh_ptr(nm), _fresh_ptr(off), _fresh_ptr(cig), cap, _fresh_ptr(ovf))
+            check(lib().msw_align_reads_strands(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch),
+                                                ctypes.byref(out), ctypes.c_void_p(_fresh_ptr(strand) or None),
+                                                ctypes.byref(aln), chunk_pairs))
+            total = int(off[B])
+            if total > cap:
+                cap = total  # once: the offsets do not depend on the capacity
+                continue
+            break
+        cigars = CigarList(cig[off[p]:off[p + 1]].copy() for p in range(B))
+        cigars.n_cigar = np.diff(off.astype(np.int64)).astype(np.int32)
+        return score, ei, ej, strand, ref_pos, nm, cigars
+
     # -- HBM-resident batches ----------------------------------------------------------
     def align_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int,
                            win_len_ptr: int, read_stride: int, win_stride: int, n_pairs: int,
@@ -502,6 +574,31 @@ def cigar_string(ops) -> str:
 
 
 _CIGAR_CHARS = {0: "M", 1: "I", 2: "D", 4: "S"}
+
+
+def _comp_table() -> np.ndarray:
+    t = np.arange(256, dtype=np.uint8)
+    for a, b in (b"AT", b"CG", b"at", b"cg"):
+        t[a], t[b] = b, a
+    return t
+
+
+_COMP = _comp_table()
+
+
+def reverse_complement(seq):
+    """The oriented read of a strand-1 record (include/msw.h, "Both
+    strands"): ``rc[k] = comp(seq[L-1-k])``, comp mapping A<->T, C<->G, a<->t,
+    c<->g and leaving every other byte value, N included.  bytes / str / a
+    1-D uint8 array in, the same kind out.  Pure numpy, on the host."""
+    if isinstance(seq, str):
+        return reverse_complement(seq.encode("latin-1")).decode("latin-1")
+    if isinstance(seq, (bytes, bytearray)):
+        return _COMP[np.frombuffer(bytes(seq), np.uint8)[::-1]].tobytes()
+    a = np.asarray(seq)
+    if a.dtype != np.uint8 or a.ndim != 1:
+        raise TypeError("reverse_complement takes bytes, str or a 1-D uint8 array")
+    return _COMP[a[::-1]]
 
 
 class Pending:

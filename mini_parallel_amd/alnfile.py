@@ -4,13 +4,20 @@ Little-endian, a sequence of self-contained blocks in whatever order the
 batches of a lane file settled:
 
   header, 32 B   u32 magic "MSWA", u32 version = 1, u64 first_read (index in
-                 the lane file), u32 n_reads, u32 n_ops, 8 B zero
+                 the lane file), u32 n_reads, u32 n_ops, u32 flags, 4 B zero
   n_reads x 24 B i64 ref_pos, i32 score, i32 nm, u32 n_ops, i16 end_i, i16 end_j
   n_ops x u32    packed ops in read order (len << 4 | op, M=0 I=1 D=2 S=4)
+  flags bit 0:   n_reads x u8 strand (0 / 1), zero-padded to a multiple of 4 B
+
+Flag bit 0 (``--both-strands``): the block carries one strand byte per read; a
+strand-1 record's end_i and CIGAR are in the coordinates of the read's reverse
+complement (include/msw.h, "Both strands").  A block without the flag is byte
+for byte what it was before the flag existed (the field was 8 zero bytes), and
+a file may hold both kinds.  Every other flag bit is refused.
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -18,25 +25,29 @@ from .aligner import CigarList
 
 MAGIC = b"MSWA"
 VERSION = 1
+FLAG_STRAND = 1
 HEADER = np.dtype([("magic", "S4"), ("version", "<u4"), ("first_read", "<u8"), ("n_reads", "<u4"),
-                   ("n_ops", "<u4"), ("zero", "<u8")])
+                   ("n_ops", "<u4"), ("flags", "<u4"), ("zero", "<u4")])
 RECORD = np.dtype([("ref_pos", "<i8"), ("score", "<i4"), ("nm", "<i4"), ("n_ops", "<u4"), ("end_i", "<i2"),
                    ("end_j", "<i2")])
 assert HEADER.itemsize == 32 and RECORD.itemsize == 24
 
 
 class Alignments(NamedTuple):
-    """Per-read arrays in read order; ``cigars[p]`` is a uint32 array."""
+    """Per-read arrays in read order; ``cigars[p]`` is a uint32 array;
+    ``strand`` is 0 for reads from blocks without strand bytes."""
     ref_pos: np.ndarray
     score: np.ndarray
     nm: np.ndarray
     end_i: np.ndarray
     end_j: np.ndarray
     cigars: CigarList
+    strand: np.ndarray
 
 
 class AlnBlock(NamedTuple):
-    """One block to write: reads first_read .. first_read + len(score)."""
+    """One block to write: reads first_read .. first_read + len(score).  With
+    ``strand`` (0 / 1 per read) the block is written with flag bit 0."""
     first_read: int
     ref_pos: Sequence
     score: Sequence
@@ -44,6 +55,7 @@ class AlnBlock(NamedTuple):
     end_i: Sequence
     end_j: Sequence
     cigars: Sequence
+    strand: Optional[Sequence] = None
 
 
 def write_alignments(path, blocks: Sequence[AlnBlock]) -> None:
@@ -62,13 +74,24 @@ def write_alignments(path, blocks: Sequence[AlnBlock]) -> None:
             head = np.zeros(1, HEADER)
             head["magic"], head["version"], head["first_read"] = MAGIC, VERSION, int(b.first_read)
             head["n_reads"], head["n_ops"] = n, ops.size
-            f.write(head.tobytes() + rec.tobytes() + ops.tobytes())
+            tail = b""
+            if b.strand is not None:
+                strand = np.asarray(b.strand, np.int64).reshape(-1)
+                if strand.size != n:
+                    raise ValueError("block arrays disagree on the number of reads")
+                if ((strand != 0) & (strand != 1)).any():
+                    raise ValueError("a strand byte is neither 0 nor 1")
+                head["flags"] = FLAG_STRAND
+                tail = strand.astype(np.uint8).tobytes() + bytes(-n % 4)
+            f.write(head.tobytes() + rec.tobytes() + ops.tobytes() + tail)
 
 
 def read_alignments(path) -> Alignments:
     """Read an ``.aln`` file back into read order.  Raises ValueError on a bad
-    magic or version, a truncated block, op counts that do not add up, or
-    blocks that do not tile [0, N) exactly (a gap or an overlap)."""
+    magic or version, an undefined flag bit or non-zero reserved bytes, a
+    truncated block (inside its strand bytes included), a strand byte other
+    than 0 / 1, op counts that do not add up, or blocks that do not tile
+    [0, N) exactly (a gap or an overlap)."""
     with open(path, "rb") as f:
         data = f.read()
     blocks = []
@@ -81,10 +104,14 @@ def read_alignments(path) -> Alignments:
             raise ValueError(f"{path}: bad magic at byte {at}")
         if int(head["version"]) != VERSION:
             raise ValueError(f"{path}: version {int(head['version'])}, expected {VERSION}")
+        flags = int(head["flags"])
+        if flags & ~FLAG_STRAND:
+            raise ValueError(f"{path}: undefined flag bits {flags & ~FLAG_STRAND:#x} at byte {at}")
         if int(head["zero"]) != 0:
             raise ValueError(f"{path}: reserved header bytes are not zero at byte {at}")
         n, n_ops = int(head["n_reads"]), int(head["n_ops"])
-        size = HEADER.itemsize + n * RECORD.itemsize + n_ops * 4
+        strand_bytes = (n + 3) // 4 * 4 if flags & FLAG_STRAND else 0
+        size = HEADER.itemsize + n * RECORD.itemsize + n_ops * 4 + strand_bytes
         if len(data) - at < size:
             raise ValueError(f"{path}: truncated block at byte {at} ({len(data) - at} of {size} bytes)")
         rec = np.frombuffer(data, RECORD, n, at + HEADER.itemsize)
@@ -92,21 +119,30 @@ def read_alignments(path) -> Alignments:
         if int(rec["n_ops"].sum(dtype=np.uint64)) != n_ops:
             raise ValueError(f"{path}: the records of the block at byte {at} hold "
                              f"{int(rec['n_ops'].sum(dtype=np.uint64))} ops, its header says {n_ops}")
-        blocks.append((int(head["first_read"]), rec, ops))
+        strand = np.zeros(n, np.uint8)
+        if flags & FLAG_STRAND:
+            raw = np.frombuffer(data, np.uint8, strand_bytes, at + size - strand_bytes)
+            if (raw[:n] > 1).any():
+                raise ValueError(f"{path}: a strand byte of the block at byte {at} is neither 0 nor 1")
+            if raw[n:].any():
+                raise ValueError(f"{path}: the strand padding of the block at byte {at} is not zero")
+            strand = raw[:n].copy()
+        blocks.append((int(head["first_read"]), rec, ops, strand))
         at += size
     blocks.sort(key=lambda b: (b[0], len(b[1])))  # an empty block sits before the reads at its index
     nxt = 0
-    for first, rec, _ in blocks:
+    for first, rec, _, _ in blocks:
         if first > nxt:
             raise ValueError(f"{path}: gap: reads {nxt}..{first - 1} are in no block")
         if first < nxt:
             raise ValueError(f"{path}: overlap: read {first} is in two blocks")
         nxt = first + len(rec)
     rec = np.concatenate([b[1] for b in blocks]) if blocks else np.zeros(0, RECORD)
+    strand = np.concatenate([b[3] for b in blocks]) if blocks else np.zeros(0, np.uint8)
     cigars = CigarList()
-    for _, r, ops in blocks:
+    for _, r, ops, _ in blocks:
         off = np.concatenate([[0], np.cumsum(r["n_ops"], dtype=np.int64)])
         cigars.extend(ops[off[k]:off[k + 1]].astype(np.uint32) for k in range(len(r)))
     cigars.n_cigar = rec["n_ops"].astype(np.int32)
     return Alignments(rec["ref_pos"].astype(np.int64), rec["score"].astype(np.int32), rec["nm"].astype(np.int32),
-                      rec["end_i"].astype(np.int16), rec["end_j"].astype(np.int16), cigars)
+                      rec["end_i"].astype(np.int16), rec["end_j"].astype(np.int16), cigars, strand)

@@ -77,6 +77,10 @@ void usage() {
         "                               <lane file>.aln per file (genome position, score, NM, CIGAR with soft\n"
         "                               clips; blocks of reads, see DESIGN.md 4.10).  Reads <= 384 and windows\n"
         "                               <= 4096 bases.  Not available with the host (gzip) lane reader.\n"
+        "      --both-strands           --full-wgs sw, BGZF lane files read on the GPU: score each read and its\n"
+        "                               reverse complement against the window and keep the better (ties: the read\n"
+        "                               as given); .aln blocks then carry a strand byte per read, and a strand-1\n"
+        "                               record's end_i and CIGAR are in the reverse complement's coordinates\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -115,6 +119,7 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--json") a.json = v();
         else if (s == "--scores-out") a.scores_out = v();
         else if (s == "--alignments-out") a.alignments_out = v();
+        else if (s == "--both-strands") a.both_strands = true;
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -131,6 +136,12 @@ Args parse_args(int argc, char** argv) {
             die("error: --alignments-out traces reads of at most 384 bases (MSW_MAX_READ_LEN)");
         if (env_or("MSW_GPU_INFLATE", "1") == "0")
             die("error: --alignments-out needs the GPU lane reader (MSW_GPU_INFLATE=0 selects the host reader)");
+    }
+    if (a.both_strands) {
+        // refused here, before any file is opened, like --alignments-out
+        if (!a.full_wgs || a.score_mode != "sw") die("error: --both-strands needs --full-wgs --score-mode sw");
+        if (env_or("MSW_GPU_INFLATE", "1") == "0")
+            die("error: --both-strands needs the GPU lane reader (MSW_GPU_INFLATE=0 selects the host reader)");
     }
     return a;
 }
@@ -241,6 +252,8 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
                       std::to_string(a.mismatch) + "|" + std::to_string(a.gap_open) + "|" +
                       std::to_string(a.gap_extend) + "|" + std::to_string(a.window) + "|" +
                       env_or("WGS_FILE_SHARD", "");
+    // a run on both strands never resumes a one-strand checkpoint, nor the other way round
+    if (a.both_strands) key += "|both-strands";
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -391,6 +404,7 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
       << ", \"result_sets_ms\": " << rep.result_sets_ms << ", \"lane_reader_ms\": " << rep.lane_reader_ms
       << ", \"kernel_load_ms\": " << rep.kernel_load_ms << "}"
       << ", \"teardown_ms\": " << rep.teardown_ms
+      << ", \"both_strands\": " << (rep.both_strands ? "true" : "false") << ", \"reverse_reads\": " << rep.reverse_reads
       << ", \"inflate_bytes_in\": " << rep.gz_in << ", \"inflate_bytes_out\": " << rep.gz_out
       << ", \"reads_per_second\": " << reads / secs << ", \"t_main_unix_ns\": " << in.t_main_ns
       << ", \"t_record_unix_ns\": " << unix_ns() << "}\n";
@@ -426,6 +440,7 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
         all_ok = all_ok && r.completed;
     }
     printf("Total reads: %llu, total bases: %llu, total score: %lld\n", tot.reads, tot.bases, tot.score);
+    if (rep.both_strands) printf("Both strands: %llu reverse reads\n", rep.reverse_reads);
     printf("Wall time: %.2f s", rep.wall_ms / 1000.0);
     if (rep.cells) printf(", %.1f GCUPS end-to-end", rep.cells / (rep.wall_ms * 1e6));
     printf("\n");

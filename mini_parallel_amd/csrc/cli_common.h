@@ -71,6 +71,7 @@ struct Args {
     std::string seq1, seq2;
     bool has_seq1 = false, has_seq2 = false, files = false, gpu = false, test_wgs = false, full_wgs = false;
     bool cigar = false;
+    bool both_strands = false;  // --both-strands: --full-wgs sw scores each read and its reverse complement
     long chunk_size = 1, num_files = -1;
     std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out, alignments_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;

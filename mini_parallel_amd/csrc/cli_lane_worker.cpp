@@ -186,6 +186,10 @@ struct ResultSet {
     uint64_t fence = 0;  // after the batch's copy-back (msw_fence_record)
     bool live = false;
     uint64_t* rec = nullptr;  // --scores-out: the batch's records (recbuf)
+    // --both-strands: the batch's oriented rows [batch][read_stride()] and
+    // strand bytes.  They belong to the set, not to the reader, so the trace
+    // and a second trace at the exact stride read them while the set is live.
+    uint8_t *d_oriented = nullptr, *d_strand = nullptr, *h_strand = nullptr;
     AlnSet aln;
     msw_out_t out() const { return msw_out_t{d_score, d_ei, d_ej}; }
 };
@@ -210,7 +214,7 @@ class LaneWorker {
     WgsRun& run_;
     const Args& a_;
     const int wi_, gi_;
-    const bool aln_;
+    const bool aln_, both_;
     const uint64_t batch_;
     Clock::time_point ts0_;
     Ctx ctx_;
@@ -233,7 +237,7 @@ class LaneWorker {
 // prefetch, genome, kernels, result sets.
 LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     : lanes_(lanes), run_(lanes.run), a_(lanes.run.a), wi_(wi), gi_(wi % lanes.run.ngpu), aln_(lanes.aln),
-      batch_(lanes.batch), ts0_(Clock::now()),
+      both_(lanes.both), batch_(lanes.batch), ts0_(Clock::now()),
       // lean: a GPU-reader worker scores device-resident batches
       // only, so its context makes just the compute stream
       ctx_(lanes.run.devices[gi_].ordinal, MSW_CTX_LEAN) {
@@ -281,6 +285,13 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
         if (!r.d_score || !r.d_ei || !r.d_ej || !r.d_wlen || !h)
             die(std::string("GPU lane reader buffers: ") + msw_last_error());
         r.h = HostResults(h, batch_);
+        if (both_) {
+            r.d_oriented = (uint8_t*)msw_dev_alloc(ctx_.h, batch_ * read_stride());
+            r.d_strand = (uint8_t*)msw_dev_alloc(ctx_.h, batch_);
+            r.h_strand = (uint8_t*)msw_host_alloc(batch_);
+            if (!r.d_oriented || !r.d_strand || !r.h_strand)
+                die(std::string("GPU lane reader strand buffers: ") + msw_last_error());
+        }
     }
     // per-read records of a batch, built here and written from here:
     // allocated and touched in setup (a fresh 2 MB buffer per batch
@@ -387,7 +398,7 @@ void LaneWorker::write_aln_block(ResultSet& r, FileState& f) {
     std::vector<uint8_t>& block = r.aln.block;
     block.clear();
     append_aln_block(block, r.first, r.n, r.aln.h.ref_pos, r.h.score, r.aln.h.nm, r.aln.h.off, r.h.end_i, r.h.end_j,
-                     r.aln.h_ops, r.aln.n_ops);
+                     r.aln.h_ops, r.aln.n_ops, both_ ? r.h_strand : nullptr);
     size_t done = 0;
     while (done < block.size()) {
         const ssize_t w = write(f.aln_fd, block.data() + done, block.size() - done);
@@ -430,6 +441,11 @@ void LaneWorker::settle(ResultSet& r) {
         f.bases += nb;
         f.reads += r.n;
         run_.cells += cl;
+        if (both_) {
+            unsigned long long rev = 0;
+            for (uint64_t i = 0; i < r.n; ++i) rev += r.h_strand[i];
+            run_.reverse_reads += rev;
+        }
         if (rec && pwrite(f.scores_fd, rec, r.n * 8, (off_t)(r.first * 8)) != (ssize_t)(r.n * 8)) {
             fprintf(stderr, "  error writing scores for %s\n", f.path.c_str());
             f.failed = true;
@@ -449,15 +465,26 @@ void LaneWorker::settle(ResultSet& r) {
 bool LaneWorker::submit(ResultSet& r, const msw_dev_reads_t& d, size_t fi, void* stream) {
     FileState& f = *run_.st[fi];
     msw_out_t o = r.out();
-    if (msw_align_reads_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, d.pos, d.n,
-                               window_for(a_, 0), d.max_len, &o, r.d_wlen, stream) != MSW_OK ||
+    // the reads the trace and the pack see: the reader's rows, or with
+    // --both-strands the set's oriented rows
+    msw_dev_reads_t da = d;
+    if (both_) {
+        da.reads = r.d_oriented;
+        da.read_stride = read_stride();
+    }
+    if ((both_ ? msw_align_reads_strands_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, d.pos, d.n,
+                                                window_for(a_, 0), d.max_len, &o, r.d_wlen, r.d_strand, r.d_oriented,
+                                                read_stride(), stream) != MSW_OK ||
+                     msw_memcpy_d2h_async(ctx_.h, r.h_strand, r.d_strand, d.n, stream) != MSW_OK
+               : msw_align_reads_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, d.pos, d.n,
+                                        window_for(a_, 0), d.max_len, &o, r.d_wlen, stream) != MSW_OK) ||
         msw_memcpy_d2h_async(ctx_.h, r.h.score, r.d_score, d.n * 4, stream) != MSW_OK ||
         // end cells only feed --scores-out records
         (sc_.want_coords && (msw_memcpy_d2h_async(ctx_.h, r.h.end_i, r.d_ei, d.n * 2, stream) != MSW_OK ||
                              msw_memcpy_d2h_async(ctx_.h, r.h.end_j, r.d_ej, d.n * 2, stream) != MSW_OK)) ||
         msw_memcpy_d2h_async(ctx_.h, r.h.read_len, d.read_len, d.n * 2, stream) != MSW_OK ||
         msw_memcpy_d2h_async(ctx_.h, r.h.win_len, r.d_wlen, d.n * 2, stream) != MSW_OK ||
-        (aln_ ? (r.aln.d = d, r.aln.stream = stream, !r.aln.run(env_, o, aln_stride_, r.aln.d_rows, true))
+        (aln_ ? (r.aln.d = da, r.aln.stream = stream, !r.aln.run(env_, o, aln_stride_, r.aln.d_rows, true))
               : msw_fence_record(ctx_.h, stream, &r.fence) != MSW_OK)) {
         fprintf(stderr, "  GPU %d alignment error: %s\n", gi_, msw_last_error());
         f.failed = true;

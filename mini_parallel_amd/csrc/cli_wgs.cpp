@@ -231,6 +231,8 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
                     : total;
     rep.teardown_ms = total - rep.wall_ms;
     rep.cells = cells.load();
+    rep.both_strands = a.both_strands;
+    rep.reverse_reads = reverse_reads.load();
     rep.readers = readers;
     rep.host_threads = host_threads;
     rep.gpu = gpu;
@@ -248,8 +250,8 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
 // (msw_gfastq_* + msw_align_reads_device).  Per-read results come back to
 // the host for the i64 sums and --scores-out, one batch behind the GPU.
 // ---------------------------------------------------------------------------
-LaneRun::LaneRun(WgsRun& run_, bool aln_, bool per_read_, uint64_t batch_, int nworkers_)
-    : run(run_), aln(aln_), per_read(per_read_), batch(batch_), nworkers(nworkers_),
+LaneRun::LaneRun(WgsRun& run_, bool aln_, bool per_read_, bool both_, uint64_t batch_, int nworkers_)
+    : run(run_), aln(aln_), per_read(per_read_), both(both_), batch(batch_), nworkers(nworkers_),
       started(new std::atomic<int>[run_.st.size()]), gstats((size_t)nworkers_, msw_stats_t{}) {
     for (size_t i = 0; i < run.st.size(); ++i) started[i] = 0;
 }
@@ -270,7 +272,7 @@ static WgsReport run_gpu_lanes(WgsRun& run, bool aln, bool per_read) {
     // host reads overlap the other's scoring
     // (three or four workers per GPU measured slower: DESIGN.md 5)
     const int per_gpu = 2;
-    LaneRun lanes(run, aln, per_read, batch, run.ngpu * per_gpu);
+    LaneRun lanes(run, aln, per_read, run.a.both_strands, batch, run.ngpu * per_gpu);
     std::vector<std::thread> workers;
     for (int wi = 0; wi < lanes.nworkers; ++wi) workers.emplace_back(lane_worker, std::ref(lanes), wi);
     run.start_clock(lanes.nworkers);
@@ -636,5 +638,8 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
     if (aln && !run.todo.empty() && !gpu_reader)
         die("error: --alignments-out needs BGZF lane files (the GPU lane reader); the host reader does not write "
             "alignments");
+    if (a.both_strands && !run.todo.empty() && !gpu_reader)
+        die("error: --both-strands needs BGZF lane files (the GPU lane reader); the host reader scores the reads as "
+            "given");
     return gpu_reader ? run_gpu_lanes(run, aln, !a.scores_out.empty() || aln) : run_host_readers(run);
 }

@@ -112,6 +112,8 @@ struct WgsReport {
     double reference_load_ms = 0, context_ms = 0, genome_ms = 0, result_sets_ms = 0, lane_reader_ms = 0;
     double kernel_load_ms = 0;  // msw_ctx_prepare: the scoring kernels' code objects, before the clock
     unsigned long long gz_in = 0, gz_out = 0;  // compressed / inflated bytes (GPU lane reader)
+    bool both_strands = false;                 // --both-strands
+    unsigned long long reverse_reads = 0;      // reads of this run whose reverse complement won (strand 1)
 };
 
 // The window of a read of `len` bases: --window, else 2 x read length capped
@@ -149,6 +151,7 @@ struct WgsRun {
     std::vector<size_t> todo;  // indices into files / st of the files not completed by an earlier run
     std::mutex ck_mu;
     std::atomic<unsigned long long> cells{0};
+    std::atomic<unsigned long long> reverse_reads{0};  // --both-strands: strand-1 reads
     StartGate gate;
     Clock::time_point t_setup, t_all;
     // the clock stops when the last worker has its last results on the host;
@@ -178,6 +181,7 @@ struct LaneRun {
     WgsRun& run;
     const bool aln;       // --alignments-out
     const bool per_read;  // per-read output of either kind: best cells, 256k-read batches, two streams
+    const bool both;      // --both-strands
     const uint64_t batch;  // reads per scoring launch
     const int nworkers;
     std::atomic<size_t> next_file{0};
@@ -191,7 +195,7 @@ struct LaneRun {
     std::vector<msw_stats_t> gstats;  // per worker
 
     static constexpr size_t kNone = ~(size_t)0;
-    LaneRun(WgsRun& run, bool aln, bool per_read, uint64_t batch, int nworkers);
+    LaneRun(WgsRun& run, bool aln, bool per_read, bool both, uint64_t batch, int nworkers);
     size_t claim() {
         const size_t k = next_file.fetch_add(1);
         return k < run.todo.size() ? run.todo[k] : kNone;

@@ -308,6 +308,24 @@ constexpr uint32_t kAlnScanTile = 1024;
 // freed stream-ordered.
 hipError_t launch_aln_pack(const AlnParams& p, hipStream_t stream);
 
+// Both strands (msw_strand.hip; the contract is in include/msw.h).
+// out[p][0, read_len[p]) = the reverse complement of read row p, zeros up to
+// out_stride: every byte of every output row is written.  out 16-byte
+// aligned, out_stride a multiple of 16 (else hipErrorInvalidValue, nothing
+// launched); the read rows at any alignment and stride.
+hipError_t launch_revcomp_rows(const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride, uint64_t n,
+                               uint8_t* out, uint32_t out_stride, hipStream_t stream);
+// strand[p] = score_r[p] > score[p]; where it is 1 the reverse results move
+// into score / end_i / end_j (the end arrays may all be null), where it is 0
+// the forward read row replaces row p of `oriented` (which holds the reverse
+// complements on entry), zero padded.
+hipError_t launch_strand_select(const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride, uint64_t n,
+                                uint8_t* oriented, uint32_t oriented_stride, int32_t* score, int16_t* end_i,
+                                int16_t* end_j, const int32_t* score_r, const int16_t* end_i_r,
+                                const int16_t* end_j_r, uint8_t* strand, hipStream_t stream);
+// blocks per CU of the two kernels (the smaller); the query loads the module
+int strand_blocks_per_cu();
+
 // smith_waterman_align restated: result must be zeroed before the launch.
 hipError_t launch_compat(const uint8_t* s1, const uint8_t* s2, int32_t* result, uint64_t L,
                          uint32_t W, uint64_t G, hipStream_t stream);

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <atomic>
 #include <deque>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -386,6 +387,9 @@ struct msw_ctx {
         uint8_t* wins = nullptr;
         uint16_t* wlen = nullptr;
         size_t wins_cap = 0, wlen_cap = 0;
+        // both strands: the reverse pass's results [score i32 | end_i i16 | end_j i16]
+        uint8_t* rev = nullptr;
+        size_t rev_cap = 0;
     };
     std::vector<ReadsScratch> rscratch;
     // streams made by msw_stream_create (synchronised by msw_synchronize,
@@ -1651,6 +1655,7 @@ void msw_ctx_destroy(msw_ctx* ctx) {
     for (auto& r : ctx->rscratch) {
         (void)hipFree(r.wins);
         (void)hipFree(r.wlen);
+        (void)hipFree(r.rev);
     }
     for (hipStream_t st : ctx->user_streams) {
         (void)hipStreamSynchronize(st);
@@ -2255,19 +2260,14 @@ int msw_align_reads_async(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genom
     return MSW_OK;
 }
 
-int msw_align_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
-                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
-                           uint32_t window, uint32_t max_read_len, msw_out_t* out, uint16_t* win_len_out,
-                           void* stream) {
-    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    if (n == 0) return MSW_OK;
-    if (!reads || !read_len || !win_pos || !out || !out->score) return fail(MSW_E_INVALID, "NULL array");
-    if (window > (uint32_t)msw::kMaxLongLen) return fail(MSW_E_RANGE, "window %u > %d", window, msw::kMaxLongLen);
-    int rc = set_device(ctx);
-    if (rc) return rc;
+// The window cut of the device-resident reads calls: the windows of n reads
+// into the stream's scratch slab; b gets the slab, the clipped lengths and the
+// stride (its reads stay the caller's), *max_win_out the window bound.
+static int cut_reads_windows(msw_ctx* ctx, const msw_genome* g, const uint16_t* read_len, const int64_t* win_pos,
+                             uint64_t n, uint32_t window, uint32_t max_read_len, uint16_t* win_len_out,
+                             hipStream_t st, msw_batch_t* b, uint32_t* max_win_out) {
+    int rc;
     const uint32_t max_win = window ? window : std::min<uint32_t>(2u * max_read_len, (uint32_t)msw::kMaxWinLen);
-    hipStream_t st = call_stream(ctx, stream);
     harvest_dev_timings(ctx, false);
     const uint32_t ws = std::max<uint32_t>(16u, (max_win + 15u) & ~15u);
     const size_t wbytes = (size_t)n * ws;
@@ -2293,39 +2293,191 @@ int msw_align_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
     }
     HIP_TRY(msw::launch_cut_windows_for_reads(g->d_seq, g->len, win_pos, read_len, window, rs->wins, wlen, ws, n,
                                               st));
-    msw_batch_t b{reads, rs->wins, read_len, wlen, read_stride, ws, n};
-    msw_ctx::DevTiming t{take_event(ctx), take_event(ctx), n};
+    b->wins = rs->wins;
+    b->read_len = read_len;
+    b->win_len = wlen;
+    b->win_stride = ws;
+    b->n_pairs = n;
+    *max_win_out = max_win;
+    return MSW_OK;
+}
+
+// One scoring pass of a device-resident reads call over the cut windows,
+// between the timing events msw_ctx_stats harvests.
+static int score_reads_batch(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
+                             uint32_t max_read_len, uint32_t max_win, void* stream, hipStream_t st) {
+    int rc;
+    msw_ctx::DevTiming t{take_event(ctx), take_event(ctx), b->n_pairs};
     if (!t.k0 || !t.k1) return fail(MSW_E_DEVICE, "hipEventCreate failed");
     HIP_TRY(hipEventRecord(t.k0, st));
-    if ((rc = msw_align_batch_device(ctx, sc, &b, out, max_read_len, max_win, stream))) return rc;
+    if ((rc = msw_align_batch_device(ctx, sc, b, out, max_read_len, max_win, stream))) return rc;
     HIP_TRY(hipEventRecord(t.k1, st));
     ctx->dev_timings.push_back(t);
     return MSW_OK;
 }
 
-int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
-                          msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
+int msw_align_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                           uint32_t window, uint32_t max_read_len, msw_out_t* out, uint16_t* win_len_out,
+                           void* stream) {
+    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    if (n == 0) return MSW_OK;
+    if (!reads || !read_len || !win_pos || !out || !out->score) return fail(MSW_E_INVALID, "NULL array");
+    if (window > (uint32_t)msw::kMaxLongLen) return fail(MSW_E_RANGE, "window %u > %d", window, msw::kMaxLongLen);
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    hipStream_t st = call_stream(ctx, stream);
+    msw_batch_t b{reads, nullptr, read_len, nullptr, read_stride, 0, n};
+    uint32_t max_win = 0;
+    if ((rc = cut_reads_windows(ctx, g, read_len, win_pos, n, window, max_read_len, win_len_out, st, &b, &max_win)))
+        return rc;
+    return score_reads_batch(ctx, sc, &b, out, max_read_len, max_win, stream, st);
+}
+
+static int check_oriented(const void* strand, const void* oriented, uint32_t oriented_stride, uint32_t max_read_len) {
+    if (!strand || !oriented) return fail(MSW_E_INVALID, "strand/oriented is NULL");
+    if (((uintptr_t)oriented & 15) != 0 || oriented_stride == 0 || oriented_stride % 16 != 0)
+        return fail(MSW_E_INVALID, "oriented must be 16-byte aligned and oriented_stride a non-zero multiple of 16");
+    if (oriented_stride < max_read_len) return fail(MSW_E_INVALID, "oriented_stride is below max_read_len");
+    return MSW_OK;
+}
+
+// Both orientations of the device batch b (windows cut) on one stream:
+// reverse complements into `oriented`, forward scoring into `out`, reverse
+// scoring into the stream's own scratch, then the choice per read.  `score`
+// is one scoring pass (both go through msw_align_batch_device).
+using ScorePass = std::function<int(const msw_batch_t*, msw_out_t*)>;
+static int score_both_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out, uint8_t* strand,
+                              uint8_t* oriented, uint32_t oriented_stride, hipStream_t st, const ScorePass& score) {
+    const uint64_t n = b->n_pairs;
+    int rc;
+    HIP_TRY(msw::launch_revcomp_rows(b->reads, b->read_len, b->read_stride, n, oriented, oriented_stride, st));
+    if ((rc = score(b, out))) return rc;
+    const bool coords = sc->want_coords != 0;
+    // [score i32 | end_i i16 | end_j i16], n each, in the stream's own scratch:
+    // everything that touches it is ordered on `st`
+    msw_ctx::ReadsScratch* rs = nullptr;
+    for (auto& r : ctx->rscratch)
+        if (r.st == st) rs = &r;
+    if (!rs) {
+        ctx->rscratch.emplace_back();
+        rs = &ctx->rscratch.back();
+        rs->st = st;
+    }
+    const size_t need = n * 8 + 16;
+    if (need > rs->rev_cap) {
+        if ((rc = grow_dev(&rs->rev, need + need / 4))) return rc;
+        rs->rev_cap = need + need / 4;
+    }
+    uint8_t* tmp = rs->rev;
+    msw_out_t rout = {reinterpret_cast<int32_t*>(tmp), nullptr, nullptr};
+    if (coords) {
+        rout.end_i = reinterpret_cast<int16_t*>(tmp + n * 4);
+        rout.end_j = rout.end_i + n;
+    }
+    msw_batch_t rb = *b;
+    rb.reads = oriented;
+    rb.read_stride = oriented_stride;
+    rc = score(&rb, &rout);
+    hipError_t e = hipSuccess;
+    if (rc == MSW_OK)
+        e = msw::launch_strand_select(b->reads, b->read_len, b->read_stride, n, oriented, oriented_stride, out->score,
+                                      coords ? out->end_i : nullptr, coords ? out->end_j : nullptr, rout.score,
+                                      rout.end_i, rout.end_j, strand, st);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return MSW_OK;
+}
+
+int msw_revcomp_device(msw_ctx* ctx, const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride, uint64_t n,
+                       uint8_t* out, uint32_t out_stride, void* stream) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    if (n == 0) return MSW_OK;
+    if (!reads || !read_len || !out) return fail(MSW_E_INVALID, "NULL array");
+    if (read_stride == 0) return fail(MSW_E_INVALID, "read_stride is 0");
+    if (((uintptr_t)out & 15) != 0 || out_stride == 0 || out_stride % 16 != 0)
+        return fail(MSW_E_INVALID, "out must be 16-byte aligned and out_stride a non-zero multiple of 16");
+    if (n > 0x7FFFFFFFull || n * (out_stride / 16u) > (0x7FFFFFFFull << 8))
+        return fail(MSW_E_RANGE, "revcomp: too many rows in one call");
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    HIP_TRY(msw::launch_revcomp_rows(reads, read_len, read_stride, n, out, out_stride, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_align_reads_strands_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                                   const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                                   uint32_t window, uint32_t max_read_len, msw_out_t* out, uint16_t* win_len_out,
+                                   uint8_t* strand, uint8_t* oriented, uint32_t oriented_stride, void* stream) {
+    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    if (!sc) return fail(MSW_E_INVALID, "scoring is NULL");
+    if (n == 0) return MSW_OK;
+    if (!reads || !read_len || !win_pos || !out || !out->score) return fail(MSW_E_INVALID, "NULL array");
+    if (sc->want_coords && (!out->end_i || !out->end_j)) return fail(MSW_E_INVALID, "want_coords needs end_i / end_j");
+    int rc;
+    if ((rc = check_oriented(strand, oriented, oriented_stride, max_read_len))) return rc;
+    if (window > (uint32_t)msw::kMaxLongLen) return fail(MSW_E_RANGE, "window %u > %d", window, msw::kMaxLongLen);
+    if (max_read_len > read_stride) return fail(MSW_E_INVALID, "max_read_len exceeds read_stride");
+    if (n > 0x7FFFFFFFull || n * (oriented_stride / 16u) > (0x7FFFFFFFull << 8))
+        return fail(MSW_E_RANGE, "both strands: too many rows in one call");
+    // scheme and bounds before anything is enqueued (the scoring passes check them again)
+    Scheme sch;
+    if ((rc = make_scheme(sc, ctx->opt, &sch))) return rc;
+    const uint32_t bound_win = window ? window : std::min<uint32_t>(2u * max_read_len, (uint32_t)msw::kMaxWinLen);
+    if ((rc = check_bounds(sch, max_read_len, bound_win))) return rc;
+    if ((rc = set_device(ctx))) return rc;
+    hipStream_t st = call_stream(ctx, stream);
+    msw_batch_t b{reads, nullptr, read_len, nullptr, read_stride, 0, n};
+    uint32_t max_win = 0;
+    if ((rc = cut_reads_windows(ctx, g, read_len, win_pos, n, window, max_read_len, win_len_out, st, &b, &max_win)))
+        return rc;
+    return score_both_strands(ctx, sc, &b, out, strand, oriented, oriented_stride, st,
+                              [&](const msw_batch_t* pb, msw_out_t* po) {
+                                  return score_reads_batch(ctx, sc, pb, po, max_read_len, max_win, stream, st);
+                              });
+}
+
+// The body of msw_align_reads_trace (strand == NULL: aln required) and of
+// msw_align_reads_strands (strand != NULL: both orientations are scored, the
+// trace and the pack read the oriented rows, and aln may be NULL for scores
+// alone, with coordinates as sc says).
+static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
+                         msw_out_t* out, msw_aln_t* aln, uint8_t* strand, bool both, uint64_t chunk_pairs) {
     if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
     if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
     if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
     msw_scoring_t scc = *sc;
-    scc.want_coords = 1;
+    if (aln) scc.want_coords = 1;
+    const bool coords = scc.want_coords != 0;
     Scheme sch;
     int rc;
     if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
-    if ((rc = validate_aln(aln))) return rc;
+    if ((aln || !both) && (rc = validate_aln(aln))) return rc;
     const uint64_t n = b->n_pairs;
-    *aln->n_overflow = 0;
-    aln->cigar_off[0] = 0;
+    if (aln) {
+        *aln->n_overflow = 0;
+        aln->cigar_off[0] = 0;
+    }
     if (n == 0) return MSW_OK;
     if (!b->reads || !b->read_len || !b->win_pos || !b->win_len) return fail(MSW_E_INVALID, "NULL array in batch");
-    if (!out || !out->score || !out->end_i || !out->end_j)
-        return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
+    if (both && !strand) return fail(MSW_E_INVALID, "strand is NULL");
+    if (aln) {
+        if (!out || !out->score || !out->end_i || !out->end_j)
+            return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
+    } else if (!out || !out->score || (coords && (!out->end_i || !out->end_j))) {
+        return fail(MSW_E_INVALID, "NULL array in out");
+    }
     if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
     uint32_t max_m = 0, max_n = 0;
     max_u16(b->read_len, n, max_m);
     max_u16(b->win_len, n, max_n);
-    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    if (aln) {
+        if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    } else if ((rc = check_bounds(sch, max_m, max_n))) {
+        return rc;
+    }
     if (max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
     if ((rc = set_device(ctx))) return rc;
     // Simple and synchronous, like msw_align_batch_trace: per chunk upload,
@@ -2333,7 +2485,8 @@ int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genom
     // exact (no alignment has more ops than rows + columns), so no read
     // overflows; the packed ops of a chunk are pulled once its total is known.
     const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
-    const size_t rs = b->read_stride, ws = std::max<size_t>(16, (max_n + 15u) & ~15u), cs = (size_t)max_m + max_n;
+    const size_t rs = b->read_stride, ws = std::max<size_t>(16, (max_n + 15u) & ~15u),
+                 cs = aln ? (size_t)max_m + max_n : 0;
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // [reads | wins | rows u32 | pos i64 | ref i64 | score nc nm i32 | off u32 [c+1] + ovf | 7 x 2 B arrays]
     const size_t o_wins = up256(chunk * rs), o_rows = up256(o_wins + chunk * ws), o_pos = up256(o_rows + chunk * cs * 4);
@@ -2344,11 +2497,23 @@ int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genom
     hipError_t e = hipMalloc((void**)&d, total_bytes);
     if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
     uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
-    uint64_t ops_cap = chunk * 8;
+    uint64_t ops_cap = aln ? chunk * 8 : 1;
     e = hipMalloc((void**)&d_ops, ops_cap * 4);
     if (e != hipSuccess) {
         (void)hipFree(d);
         return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
+    }
+    // both strands: the chunk's oriented rows [chunk][ors] and its strand bytes
+    const size_t ors = std::max<size_t>(16, (max_m + 15u) & ~15u);
+    uint8_t *d_or = nullptr, *d_strand = nullptr;
+    if (both) {
+        e = hipMalloc((void**)&d_or, chunk * ors + chunk + 16);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            (void)hipFree(d_ops);
+            return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", chunk * ors + chunk, hipGetErrorString(e));
+        }
+        d_strand = d_or + chunk * ors;
     }
     uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
     uint16_t *d_want = d_rl + chunk, *d_wl = d_want + chunk;
@@ -2381,12 +2546,34 @@ int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genom
         msw_out_t dout = {reinterpret_cast<int32_t*>(d + o_score), d_ei, d_ej};
         msw_trace_t dtr = {d_si, d_sj, reinterpret_cast<int32_t*>(d + o_nc), reinterpret_cast<uint32_t*>(d + o_rows),
                            (uint32_t)cs};
-        if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) break;
+        if (both) {
+            rc = score_both_strands(ctx, &scc, &db, &dout, d_strand, d_or, (uint32_t)ors, st,
+                                    [&](const msw_batch_t* pb, msw_out_t* po) {
+                                        return msw_align_batch_device(ctx, &scc, pb, po, cm, cn, st);
+                                    });
+            if (rc) break;
+            down(strand + lo, d_strand, c);
+            // from here on the reads are the oriented rows
+            db.reads = d_or;
+            db.read_stride = (uint32_t)ors;
+            if (!aln) {
+                down(out->score + lo, dout.score, c * 4);
+                if (coords) {
+                    down(out->end_i + lo, d_ei, c * 2);
+                    down(out->end_j + lo, d_ej, c * 2);
+                }
+                if (e == hipSuccess) e = hipStreamSynchronize(st);
+                continue;
+            }
+        } else if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) {
+            break;
+        }
         if ((rc = msw_trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st))) break;
         uint64_t total = 0;
         for (int pass = 0; pass < 2; ++pass) {
             msw_aln_t da = {d_ref, reinterpret_cast<int32_t*>(d + o_nm), d_off, d_ops, ops_cap, d_off + c + 1};
-            if ((rc = msw_aln_pack_device(ctx, g, d, d_rl, (uint32_t)rs, d_pos, c, &dout, &dtr, &da, st))) break;
+            if ((rc = msw_aln_pack_device(ctx, g, db.reads, d_rl, db.read_stride, d_pos, c, &dout, &dtr, &da, st)))
+                break;
             down(off.data(), d_off, (c + 1) * 4);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) break;
@@ -2413,9 +2600,20 @@ int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genom
     if (e != hipSuccess) (void)hipStreamSynchronize(st);
     (void)hipFree(d);
     if (d_ops) (void)hipFree(d_ops);
+    if (d_or) (void)hipFree(d_or);
     if (rc) return rc;
     if (e != hipSuccess) return fail(MSW_E_DEVICE, "alignment records: %s", hipGetErrorString(e));
     return MSW_OK;
+}
+
+int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
+                          msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
+    return reads_records(ctx, sc, g, b, out, aln, nullptr, false, chunk_pairs);
+}
+
+int msw_align_reads_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
+                            msw_out_t* out, uint8_t* strand, msw_aln_t* aln, uint64_t chunk_pairs) {
+    return reads_records(ctx, sc, g, b, out, aln, strand, true, chunk_pairs);
 }
 
 int msw_memcpy_d2h_async(msw_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {
@@ -2528,6 +2726,7 @@ int msw_ctx_prepare(msw_ctx* ctx, const msw_scoring_t* sc) {
     p.win_src = nullptr;
     ok &= msw::long_blocks_per_cu(sch.affine, sch.coords, 600, 600) > 0;
     ok &= msw::cut_blocks_per_cu() > 0;
+    ok &= msw::strand_blocks_per_cu() > 0;  // both strands
     msw::TraceParams tp;
     memset(&tp, 0, sizeof(tp));
     tp.max_rows = 150;

@@ -12,6 +12,10 @@ from dataclasses import dataclass
 import numpy as np
 
 ACGT = np.frombuffer(b"ACGT", np.uint8)
+# the complement table of include/msw.h ("Both strands")
+_COMP = np.arange(256, dtype=np.uint8)
+for _a, _b in (b"AT", b"CG", b"at", b"cg"):
+    _COMP[_a], _COMP[_b] = _b, _a
 
 
 @dataclass
@@ -21,6 +25,9 @@ class PairBatch:
     wins: np.ndarray       # uint8 [B, win_stride]
     win_len: np.ndarray    # uint16 [B]
     pos: np.ndarray        # int64 [B] genome offset of the window (-1: unrelated read)
+    # bool [B]: the read row is the reverse complement of the read that was
+    # drawn (write_wgs_dataset with reverse_fraction > 0); None otherwise
+    reverse: np.ndarray | None = None
 
     @property
     def n_pairs(self) -> int:
@@ -32,7 +39,7 @@ class PairBatch:
 
     def slice(self, a: int, b: int) -> "PairBatch":
         return PairBatch(self.reads[a:b], self.read_len[a:b], self.wins[a:b], self.win_len[a:b],
-                         self.pos[a:b])
+                         self.pos[a:b], None if self.reverse is None else self.reverse[a:b])
 
 
 def genome(n_bases: int, rng: np.random.Generator) -> np.ndarray:
@@ -268,8 +275,17 @@ def _lane_records(b, pos, rng, tag: bytes, lane: int, qual: str, first: int = 0)
 def _write_lane_file(job):
     """One lane file of write_wgs_dataset (a process-pool job)."""
     import gzip
-    (g, name, sample, lane, k, reads_per_file, read_len, win_factor, seed, compresslevel, keep, bgzf, qual) = job
+    (g, name, sample, lane, k, reads_per_file, read_len, win_factor, seed, compresslevel, keep, bgzf, qual,
+     reverse_fraction) = job
     b, pos, rng = _lane_reads(g, k, reads_per_file, read_len, win_factor, seed)
+    reverse = None
+    if reverse_fraction > 0.0:
+        # a generator of its own: the draws above and the quality strings'
+        # below are those of the file without reverse reads
+        reverse = np.random.default_rng([seed, k, 0, 1]).random(b.n_pairs) < reverse_fraction
+        for i in np.flatnonzero(reverse):
+            m = int(b.read_len[i])
+            b.reads[i, :m] = _COMP[b.reads[i, :m][::-1]]
     text = _lane_records(b, pos, rng, sample.encode(), lane, qual)
     if bgzf:
         with open(name, "wb") as f:
@@ -279,7 +295,9 @@ def _write_lane_file(job):
             f.write(text)
     if not keep:
         return None
-    return _with_windows(g, b, pos)
+    out = _with_windows(g, b, pos)
+    out.reverse = reverse
+    return out
 
 
 def write_lane_file_segmented(job) -> int:
@@ -304,7 +322,8 @@ def write_lane_file_segmented(job) -> int:
 def write_wgs_dataset(out_dir: str, sample: str = "SYN", lanes: int = 2, reads_per_lane: int = 2,
                       reads_per_file: int = 1000, read_len: int = 150, win_factor: float = 2.0,
                       seed: int = 1004, genome_bases: int = 1 << 20, keep_batches: bool = True,
-                      compresslevel: int = 1, workers: int = 1, bgzf: bool = False, qual: str = "I") -> dict:
+                      compresslevel: int = 1, workers: int = 1, bgzf: bool = False, qual: str = "I",
+                      reverse_fraction: float = 0.0) -> dict:
     """Config-4-shaped dataset: lane files {sample}_L{lane:03}_R{r}_001.fastq.gz
     (aligner.rs:198-204 naming) whose headers carry "pos=<window start>", and
     the reference genome as reference.fa.  Returns paths and (keep_batches) the
@@ -312,7 +331,11 @@ def write_wgs_dataset(out_dir: str, sample: str = "SYN", lanes: int = 2, reads_p
     Vectorised, and ``workers`` > 1 writes the lane files in parallel processes
     (same files either way).  ``bgzf`` writes block-gzip (bgzip) lane files;
     ``qual`` picks the quality strings: "I" (constant), "binned" (NovaSeq
-    4-level) or "illumina" (Q2-Q41 drifting down the read, noisy)."""
+    4-level) or "illumina" (Q2-Q41 drifting down the read, noisy).
+    ``reverse_fraction`` > 0: a seeded share of the reads of each lane file is
+    written reverse-complemented (its window stays where the read was drawn),
+    and each batch's ``reverse`` says which; at 0.0 no draw is made for it and
+    files and batches are what they were without the argument."""
     import os
     os.makedirs(out_dir, exist_ok=True)
     g = wgs_genome(seed, genome_bases)
@@ -326,7 +349,7 @@ def write_wgs_dataset(out_dir: str, sample: str = "SYN", lanes: int = 2, reads_p
         for r in range(1, reads_per_lane + 1):
             name = os.path.join(out_dir, "%s_L%03d_R%d_001.fastq.gz" % (sample, lane, r))
             jobs.append((g, name, sample, lane, k, reads_per_file, read_len, win_factor, seed, compresslevel,
-                         keep_batches, bgzf, qual))
+                         keep_batches, bgzf, qual, float(reverse_fraction)))
             files.append(name)
             k += 1
     if workers > 1 and len(jobs) > 1:
