@@ -389,6 +389,109 @@ int msw_align_reads_strands_device(msw_ctx* ctx, const msw_scoring_t* sc, const 
 int msw_align_reads_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* batch,
                             msw_out_t* out, uint8_t* strand, msw_aln_t* aln, uint64_t chunk_pairs);
 
+/* Placing reads: a k-mer index of the resident genome and seed voting.
+ *
+ * Everything is defined on bytes and integers, so a plain restatement
+ * (tests/seed_oracle.py) can be compared value for value.
+ *
+ * k-mers.  Codes are A 0, C 1, G 2, T 3, upper case only (the scorer compares
+ * bytes).  A k-mer that contains any other byte has no code and is skipped.
+ * The code of s[i .. i+k) is the base-4 number with s[i] most significant.
+ * 4 <= k <= 14.
+ *
+ * Index over a genome g of length n (n <= 0xFFFF0000, else MSW_E_RANGE:
+ * positions are u32 and diagonals are stored biased by 65536).  cnt[c] is the
+ * number of positions p in [0, n-k] whose k-mer has code c.  A bucket with
+ * cnt[c] > max_occ is masked: it is stored as empty (1 <= max_occ <= 64).
+ * off u32[4^k + 1] is the exclusive prefix sum of the masked counts, and
+ * pos u32[off[4^k]] holds each bucket's positions in ascending order, so the
+ * index is bit-reproducible whatever order the build's atomics ran in.
+ *
+ * Seeding one orientation of one read r of length L, with band >= 1, cap in
+ * [1, 8192] and step >= 1:
+ *  1. for each offset i in [0, L-k] with i % step == 0 and a coded k-mer, c_i
+ *     is the size of its bucket; otherwise c_i = 0;
+ *  2. P_i = the sum of c_j over j <= i; offset i contributes its c_i hits iff
+ *     P_i <= cap; the read is truncated iff the last P exceeds cap;
+ *  3. every contributing hit (i, p) gives a diagonal d = p - i, signed (it is
+ *     negative where a read overhangs the genome start);
+ *  4. for each d0 in the multiset D of diagonals, score(d0) is the number of
+ *     d in D with d0 <= d < d0 + band;
+ *  5. the seed is the d0 of maximal score, the smallest such d0 on ties;
+ *     votes is that score and hits is |D|;
+ *  6. no diagonal at all (L < k, no coded k-mer, every bucket empty or
+ *     masked) gives votes = 0.
+ *
+ * Orientation.  With a reverse-complement slab (rows as msw_revcomp_device
+ * writes them) both orientations are seeded, and the reverse one is chosen
+ * iff its votes is strictly greater: a tie goes to forward, as in the strand
+ * rule above.  Without the slab the orientation is forward.
+ *
+ * Placement.  W is the window rule of the device-resident genome calls
+ * (`window`, or 2 x L capped at 4096 when `window` is 0);
+ * pad = max(0, (W - (L + band - 1)) / 2); win_pos = max(0, d0 - pad); and
+ * win_pos = -1 when votes < min_votes (min_votes >= 1): the existing "empty
+ * window, score 0" case, so nothing downstream needs a new rule.
+ *
+ * Composition.  win_pos feeds the reads-against-genome calls unchanged.
+ * msw_align_reads_strands_device scores both orientations against the seeded
+ * window and the right one wins there by score: bit 0 of flags is a hint, not
+ * the record's strand. */
+typedef struct msw_index msw_index;
+typedef struct {
+    uint32_t k;
+    uint32_t max_occ;
+    uint64_t n_buckets;       /* 4^k */
+    uint64_t n_pos;           /* stored positions = off[4^k] */
+    uint64_t n_masked;        /* buckets over max_occ */
+    const uint32_t* off;      /* device, [n_buckets + 1]; read-only, for tests and tools */
+    const uint32_t* pos;      /* device, [n_pos] */
+    double build_ms[5];       /* GPU time of the count, mask, scan, fill and sort passes */
+} msw_index_info_t;
+
+/* Builds the index of `genome` on the GPU, synchronously.  An index belongs
+ * to the context of its genome; it keeps nothing of the genome itself, and is
+ * destroyed before that context. */
+int msw_index_create(msw_ctx* ctx, const msw_genome* genome, uint32_t k, uint32_t max_occ, msw_index** out);
+void msw_index_destroy(msw_index* idx);
+int msw_index_info(const msw_index* idx, msw_index_info_t* out);
+
+typedef struct {
+    uint32_t band;
+    uint32_t cap;
+    uint32_t step;
+    uint32_t min_votes;
+    uint32_t window;          /* the `window` argument the scoring call will get */
+} msw_seed_params_t;
+
+/* Per read: the placement, the chosen orientation's votes and hits, and
+ * flags: bit 0 the reverse orientation was chosen, bit 1 the chosen
+ * orientation was truncated. */
+typedef struct {
+    int64_t*  win_pos;
+    uint32_t* votes;
+    uint32_t* hits;
+    uint8_t*  flags;
+} msw_seed_out_t;
+
+/* Device-resident: every array is device memory; rc_reads (may be NULL:
+ * forward only) holds the reverse complements in rows of rc_stride bytes.
+ * Rows at any alignment and stride >= max_read_len (else MSW_E_INVALID);
+ * max_read_len <= 32767 and window <= 32767, band / cap / step / min_votes as
+ * above, else MSW_E_RANGE.  Enqueued on `stream` (NULL = the context's compute
+ * stream) with no host synchronisation; n = 0 launches nothing. */
+int msw_seed_reads_device(msw_ctx* ctx, const msw_index* idx, const uint8_t* reads, const uint8_t* rc_reads,
+                          const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
+                          uint32_t max_read_len, const msw_seed_params_t* params, const msw_seed_out_t* out,
+                          void* stream);
+
+/* Host memory, synchronous, in chunks of `chunk_reads` (0 = 65536): per chunk
+ * it uploads the rows, makes the reverse complements on the GPU when `both`
+ * is non-zero, seeds and downloads.  batch->win_pos and batch->win_len are
+ * not read. */
+int msw_seed_reads(msw_ctx* ctx, const msw_index* idx, const msw_read_batch_t* batch, int both,
+                   const msw_seed_params_t* params, const msw_seed_out_t* out, uint64_t chunk_reads);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);
@@ -439,7 +542,8 @@ int msw_ctx_stats(msw_ctx* ctx, msw_stats_t* out, int reset);
 
 /* Optional, before a timed region: load the code objects of every scoring
  * kernel module a call under this scheme may use (the packed layouts, the
- * length-bucketed grid, genome windows, long pairs, the window cut).  HIP
+ * length-bucketed grid, genome windows, long pairs, the window cut, both
+ * strands, traceback, the seed kernels).  HIP
  * loads a module on its first launch, ~1-2 ms each, which a short run --
  * one lane file per worker -- would otherwise pay inside its first batch
  * (the reference has no analogue: it JIT-builds its OpenCL program on every

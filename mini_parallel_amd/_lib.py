@@ -33,6 +33,7 @@ EXPORTED = (
     "msw_stream_create", "msw_stream_destroy", "msw_trace_batch_device", "msw_align_batch_trace",
     "msw_trace_reads_device", "msw_aln_pack_device", "msw_align_reads_trace",
     "msw_revcomp_device", "msw_align_reads_strands_device", "msw_align_reads_strands",
+    "msw_index_create", "msw_index_destroy", "msw_index_info", "msw_seed_reads_device", "msw_seed_reads",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -81,6 +82,22 @@ class TraceT(ctypes.Structure):
 class AlnT(ctypes.Structure):
     _fields_ = [("ref_pos", ctypes.c_void_p), ("nm", ctypes.c_void_p), ("cigar_off", ctypes.c_void_p),
                 ("cigar", ctypes.c_void_p), ("cigar_cap", ctypes.c_uint64), ("n_overflow", ctypes.c_void_p)]
+
+
+class IndexInfoT(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint32), ("max_occ", ctypes.c_uint32), ("n_buckets", ctypes.c_uint64),
+                ("n_pos", ctypes.c_uint64), ("n_masked", ctypes.c_uint64), ("off", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("build_ms", ctypes.c_double * 5)]
+
+
+class SeedParamsT(ctypes.Structure):
+    _fields_ = [("band", ctypes.c_uint32), ("cap", ctypes.c_uint32), ("step", ctypes.c_uint32),
+                ("min_votes", ctypes.c_uint32), ("window", ctypes.c_uint32)]
+
+
+class SeedOutT(ctypes.Structure):
+    _fields_ = [("win_pos", ctypes.c_void_p), ("votes", ctypes.c_void_p), ("hits", ctypes.c_void_p),
+                ("flags", ctypes.c_void_p)]
 
 
 class DevReadsT(ctypes.Structure):
@@ -137,6 +154,13 @@ def _declare(L):
                                                ctypes.POINTER(OutT), P, P, P, ctypes.c_uint32, P]),
         "msw_align_reads_strands": (I, [P, ctypes.POINTER(ScoringT), P, ctypes.POINTER(ReadBatchT),
                                         ctypes.POINTER(OutT), P, ctypes.POINTER(AlnT), ctypes.c_uint64]),
+        "msw_index_create": (I, [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(P)]),
+        "msw_index_destroy": (None, [P]),
+        "msw_index_info": (I, [P, ctypes.POINTER(IndexInfoT)]),
+        "msw_seed_reads_device": (I, [P, P, P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                      ctypes.c_uint32, ctypes.POINTER(SeedParamsT), ctypes.POINTER(SeedOutT), P]),
+        "msw_seed_reads": (I, [P, P, ctypes.POINTER(ReadBatchT), I, ctypes.POINTER(SeedParamsT),
+                               ctypes.POINTER(SeedOutT), ctypes.c_uint64]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),
@@ -157,8 +181,8 @@ def _declare(L):
         "msw_host_free": (None, [P]),
         "msw_dev_alloc": (P, [P, ctypes.c_size_t]),
         "msw_dev_free": (None, [P, P]),
-        "msw_memcpy_h2d": (I, [P, P, ctypes.c_size_t]),
-        "msw_memcpy_d2h": (I, [P, P, ctypes.c_size_t]),
+        "msw_memcpy_h2d": (I, [P, P, P, ctypes.c_size_t]),
+        "msw_memcpy_d2h": (I, [P, P, P, ctypes.c_size_t]),
         "msw_memcpy_d2h_async": (I, [P, P, P, ctypes.c_size_t, P]),
         "msw_fence_record": (I, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
         "msw_fence_wait": (I, [P, ctypes.c_uint64]),

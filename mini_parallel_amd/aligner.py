@@ -26,8 +26,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, AlnT, BatchT, DeviceInfoT, MswError, OutT, ReadBatchT, ScoringT, StatsT, TraceT,
-                   check, lib)
+from ._lib import (MSW_E_INVALID, AlnT, BatchT, DeviceInfoT, IndexInfoT, MswError, OutT, ReadBatchT, ScoringT,
+                   SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
 GPU_MAX_WORK_GROUPS = 1_000_000     # gpu.rs:10
@@ -451,6 +451,70 @@ class Context:
         cigars.n_cigar = np.diff(off.astype(np.int64)).astype(np.int32)
         return score, ei, ej, strand, ref_pos, nm, cigars
 
+    # -- placing reads (include/msw.h, "Placing reads") ---------------------------------
+    def build_index(self, genome: "Genome", k: int = 12, max_occ: int = 64) -> "Index":
+        """The k-mer index of a resident genome, built on the GPU
+        (msw_index_create)."""
+        return Index(self, genome, k, max_occ)
+
+    def seed_reads_device(self, index: "Index", reads_ptr: int, read_len_ptr: int, read_stride: int, n: int,
+                          max_read_len: int, win_pos_ptr: int, votes_ptr: int, hits_ptr: int, flags_ptr: int,
+                          rc_reads_ptr: int = 0, rc_stride: int = 0, band: int = 16, cap: int = 4096,
+                          step: int = 1, min_votes: int = 1, window: int = 0, stream: int = 0) -> None:
+        """Enqueue the seeding of n device-resident reads (raw device
+        pointers) on ``stream`` (msw_seed_reads_device): a window position,
+        the votes, the hits and the flags per read.  ``rc_reads_ptr``: the
+        reverse complements' rows (:meth:`revcomp_device`), 0 = forward only."""
+        sp = SeedParamsT(band, cap, step, min_votes, window)
+        out = SeedOutT(win_pos_ptr or None, votes_ptr or None, hits_ptr or None, flags_ptr or None)
+        check(lib().msw_seed_reads_device(self.handle, index.handle, ctypes.c_void_p(reads_ptr or None),
+                                          ctypes.c_void_p(rc_reads_ptr or None), ctypes.c_void_p(read_len_ptr or None),
+                                          read_stride, rc_stride, n, max_read_len, ctypes.byref(sp), ctypes.byref(out),
+                                          ctypes.c_void_p(stream or None)))
+
+    def seed_reads(self, index: "Index", reads: np.ndarray, read_len: np.ndarray, both_strands: bool = True,
+                   band: int = 16, cap: int = 4096, step: int = 1, min_votes: int = 1, window: int = 0,
+                   chunk_reads: int = 0):
+        """Place every read of a host batch on the indexed genome
+        (msw_seed_reads).  Returns (win_pos int64[B], votes uint32[B], hits
+        uint32[B], flags uint8[B]): ``win_pos`` is what the
+        reads-against-genome calls take (-1: fewer than ``min_votes`` votes),
+        bit 0 of ``flags`` says the reverse complement gathered more votes,
+        bit 1 that the read's hits were cut at ``cap``."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        B = reads.shape[0]
+        if read_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        win_pos, votes = np.empty(B, np.int64), np.empty(B, np.uint32)
+        hits, flags = np.empty(B, np.uint32), np.empty(B, np.uint8)
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0, None, None, B)
+        sp = SeedParamsT(band, cap, step, min_votes, window)
+        out = SeedOutT(_fresh_ptr(win_pos), _fresh_ptr(votes), _fresh_ptr(hits), _fresh_ptr(flags))
+        check(lib().msw_seed_reads(self.handle, index.handle, ctypes.byref(batch), 1 if both_strands else 0,
+                                   ctypes.byref(sp), ctypes.byref(out), chunk_reads))
+        return win_pos, votes, hits, flags
+
+    def map_reads(self, genome: "Genome", index: "Index", reads: np.ndarray, read_len: np.ndarray,
+                  scoring: Scoring = LINEAR, both_strands: bool = True, window: int = 0, band: int = 16,
+                  cap: int = 4096, step: int = 1, min_votes: int = 1, chunk_pairs: int = 0):
+        """Seed, then align with records: :meth:`seed_reads` gives every read
+        its window position, and :meth:`align_reads_strands` with ``trace``
+        (``both_strands``) or :meth:`align_reads_trace` scores, traces and
+        packs it against genome[win_pos : win_pos + W], W = ``window`` or
+        twice the read length capped at 4096.  Returns what those return; a
+        read that was not placed has score 0 and ref_pos -1."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        win_pos, _, _, _ = self.seed_reads(index, reads, read_len, both_strands, band=band, cap=cap, step=step,
+                                           min_votes=min_votes, window=window, chunk_reads=chunk_pairs)
+        rl = read_len.astype(np.int64)
+        win_len = (np.full(rl.shape, window, np.int64) if window else np.minimum(2 * rl, 4096)).astype(np.uint16)
+        if both_strands:
+            return self.align_reads_strands(genome, reads, read_len, win_pos, win_len, scoring, trace=True,
+                                            chunk_pairs=chunk_pairs)
+        return self.align_reads_trace(genome, reads, read_len, win_pos, win_len, scoring, chunk_pairs=chunk_pairs)
+
     # -- HBM-resident batches ----------------------------------------------------------
     def align_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int,
                            win_len_ptr: int, read_stride: int, win_stride: int, n_pairs: int,
@@ -661,6 +725,55 @@ class Genome:
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:
             lib().msw_genome_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Index:
+    """The k-mer index of a resident genome (msw_index_*): for every k-mer
+    code the ascending genome positions of its occurrences, buckets over
+    ``max_occ`` stored as empty."""
+
+    def __init__(self, ctx: Context, genome: Genome, k: int = 12, max_occ: int = 64):
+        h = ctypes.c_void_p()
+        check(lib().msw_index_create(ctx.handle, genome.handle, k, max_occ, ctypes.byref(h)))
+        self._h = h
+        self.ctx = ctx  # keeps the context alive for as long as the index
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        if self._h is None:
+            raise MswError(MSW_E_INVALID, "index is closed")
+        return self._h
+
+    def info(self) -> dict:
+        """msw_index_info: k, max_occ, the bucket count, the stored positions,
+        the masked buckets, the device addresses of ``off`` and ``pos`` and
+        the build's GPU time per pass (ms)."""
+        i = IndexInfoT()
+        check(lib().msw_index_info(self.handle, ctypes.byref(i)))
+        return {"k": int(i.k), "max_occ": int(i.max_occ), "n_buckets": int(i.n_buckets), "n_pos": int(i.n_pos),
+                "n_masked": int(i.n_masked), "off_ptr": int(i.off or 0), "pos_ptr": int(i.pos or 0),
+                "build_ms": dict(zip(("count", "mask", "scan", "fill", "sort"), (float(v) for v in i.build_ms)))}
+
+    def arrays(self):
+        """(off uint32[4^k + 1], pos uint32[n_pos]) copied to the host."""
+        i = self.info()
+        off = np.empty(i["n_buckets"] + 1, np.uint32)
+        pos = np.empty(i["n_pos"], np.uint32)
+        check(lib().msw_memcpy_d2h(self.ctx.handle, _fresh_ptr(off), i["off_ptr"], off.nbytes))
+        if pos.size:
+            check(lib().msw_memcpy_d2h(self.ctx.handle, _fresh_ptr(pos), i["pos_ptr"], pos.nbytes))
+        return off, pos
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            lib().msw_index_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -81,6 +81,13 @@ void usage() {
         "                               reverse complement against the window and keep the better (ties: the read\n"
         "                               as given); .aln blocks then carry a strand byte per read, and a strand-1\n"
         "                               record's end_i and CIGAR are in the reverse complement's coordinates\n"
+        "      --map                    --full-wgs sw, BGZF lane files read on the GPU: place each read on the\n"
+        "                               reference with a k-mer index and seed voting instead of a pos= tag in its\n"
+        "                               header (an unplaced read scores 0, ref_pos -1).  With --scores-out it\n"
+        "                               needs --alignments-out too: end cells are relative to the seeded window\n"
+        "      --seed-k N               --map: k-mer length, 4..14 (default 12)\n"
+        "      --seed-max-occ N         --map: k-mers with more occurrences are ignored, 1..64 (default 64)\n"
+        "      --seed-band N            --map: width of the diagonal band that votes together (default 16)\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -120,6 +127,10 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--scores-out") a.scores_out = v();
         else if (s == "--alignments-out") a.alignments_out = v();
         else if (s == "--both-strands") a.both_strands = true;
+        else if (s == "--map") a.map = true;
+        else if (s == "--seed-k") a.seed_k = atoi(v().c_str());
+        else if (s == "--seed-max-occ") a.seed_max_occ = atoi(v().c_str());
+        else if (s == "--seed-band") a.seed_band = atoi(v().c_str());
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -142,6 +153,17 @@ Args parse_args(int argc, char** argv) {
         if (!a.full_wgs || a.score_mode != "sw") die("error: --both-strands needs --full-wgs --score-mode sw");
         if (env_or("MSW_GPU_INFLATE", "1") == "0")
             die("error: --both-strands needs the GPU lane reader (MSW_GPU_INFLATE=0 selects the host reader)");
+    }
+    if (a.map) {
+        // refused here, before any file is opened, like --both-strands
+        if (!a.full_wgs || a.score_mode != "sw") die("error: --map needs --full-wgs --score-mode sw");
+        if (env_or("MSW_GPU_INFLATE", "1") == "0")
+            die("error: --map needs the GPU lane reader (MSW_GPU_INFLATE=0 selects the host reader)");
+        if (!a.scores_out.empty() && a.alignments_out.empty())
+            die("error: --map with --scores-out needs --alignments-out (end cells are relative to the seeded window)");
+        if (a.seed_k < 4 || a.seed_k > 14) die("error: --seed-k must be 4..14");
+        if (a.seed_max_occ < 1 || a.seed_max_occ > 64) die("error: --seed-max-occ must be 1..64");
+        if (a.seed_band < 1) die("error: --seed-band must be at least 1");
     }
     return a;
 }
@@ -254,6 +276,10 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
                       env_or("WGS_FILE_SHARD", "");
     // a run on both strands never resumes a one-strand checkpoint, nor the other way round
     if (a.both_strands) key += "|both-strands";
+    // nor does a mapped run resume one that took its positions from the headers, or other seed parameters
+    if (a.map)
+        key += "|map|" + std::to_string(a.seed_k) + "|" + std::to_string(a.seed_max_occ) + "|" +
+               std::to_string(a.seed_band);
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -402,9 +428,11 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
       << ", \"setup_phases\": {\"hip_init_ms\": " << in.hip_init_ms << ", \"reference_load_ms\": " << rep.reference_load_ms
       << ", \"context_ms\": " << rep.context_ms << ", \"genome_ms\": " << rep.genome_ms
       << ", \"result_sets_ms\": " << rep.result_sets_ms << ", \"lane_reader_ms\": " << rep.lane_reader_ms
-      << ", \"kernel_load_ms\": " << rep.kernel_load_ms << "}"
+      << ", \"kernel_load_ms\": " << rep.kernel_load_ms << ", \"index_ms\": " << rep.index_ms << "}"
       << ", \"teardown_ms\": " << rep.teardown_ms
       << ", \"both_strands\": " << (rep.both_strands ? "true" : "false") << ", \"reverse_reads\": " << rep.reverse_reads
+      << ", \"map\": " << (rep.map ? "true" : "false") << ", \"seed_k\": " << (rep.map ? a.seed_k : 0)
+      << ", \"placed_reads\": " << rep.placed_reads
       << ", \"inflate_bytes_in\": " << rep.gz_in << ", \"inflate_bytes_out\": " << rep.gz_out
       << ", \"reads_per_second\": " << reads / secs << ", \"t_main_unix_ns\": " << in.t_main_ns
       << ", \"t_record_unix_ns\": " << unix_ns() << "}\n";
@@ -441,6 +469,7 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
     }
     printf("Total reads: %llu, total bases: %llu, total score: %lld\n", tot.reads, tot.bases, tot.score);
     if (rep.both_strands) printf("Both strands: %llu reverse reads\n", rep.reverse_reads);
+    if (rep.map) printf("Mapped (k = %d): %llu of %llu reads placed\n", a.seed_k, rep.placed_reads, tot.reads);
     printf("Wall time: %.2f s", rep.wall_ms / 1000.0);
     if (rep.cells) printf(", %.1f GCUPS end-to-end", rep.cells / (rep.wall_ms * 1e6));
     printf("\n");

@@ -72,6 +72,10 @@ struct Args {
     bool has_seq1 = false, has_seq2 = false, files = false, gpu = false, test_wgs = false, full_wgs = false;
     bool cigar = false;
     bool both_strands = false;  // --both-strands: --full-wgs sw scores each read and its reverse complement
+    // --map: --full-wgs sw places each read on the genome itself (k-mer index, seed voting) instead of
+    // taking the window position from a pos= tag of the FASTQ header
+    bool map = false;
+    int seed_k = 12, seed_max_occ = 64, seed_band = 16;
     long chunk_size = 1, num_files = -1;
     std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out, alignments_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;

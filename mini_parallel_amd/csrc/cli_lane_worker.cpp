@@ -190,6 +190,12 @@ struct ResultSet {
     // strand bytes.  They belong to the set, not to the reader, so the trace
     // and a second trace at the exact stride read them while the set is live.
     uint8_t *d_oriented = nullptr, *d_strand = nullptr, *h_strand = nullptr;
+    // --map: the batch's seeded window positions (they take the place of the
+    // reader's pos array in the scoring call, the trace and the pack), votes,
+    // hits and flags; the votes come back to count the placed reads
+    int64_t* d_wpos = nullptr;
+    uint32_t *d_votes = nullptr, *d_hits = nullptr, *h_votes = nullptr;
+    uint8_t* d_flags = nullptr;
     AlnSet aln;
     msw_out_t out() const { return msw_out_t{d_score, d_ei, d_ej}; }
 };
@@ -214,7 +220,7 @@ class LaneWorker {
     WgsRun& run_;
     const Args& a_;
     const int wi_, gi_;
-    const bool aln_, both_;
+    const bool aln_, both_, map_;
     const uint64_t batch_;
     Clock::time_point ts0_;
     Ctx ctx_;
@@ -223,6 +229,8 @@ class LaneWorker {
     size_t pending_ = LaneRun::kNone;  // the file claimed ahead and prefetched
     msw_scoring_t sc_;
     msw_genome* gen_ = nullptr;
+    msw_index* idx_ = nullptr;  // --map
+    msw_seed_params_t seed_{};
     LaneEnv env_;
     ResultSet res_[2];
     uint32_t aln_stride_ = 16;  // ops per read the first trace's rows hold (tests set 1 to force the second trace)
@@ -237,7 +245,7 @@ class LaneWorker {
 // prefetch, genome, kernels, result sets.
 LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     : lanes_(lanes), run_(lanes.run), a_(lanes.run.a), wi_(wi), gi_(wi % lanes.run.ngpu), aln_(lanes.aln),
-      both_(lanes.both), batch_(lanes.batch), ts0_(Clock::now()),
+      both_(lanes.both), map_(lanes.run.a.map), batch_(lanes.batch), ts0_(Clock::now()),
       // lean: a GPU-reader worker scores device-resident batches
       // only, so its context makes just the compute stream
       ctx_(lanes.run.devices[gi_].ordinal, MSW_CTX_LEAN) {
@@ -269,6 +277,14 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     if (msw_genome_create(ctx_.h, (const uint8_t*)ref_seq.data(), ref_seq.size(), &gen_) != MSW_OK)
         die(std::string("GPU genome upload error: ") + msw_last_error());
     const double t_gen = ms_since(tg0);
+    // --map: the k-mer index of the genome just uploaded, before the clock
+    const auto ti0 = Clock::now();
+    if (map_) {
+        if (msw_index_create(ctx_.h, gen_, (uint32_t)a_.seed_k, (uint32_t)a_.seed_max_occ, &idx_) != MSW_OK)
+            die(std::string("GPU k-mer index error: ") + msw_last_error());
+        seed_ = msw_seed_params_t{(uint32_t)a_.seed_band, 4096u, 1u, 1u, window_for(a_, 0)};
+    }
+    const double t_ix = map_ ? ms_since(ti0) : 0.0;
     // the scoring kernels' modules, loaded now rather than at the first batch
     const auto tk0 = Clock::now();
     if (msw_ctx_prepare(ctx_.h, &sc_) != MSW_OK) die(std::string("GPU kernel load: ") + msw_last_error());
@@ -292,6 +308,15 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
             if (!r.d_oriented || !r.d_strand || !r.h_strand)
                 die(std::string("GPU lane reader strand buffers: ") + msw_last_error());
         }
+        if (map_) {
+            r.d_wpos = (int64_t*)msw_dev_alloc(ctx_.h, batch_ * 8);
+            r.d_votes = (uint32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
+            r.d_hits = (uint32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
+            r.d_flags = (uint8_t*)msw_dev_alloc(ctx_.h, batch_);
+            r.h_votes = (uint32_t*)msw_host_alloc(batch_ * 4);
+            if (!r.d_wpos || !r.d_votes || !r.d_hits || !r.d_flags || !r.h_votes)
+                die(std::string("GPU lane reader seed buffers: ") + msw_last_error());
+        }
     }
     // per-read records of a batch, built here and written from here:
     // allocated and touched in setup (a fresh 2 MB buffer per batch
@@ -304,7 +329,7 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     }
     if (aln_)
         for (ResultSet& r : res_) r.aln.alloc(env_, aln_stride_);
-    run_.setup_phase(t_ctx, t_gen, ms_since(tres0), t_rd, t_kl);
+    run_.setup_phase(t_ctx, t_gen, ms_since(tres0), t_rd, t_kl, t_ix);
 }
 
 void LaneWorker::maybe_finish(size_t fi) {
@@ -446,6 +471,11 @@ void LaneWorker::settle(ResultSet& r) {
             for (uint64_t i = 0; i < r.n; ++i) rev += r.h_strand[i];
             run_.reverse_reads += rev;
         }
+        if (map_) {
+            unsigned long long placed = 0;
+            for (uint64_t i = 0; i < r.n; ++i) placed += r.h_votes[i] >= seed_.min_votes;  // win_pos >= 0
+            run_.placed_reads += placed;
+        }
         if (rec && pwrite(f.scores_fd, rec, r.n * 8, (off_t)(r.first * 8)) != (ssize_t)(r.n * 8)) {
             fprintf(stderr, "  error writing scores for %s\n", f.path.c_str());
             f.failed = true;
@@ -472,11 +502,26 @@ bool LaneWorker::submit(ResultSet& r, const msw_dev_reads_t& d, size_t fi, void*
         da.reads = r.d_oriented;
         da.read_stride = read_stride();
     }
-    if ((both_ ? msw_align_reads_strands_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, d.pos, d.n,
+    // --map: seed on this batch's stream, in front of the scoring call; the
+    // seeded positions then stand wherever the reader's stood
+    const int64_t* pos = d.pos;
+    bool seeded = true;
+    if (map_) {
+        const msw_seed_out_t so{r.d_wpos, r.d_votes, r.d_hits, r.d_flags};
+        seeded = (!both_ || msw_revcomp_device(ctx_.h, d.reads, d.read_len, d.read_stride, d.n, r.d_oriented,
+                                               read_stride(), stream) == MSW_OK) &&
+                 msw_seed_reads_device(ctx_.h, idx_, d.reads, both_ ? r.d_oriented : nullptr, d.read_len, d.read_stride,
+                                       both_ ? read_stride() : 0, d.n, d.max_len, &seed_, &so, stream) == MSW_OK &&
+                 msw_memcpy_d2h_async(ctx_.h, r.h_votes, r.d_votes, d.n * 4, stream) == MSW_OK;
+        pos = r.d_wpos;
+        da.pos = r.d_wpos;
+    }
+    if (!seeded ||
+        (both_ ? msw_align_reads_strands_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, pos, d.n,
                                                 window_for(a_, 0), d.max_len, &o, r.d_wlen, r.d_strand, r.d_oriented,
                                                 read_stride(), stream) != MSW_OK ||
                      msw_memcpy_d2h_async(ctx_.h, r.h_strand, r.d_strand, d.n, stream) != MSW_OK
-               : msw_align_reads_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, d.pos, d.n,
+               : msw_align_reads_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, pos, d.n,
                                         window_for(a_, 0), d.max_len, &o, r.d_wlen, stream) != MSW_OK) ||
         msw_memcpy_d2h_async(ctx_.h, r.h.score, r.d_score, d.n * 4, stream) != MSW_OK ||
         // end cells only feed --scores-out records

@@ -154,8 +154,9 @@ WgsRun::WgsRun(const Args& a_, const std::vector<Device>& devices_, const std::v
     t_all = t_setup;
 }
 
-void WgsRun::setup_phase(double c, double g, double r, double rd, double kl) {
+void WgsRun::setup_phase(double c, double g, double r, double rd, double kl, double ix) {
     std::lock_guard<std::mutex> lk(setup_mu);
+    ph_index = std::max(ph_index, ix);
     ph_ctx = std::max(ph_ctx, c);
     ph_gen = std::max(ph_gen, g);
     ph_res = std::max(ph_res, r);
@@ -233,6 +234,9 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
     rep.cells = cells.load();
     rep.both_strands = a.both_strands;
     rep.reverse_reads = reverse_reads.load();
+    rep.map = a.map;
+    rep.placed_reads = placed_reads.load();
+    rep.index_ms = ph_index;
     rep.readers = readers;
     rep.host_threads = host_threads;
     rep.gpu = gpu;
@@ -641,5 +645,8 @@ WgsReport run_full_wgs(const Args& a, const std::vector<Device>& devices, const 
     if (a.both_strands && !run.todo.empty() && !gpu_reader)
         die("error: --both-strands needs BGZF lane files (the GPU lane reader); the host reader scores the reads as "
             "given");
+    if (a.map && !run.todo.empty() && !gpu_reader)
+        die("error: --map needs BGZF lane files (the GPU lane reader); the host reader takes the positions from the "
+            "headers");
     return gpu_reader ? run_gpu_lanes(run, aln, !a.scores_out.empty() || aln) : run_host_readers(run);
 }

@@ -114,6 +114,9 @@ struct WgsReport {
     unsigned long long gz_in = 0, gz_out = 0;  // compressed / inflated bytes (GPU lane reader)
     bool both_strands = false;                 // --both-strands
     unsigned long long reverse_reads = 0;      // reads of this run whose reverse complement won (strand 1)
+    bool map = false;                          // --map
+    unsigned long long placed_reads = 0;       // --map: reads the seeding gave a window (win_pos >= 0)
+    double index_ms = 0;                       // --map: the k-mer index build, a phase of the setup split
 };
 
 // The window of a read of `len` bases: --window, else 2 x read length capped
@@ -152,13 +155,14 @@ struct WgsRun {
     std::mutex ck_mu;
     std::atomic<unsigned long long> cells{0};
     std::atomic<unsigned long long> reverse_reads{0};  // --both-strands: strand-1 reads
+    std::atomic<unsigned long long> placed_reads{0};   // --map: reads with a window
     StartGate gate;
     Clock::time_point t_setup, t_all;
     // the clock stops when the last worker has its last results on the host;
     // teardown (reader / context / genome release) is reported apart, like setup
     std::atomic<long long> t_done_ns{0};
     std::mutex setup_mu;
-    double ph_ctx = 0, ph_gen = 0, ph_res = 0, ph_reader = 0, ph_kl = 0;  // max over workers
+    double ph_ctx = 0, ph_gen = 0, ph_res = 0, ph_reader = 0, ph_kl = 0, ph_index = 0;  // max over workers
     // MSW_CLI_TRACE=1: per worker, ms since the start gate of each batch's
     // arrival from the reader, its submission, and its settle (stderr)
     const bool cli_trace;
@@ -169,7 +173,8 @@ struct WgsRun {
     void finish_file(size_t fi);  // exactly once per file: checkpoint entry and the "File done" line
     void mark_done();
     void trace_ev(int wi, const char* what, uint64_t n) const;
-    void setup_phase(double ctx, double genome, double result_sets, double reader, double kernel_load);
+    void setup_phase(double ctx, double genome, double result_sets, double reader, double kernel_load,
+                     double index = 0.0);
     // opens the gate once n workers have arrived; the clock starts here
     void start_clock(int n);
     WgsReport report(int readers, int host_threads, const std::vector<msw_stats_t>& gpu, bool gpu_inflate,

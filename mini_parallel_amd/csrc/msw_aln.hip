@@ -169,6 +169,8 @@ __global__ __launch_bounds__(256) void aln_gather_kernel(AlnParams p) {
 
 uint64_t tiles(uint64_t count) { return (count + kAlnScanTile - 1) / kAlnScanTile; }
 
+}  // namespace
+
 // exclusive scan of data[0, count) in place; tmp holds the block sums of every level
 hipError_t scan_in_place(uint32_t* data, uint64_t count, uint32_t* tmp, hipStream_t st) {
     const uint64_t blocks = tiles(count);
@@ -185,8 +187,6 @@ hipError_t scan_in_place(uint32_t* data, uint64_t count, uint32_t* tmp, hipStrea
                        (const uint32_t*)tmp);
     return hipGetLastError();
 }
-
-}  // namespace
 
 hipError_t launch_aln_pack(const AlnParams& p, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(p.n_overflow, 0, sizeof(uint32_t), stream);

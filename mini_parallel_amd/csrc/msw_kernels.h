@@ -307,6 +307,46 @@ constexpr uint32_t kAlnScanTile = 1024;
 // Everything enqueued on `stream`; the scan's block sums are allocated and
 // freed stream-ordered.
 hipError_t launch_aln_pack(const AlnParams& p, hipStream_t stream);
+// The scan itself: the exclusive prefix sum of data[0, count) in place,
+// enqueued on `st`; tmp holds the block sums of every level (the sum, over
+// c = ceil(count / kAlnScanTile), ceil(c / kAlnScanTile), ... while c > 1, of c
+// words).  No block waits for another: the levels are separate launches.
+hipError_t scan_in_place(uint32_t* data, uint64_t count, uint32_t* tmp, hipStream_t st);
+
+// Placing reads (msw_seed.hip; the contract is in include/msw.h).
+constexpr uint32_t kSeedMaxCap = 8192;      // keys one read's LDS array holds (32 KiB)
+constexpr uint32_t kSeedMaxOcc = 64;
+constexpr uint64_t kSeedMaxGenome = 0xFFFF0000ull;
+struct SeedParams {
+    const uint32_t* off;      // the index: [4^k + 1]
+    const uint32_t* pos;
+    const uint8_t* reads;
+    const uint8_t* rc_reads;  // the reverse complements' rows, or null: forward only
+    const uint16_t* read_len;
+    uint64_t read_stride;
+    uint64_t rc_stride;
+    uint64_t n;
+    uint32_t k, band, cap, step, min_votes, window;
+    int64_t* win_pos;
+    uint32_t* votes;
+    uint32_t* hits;
+    uint8_t* flags;
+};
+// u32 words of scan temporaries an index of 4^k = `buckets` buckets needs
+uint64_t index_scan_tmp_words(uint64_t buckets);
+// Steps 1-3 of the build: off[buckets + 1] = the masked counts, scanned;
+// *n_masked = the buckets over max_occ.  ev[0..3] are recorded around the
+// count, the mask and the scan.
+hipError_t launch_index_count(const uint8_t* genome, uint64_t glen, uint32_t k, uint32_t max_occ, uint32_t* off,
+                              uint32_t* n_masked, uint32_t* scan_tmp, hipEvent_t* ev, hipStream_t st);
+// Steps 4-5: pos[off[buckets]] filled (cursor: buckets words of scratch) and
+// every bucket sorted ascending.  ev[0..2] around the fill and the sort.
+hipError_t launch_index_fill(const uint8_t* genome, uint64_t glen, uint32_t k, const uint32_t* off, uint32_t* cursor,
+                             uint32_t* pos, hipEvent_t* ev, hipStream_t st);
+size_t seed_lds_bytes(uint32_t cap);
+hipError_t launch_seed_reads(const SeedParams& p, hipStream_t stream);
+// blocks per CU of seed_reads_kernel at this cap; the query loads the module
+int seed_blocks_per_cu(uint32_t cap);
 
 // Both strands (msw_strand.hip; the contract is in include/msw.h).
 // out[p][0, read_len[p]) = the reverse complement of read row p, zeros up to

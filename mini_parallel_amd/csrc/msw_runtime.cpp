@@ -420,6 +420,16 @@ struct msw_genome {
     uint64_t len = 0;
 };
 
+struct msw_index {
+    const msw_ctx* ctx = nullptr;  // identity only
+    int device = 0;
+    uint32_t k = 0, max_occ = 0;
+    uint64_t buckets = 0, n_pos = 0, n_masked = 0;
+    uint32_t* d_off = nullptr;     // [buckets + 1]
+    uint32_t* d_pos = nullptr;     // [max(n_pos, 1)]
+    double build_ms[5] = {0, 0, 0, 0, 0};
+};
+
 // Internal accessors for the other units of the library (msw_gfastq.cpp).
 namespace msw_detail {
 int ctx_device(const msw_ctx* c) { return c->device; }
@@ -2616,6 +2626,203 @@ int msw_align_reads_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_gen
     return reads_records(ctx, sc, g, b, out, aln, strand, true, chunk_pairs);
 }
 
+// Placing reads (include/msw.h, "Placing reads"; the kernels: msw_seed.hip).
+int msw_index_create(msw_ctx* ctx, const msw_genome* g, uint32_t k, uint32_t max_occ, msw_index** out) {
+    if (!ctx || !out) return fail(MSW_E_INVALID, "ctx/out is NULL");
+    *out = nullptr;
+    if (!g) return fail(MSW_E_INVALID, "genome is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    if (k < 4 || k > 14) return fail(MSW_E_RANGE, "index: k %u outside [4, 14]", k);
+    if (max_occ < 1 || max_occ > msw::kSeedMaxOcc)
+        return fail(MSW_E_RANGE, "index: max_occ %u outside [1, %u]", max_occ, msw::kSeedMaxOcc);
+    if (g->len > msw::kSeedMaxGenome)
+        return fail(MSW_E_RANGE, "index: genome of %llu bases > %llu", (unsigned long long)g->len,
+                    (unsigned long long)msw::kSeedMaxGenome);
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    msw_index* x = new msw_index();
+    x->ctx = ctx;
+    x->device = ctx->device;
+    x->k = k;
+    x->max_occ = max_occ;
+    x->buckets = 1ull << (2 * k);
+    // plain hipMalloc for the temporaries: a one-off, synchronous build
+    uint32_t *tmp = nullptr, *cursor = nullptr, *d_masked = nullptr;
+    hipEvent_t ev[7] = {};
+    hipStream_t st = ctx->compute;
+    const uint64_t tmp_words = msw::index_scan_tmp_words(x->buckets);
+    uint32_t h_masked = 0, total = 0;
+    int err = MSW_OK;
+    hipError_t e = hipMalloc((void**)&x->d_off, (x->buckets + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&tmp, (tmp_words + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_masked, sizeof(uint32_t));
+    if (e != hipSuccess) err = fail(MSW_E_NOMEM, "index: hipMalloc for 4^%u buckets: %s", k, hipGetErrorString(e));
+    for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    if (e == hipSuccess)
+        e = msw::launch_index_count(g->d_seq, g->len, k, max_occ, x->d_off, d_masked, tmp, ev, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, x->d_off + x->buckets, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_masked, d_masked, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) {
+        x->n_pos = total;
+        x->n_masked = h_masked;
+        e = hipMalloc((void**)&x->d_pos, std::max<uint64_t>(total, 1) * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&cursor, x->buckets * sizeof(uint32_t));
+        if (e != hipSuccess)
+            err = fail(MSW_E_NOMEM, "index: hipMalloc for %u positions: %s", total, hipGetErrorString(e));
+    }
+    if (e == hipSuccess) e = msw::launch_index_fill(g->d_seq, g->len, k, x->d_off, cursor, x->d_pos, ev + 4, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) {
+        // ev: [count | mask | scan |] then [fill | sort |]
+        const int a[5] = {0, 1, 2, 4, 5};
+        for (int i = 0; i < 5; ++i) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[a[i]], ev[a[i] + 1]) == hipSuccess) x->build_ms[i] = ms;
+        }
+    } else {
+        (void)hipStreamSynchronize(st);
+    }
+    for (hipEvent_t v : ev)
+        if (v) (void)hipEventDestroy(v);
+    (void)hipFree(tmp);
+    (void)hipFree(cursor);
+    (void)hipFree(d_masked);
+    if (e != hipSuccess) {
+        msw_index_destroy(x);
+        return err ? err : fail(MSW_E_DEVICE, "index build: %s", hipGetErrorString(e));
+    }
+    *out = x;
+    return MSW_OK;
+}
+
+void msw_index_destroy(msw_index* x) {
+    if (!x) return;
+    (void)hipSetDevice(x->device);
+    if (x->d_off) (void)hipFree(x->d_off);
+    if (x->d_pos) (void)hipFree(x->d_pos);
+    delete x;
+}
+
+int msw_index_info(const msw_index* x, msw_index_info_t* out) {
+    if (!x || !out) return fail(MSW_E_INVALID, "index/out is NULL");
+    out->k = x->k;
+    out->max_occ = x->max_occ;
+    out->n_buckets = x->buckets;
+    out->n_pos = x->n_pos;
+    out->n_masked = x->n_masked;
+    out->off = x->d_off;
+    out->pos = x->d_pos;
+    for (int i = 0; i < 5; ++i) out->build_ms[i] = x->build_ms[i];
+    return MSW_OK;
+}
+
+static int check_seed_params(const msw_seed_params_t* sp, uint32_t max_read_len) {
+    if (!sp) return fail(MSW_E_INVALID, "seed params is NULL");
+    if (sp->band < 1) return fail(MSW_E_RANGE, "seed: band must be >= 1");
+    if (sp->cap < 1 || sp->cap > msw::kSeedMaxCap)
+        return fail(MSW_E_RANGE, "seed: cap %u outside [1, %u]", sp->cap, msw::kSeedMaxCap);
+    if (sp->step < 1) return fail(MSW_E_RANGE, "seed: step must be >= 1");
+    if (sp->min_votes < 1) return fail(MSW_E_RANGE, "seed: min_votes must be >= 1");
+    if (sp->window > (uint32_t)msw::kMaxLongLen)
+        return fail(MSW_E_RANGE, "seed: window %u > %d", sp->window, msw::kMaxLongLen);
+    if (max_read_len > (uint32_t)msw::kMaxLongLen)
+        return fail(MSW_E_RANGE, "seed: max_read_len %u > %d", max_read_len, msw::kMaxLongLen);
+    return MSW_OK;
+}
+
+int msw_seed_reads_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
+                          const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
+                          uint32_t max_read_len, const msw_seed_params_t* sp, const msw_seed_out_t* out, void* stream) {
+    if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
+    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
+    int rc;
+    if ((rc = check_seed_params(sp, max_read_len))) return rc;
+    if (n == 0) return MSW_OK;
+    if (!reads || !read_len || !out || !out->win_pos || !out->votes || !out->hits || !out->flags)
+        return fail(MSW_E_INVALID, "NULL array");
+    if (read_stride == 0 || max_read_len > read_stride) return fail(MSW_E_INVALID, "max_read_len exceeds read_stride");
+    if (rc_reads && (rc_stride == 0 || max_read_len > rc_stride))
+        return fail(MSW_E_INVALID, "max_read_len exceeds rc_stride");
+    if ((rc = set_device(ctx))) return rc;
+    msw::SeedParams p;
+    p.off = x->d_off;
+    p.pos = x->d_pos;
+    p.reads = reads;
+    p.rc_reads = rc_reads;
+    p.read_len = read_len;
+    p.read_stride = read_stride;
+    p.rc_stride = rc_stride;
+    p.n = n;
+    p.k = x->k;
+    p.band = sp->band;
+    p.cap = sp->cap;
+    p.step = sp->step;
+    p.min_votes = sp->min_votes;
+    p.window = sp->window;
+    p.win_pos = out->win_pos;
+    p.votes = out->votes;
+    p.hits = out->hits;
+    p.flags = out->flags;
+    HIP_TRY(msw::launch_seed_reads(p, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_seed_reads(msw_ctx* ctx, const msw_index* x, const msw_read_batch_t* b, int both,
+                   const msw_seed_params_t* sp, const msw_seed_out_t* out, uint64_t chunk_reads) {
+    if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
+    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
+    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
+    const uint64_t n = b->n_pairs;
+    uint32_t max_m = 0;
+    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array");
+    max_u16(b->read_len, n, max_m);
+    int rc;
+    if ((rc = check_seed_params(sp, max_m))) return rc;
+    if (n == 0) return MSW_OK;
+    if (!b->reads || !out || !out->win_pos || !out->votes || !out->hits || !out->flags)
+        return fail(MSW_E_INVALID, "NULL array");
+    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    // Simple and synchronous, like msw_align_batch_trace: per chunk upload,
+    // reverse complement, seed, download.
+    const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
+    const size_t rs = b->read_stride, os = round16((uint32_t)std::max<uint32_t>(max_m, 1));
+    // [reads | rc rows | win_pos i64 | votes u32 | hits u32 | read_len u16 | flags u8]
+    const size_t o_rc = (chunk * rs + 255) & ~(size_t)255, o_wp = (o_rc + (both ? chunk * os : 0) + 255) & ~(size_t)255;
+    const size_t o_votes = o_wp + chunk * 8, o_hits = o_votes + chunk * 4, o_rl = o_hits + chunk * 4,
+                 o_fl = o_rl + chunk * 2;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, o_fl + chunk + 256);
+    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", o_fl + chunk, hipGetErrorString(e));
+    hipStream_t st = ctx->compute;
+    rc = MSW_OK;
+    for (uint64_t lo = 0; lo < n && rc == MSW_OK; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_rl);
+        msw_seed_out_t dout = {reinterpret_cast<int64_t*>(d + o_wp), reinterpret_cast<uint32_t*>(d + o_votes),
+                               reinterpret_cast<uint32_t*>(d + o_hits), d + o_fl};
+        e = hipMemcpyAsync(d, b->reads + lo * rs, c * rs, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rl, b->read_len + lo, c * 2, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) break;
+        if (both && (rc = msw_revcomp_device(ctx, d, d_rl, (uint32_t)rs, c, d + o_rc, (uint32_t)os, st))) break;
+        if ((rc = msw_seed_reads_device(ctx, x, d, both ? d + o_rc : nullptr, d_rl, (uint32_t)rs, (uint32_t)os, c, max_m,
+                                        sp, &dout, st)))
+            break;
+        e = hipMemcpyAsync(out->win_pos + lo, dout.win_pos, c * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out->votes + lo, dout.votes, c * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out->hits + lo, dout.hits, c * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out->flags + lo, dout.flags, c, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+    }
+    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "seeding: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
 int msw_memcpy_d2h_async(msw_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     int rc = set_device(ctx);
@@ -2727,6 +2934,7 @@ int msw_ctx_prepare(msw_ctx* ctx, const msw_scoring_t* sc) {
     ok &= msw::long_blocks_per_cu(sch.affine, sch.coords, 600, 600) > 0;
     ok &= msw::cut_blocks_per_cu() > 0;
     ok &= msw::strand_blocks_per_cu() > 0;  // both strands
+    ok &= msw::seed_blocks_per_cu(4096) > 0;  // placing reads
     msw::TraceParams tp;
     memset(&tp, 0, sizeof(tp));
     tp.max_rows = 150;
