@@ -492,6 +492,111 @@ int msw_seed_reads_device(msw_ctx* ctx, const msw_index* idx, const uint8_t* rea
 int msw_seed_reads(msw_ctx* ctx, const msw_index* idx, const msw_read_batch_t* batch, int both,
                    const msw_seed_params_t* params, const msw_seed_out_t* out, uint64_t chunk_reads);
 
+/* Candidates and mapping quality.
+ *
+ * Defined on integers, like "Placing reads" (tests/mapq_oracle.py restates
+ * it).  A read gets up to two candidate loci; both are scored, the better one
+ * becomes the read's record, and the other one's score is the sub-optimal
+ * score that the mapping quality is made of.
+ *
+ * Per orientation.  D is the multiset of contributing diagonals and (d1, v1)
+ * the seed of "Placing reads".  With sep >= band, a diagonal e is admissible
+ * against d iff |e - d| >= sep.  The orientation's second band (d2, v2) is the
+ * seed rule (steps 4-6) applied to the subset of D admissible against d1; no
+ * admissible diagonal gives v2 = 0.
+ *
+ * Per read.  Candidate 0 is exactly what msw_seed_reads_device reports: the
+ * same orientation rule, win_pos, votes, hits and flags, bit for bit; d0 is
+ * its diagonal.  Candidate 1 is chosen among the other bands, up to three: the
+ * chosen orientation's second band, and the other orientation's first and
+ * second bands.  A band is eligible iff its votes >= min_votes and its
+ * diagonal is admissible against d0.  The most votes win; on a tie the forward
+ * orientation goes before the reverse one, then the smaller diagonal.  No
+ * eligible band (candidate 0 without a diagonal included) gives win_pos1 = -1,
+ * votes1 = 0, flags1 = 0.  win_pos1 follows the placement formula of "Placing
+ * reads".  sep = 0 means max(W, band), W the window rule's length for that
+ * read; a sep that is neither 0 nor >= band is MSW_E_RANGE.
+ *
+ * This is NOT the globally second-best band over both orientations: a band
+ * that is third in its own orientation is never seen, and the other
+ * orientation's second band is the one admissible against that orientation's
+ * own first band, which is then tested against d0.  The rule is what one pass
+ * over each orientation's sorted diagonals can give without a second key array
+ * or a re-expansion of the first orientation.
+ *
+ * Selection.  s_p and s_a are the scores of candidates 0 and 1 (the both-strand
+ * score where both strands are scored; an empty window scores 0).  The
+ * alternate wins iff s_a > s_p; ties keep candidate 0.  The winner's score,
+ * end cell, win_len, strand, oriented row and win_pos become the read's;
+ * sub_score is the loser's score and cand is 0 or 1.
+ *
+ * Mapping quality, with s1 the winner's score and L the read length:
+ * mapq = 0 when s1 <= 0 or match * L == 0; otherwise
+ * mapq = min(60, 120 * (s1 - s2) / (match * L)), floor division in 64-bit
+ * integers, s2 = clamp(sub_score, 0, s1).  This is an uncalibrated heuristic:
+ * a monotone function of the score gap per best-possible score, not a
+ * probability, and not comparable with another mapper's MAPQ. */
+typedef struct {
+    int64_t*  win_pos;        /* [n] candidate 1's window position, -1: none */
+    uint32_t* votes;          /* [n] its votes, 0: none */
+    uint8_t*  flags;          /* [n] bit 0: it comes from the reverse orientation */
+} msw_seed_alt_t;
+
+/* msw_seed_reads_device with the second candidate: the same arguments, checks
+ * and errors; `out` is written as that call writes it.  Enqueued on `stream`,
+ * no host synchronisation. */
+int msw_seed_candidates_device(msw_ctx* ctx, const msw_index* idx, const uint8_t* reads, const uint8_t* rc_reads,
+                               const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
+                               uint32_t max_read_len, const msw_seed_params_t* params, uint32_t sep,
+                               const msw_seed_out_t* out, const msw_seed_alt_t* alt, void* stream);
+
+/* Host memory, synchronous, chunked like msw_seed_reads. */
+int msw_seed_candidates(msw_ctx* ctx, const msw_index* idx, const msw_read_batch_t* batch, int both,
+                        const msw_seed_params_t* params, uint32_t sep, const msw_seed_out_t* out,
+                        const msw_seed_alt_t* alt, uint64_t chunk_reads);
+
+/* One candidate's scoring results, device arrays of n.  end_i / end_j NULL
+ * (in both candidates): scores only.  strand / oriented NULL (in both): one
+ * strand, no rows.  win_len NULL (in both): not moved. */
+typedef struct {
+    int32_t*  score;
+    int16_t*  end_i;
+    int16_t*  end_j;
+    uint16_t* win_len;
+    uint8_t*  strand;
+    uint8_t*  oriented;       /* [n][oriented_stride], as msw_align_reads_strands_device writes it */
+    int64_t*  win_pos;
+} msw_cand_t;
+
+/* The selection above, in place: where the alternate wins its results and its
+ * oriented row (zero padding included) replace the primary's; elsewhere the
+ * primary's arrays are not written and the alternate's row is not read.
+ * sub_score i32[n], mapq u8[n], cand u8[n] are written for every read.  With
+ * rows: both slabs 16-byte aligned and oriented_stride a non-zero multiple of
+ * 16, else MSW_E_INVALID; match outside [0, 64] is MSW_E_RANGE.  Enqueued on
+ * `stream`, no host synchronisation. */
+int msw_mapq_select_device(msw_ctx* ctx, const msw_cand_t* primary, const msw_cand_t* alt, uint32_t oriented_stride,
+                           const uint16_t* read_len, uint64_t n, int32_t match, int32_t* sub_score, uint8_t* mapq,
+                           uint8_t* cand, void* stream);
+
+typedef struct {
+    uint8_t* mapq;            /* [n] */
+    int32_t* sub_score;       /* [n] */
+    uint8_t* cand;            /* [n] 0: candidate 0 is the record's locus, 1: candidate 1 */
+} msw_mapq_t;
+
+/* Host memory, synchronous, in chunks of `chunk_pairs` (0 = 65536): per chunk
+ * the candidates, the scoring of both (msw_align_reads_strands_device twice
+ * when `both` is non-zero, else msw_align_reads_device twice), the selection,
+ * then the trace and the pack of the winner's rows at the winner's positions.
+ * batch->win_pos and batch->win_len are not read: the window is
+ * params->window.  out, strand (required when `both`, else may be NULL) and
+ * aln (required) are filled as by msw_align_reads_strands; ranges and
+ * MSW_E_RANGE as for msw_align_reads_trace. */
+int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_index* idx,
+                  const msw_read_batch_t* batch, int both, const msw_seed_params_t* params, uint32_t sep,
+                  msw_out_t* out, uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint64_t chunk_pairs);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

@@ -34,6 +34,7 @@ EXPORTED = (
     "msw_trace_reads_device", "msw_aln_pack_device", "msw_align_reads_trace",
     "msw_revcomp_device", "msw_align_reads_strands_device", "msw_align_reads_strands",
     "msw_index_create", "msw_index_destroy", "msw_index_info", "msw_seed_reads_device", "msw_seed_reads",
+    "msw_seed_candidates_device", "msw_seed_candidates", "msw_mapq_select_device", "msw_map_reads",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -100,6 +101,20 @@ class SeedOutT(ctypes.Structure):
                 ("flags", ctypes.c_void_p)]
 
 
+class SeedAltT(ctypes.Structure):
+    _fields_ = [("win_pos", ctypes.c_void_p), ("votes", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
+
+
+class CandT(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_void_p), ("end_i", ctypes.c_void_p), ("end_j", ctypes.c_void_p),
+                ("win_len", ctypes.c_void_p), ("strand", ctypes.c_void_p), ("oriented", ctypes.c_void_p),
+                ("win_pos", ctypes.c_void_p)]
+
+
+class MapqT(ctypes.Structure):
+    _fields_ = [("mapq", ctypes.c_void_p), ("sub_score", ctypes.c_void_p), ("cand", ctypes.c_void_p)]
+
+
 class DevReadsT(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_void_p), ("read_len", ctypes.c_void_p), ("pos", ctypes.c_void_p),
                 ("read_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("first_read", ctypes.c_uint64),
@@ -161,6 +176,16 @@ def _declare(L):
                                       ctypes.c_uint32, ctypes.POINTER(SeedParamsT), ctypes.POINTER(SeedOutT), P]),
         "msw_seed_reads": (I, [P, P, ctypes.POINTER(ReadBatchT), I, ctypes.POINTER(SeedParamsT),
                                ctypes.POINTER(SeedOutT), ctypes.c_uint64]),
+        "msw_seed_candidates_device": (I, [P, P, P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                           ctypes.c_uint32, ctypes.POINTER(SeedParamsT), ctypes.c_uint32,
+                                           ctypes.POINTER(SeedOutT), ctypes.POINTER(SeedAltT), P]),
+        "msw_seed_candidates": (I, [P, P, ctypes.POINTER(ReadBatchT), I, ctypes.POINTER(SeedParamsT), ctypes.c_uint32,
+                                    ctypes.POINTER(SeedOutT), ctypes.POINTER(SeedAltT), ctypes.c_uint64]),
+        "msw_mapq_select_device": (I, [P, ctypes.POINTER(CandT), ctypes.POINTER(CandT), ctypes.c_uint32, P,
+                                       ctypes.c_uint64, ctypes.c_int32, P, P, P, P]),
+        "msw_map_reads": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.POINTER(ReadBatchT), I,
+                              ctypes.POINTER(SeedParamsT), ctypes.c_uint32, ctypes.POINTER(OutT), P,
+                              ctypes.POINTER(AlnT), ctypes.POINTER(MapqT), ctypes.c_uint64]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

@@ -26,8 +26,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, AlnT, BatchT, DeviceInfoT, IndexInfoT, MswError, OutT, ReadBatchT, ScoringT,
-                   SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
+from ._lib import (MSW_E_INVALID, AlnT, BatchT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, ReadBatchT,
+                   ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
 GPU_MAX_WORK_GROUPS = 1_000_000     # gpu.rs:10
@@ -497,15 +497,26 @@ class Context:
 
     def map_reads(self, genome: "Genome", index: "Index", reads: np.ndarray, read_len: np.ndarray,
                   scoring: Scoring = LINEAR, both_strands: bool = True, window: int = 0, band: int = 16,
-                  cap: int = 4096, step: int = 1, min_votes: int = 1, chunk_pairs: int = 0):
+                  cap: int = 4096, step: int = 1, min_votes: int = 1, chunk_pairs: int = 0, mapq: bool = False,
+                  sep: int = 0):
         """Seed, then align with records: :meth:`seed_reads` gives every read
         its window position, and :meth:`align_reads_strands` with ``trace``
         (``both_strands``) or :meth:`align_reads_trace` scores, traces and
         packs it against genome[win_pos : win_pos + W], W = ``window`` or
         twice the read length capped at 4096.  Returns what those return; a
-        read that was not placed has score 0 and ref_pos -1."""
+        read that was not placed has score 0 and ref_pos -1.
+
+        ``mapq`` (msw_map_reads): a second candidate locus at least ``sep``
+        diagonals away (0 = the window length) is scored too, the better of
+        the two becomes the record, and the tuple ends with three more
+        arrays: mapq uint8[B] (0..60, an uncalibrated heuristic), sub_score
+        int32[B] (the other candidate's score) and cand uint8[B] (1 where the
+        second candidate won)."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        if mapq:
+            return self._map_reads_mapq(genome, index, reads, read_len, scoring, both_strands, window, band, cap,
+                                        step, min_votes, chunk_pairs, sep)
         win_pos, _, _, _ = self.seed_reads(index, reads, read_len, both_strands, band=band, cap=cap, step=step,
                                            min_votes=min_votes, window=window, chunk_reads=chunk_pairs)
         rl = read_len.astype(np.int64)
@@ -514,6 +525,100 @@ class Context:
             return self.align_reads_strands(genome, reads, read_len, win_pos, win_len, scoring, trace=True,
                                             chunk_pairs=chunk_pairs)
         return self.align_reads_trace(genome, reads, read_len, win_pos, win_len, scoring, chunk_pairs=chunk_pairs)
+
+    # -- candidates and mapping quality (include/msw.h) ---------------------------------
+    def _map_reads_mapq(self, genome, index, reads, read_len, scoring, both, window, band, cap, step, min_votes,
+                        chunk_pairs, sep):
+        B = reads.shape[0]
+        if read_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0, None, None, B)
+        sc = _scoring_c(scoring)
+        sp = SeedParamsT(band, cap, step, min_votes, window)
+        strand = np.zeros(B, np.uint8)
+        mq, sub, cand = np.zeros(B, np.uint8), np.zeros(B, np.int32), np.zeros(B, np.uint8)
+        ccap = 4 * B
+        while B:
+            (score, ei, ej), out = _outputs(B, True)
+            ref_pos, nm = np.empty(B, np.int64), np.empty(B, np.int32)
+            off = np.zeros(B + 1, np.uint32)
+            cig = np.zeros(max(ccap, 1), np.uint32)
+            ovf = np.zeros(1, np.uint32)
+            aln = AlnT(_fresh_ptr(ref_pos), _fresh_ptr(nm), _fresh_ptr(off), _fresh_ptr(cig), ccap, _fresh_ptr(ovf))
+            mt = MapqT(_fresh_ptr(mq), _fresh_ptr(sub), _fresh_ptr(cand))
+            check(lib().msw_map_reads(self.handle, ctypes.byref(sc), genome.handle, index.handle, ctypes.byref(batch),
+                                      1 if both else 0, ctypes.byref(sp), sep, ctypes.byref(out),
+                                      ctypes.c_void_p(_fresh_ptr(strand) or None), ctypes.byref(aln),
+                                      ctypes.byref(mt), chunk_pairs))
+            total = int(off[B])
+            if total > ccap:
+                ccap = total  # once: the offsets do not depend on the capacity
+                continue
+            break
+        if B == 0:  # nothing to call with: every array is empty
+            (score, ei, ej), _ = _outputs(0, True)
+            ref_pos, nm, off, cig = np.empty(0, np.int64), np.empty(0, np.int32), np.zeros(1, np.uint32), None
+        cigars = CigarList(cig[off[p]:off[p + 1]].copy() for p in range(B))
+        cigars.n_cigar = np.diff(off.astype(np.int64)).astype(np.int32)
+        if both:
+            return score, ei, ej, strand, ref_pos, nm, cigars, mq, sub, cand
+        return score, ei, ej, ref_pos, nm, cigars, mq, sub, cand
+
+    def seed_candidates_device(self, index: "Index", reads_ptr: int, read_len_ptr: int, read_stride: int, n: int,
+                               max_read_len: int, win_pos_ptr: int, votes_ptr: int, hits_ptr: int, flags_ptr: int,
+                               win_pos1_ptr: int, votes1_ptr: int, flags1_ptr: int, rc_reads_ptr: int = 0,
+                               rc_stride: int = 0, band: int = 16, cap: int = 4096, step: int = 1,
+                               min_votes: int = 1, window: int = 0, sep: int = 0, stream: int = 0) -> None:
+        """:meth:`seed_reads_device` with the second candidate locus
+        (msw_seed_candidates_device): the first four arrays as that call
+        writes them, then candidate 1's window position (-1: none), votes and
+        flags (bit 0: from the reverse orientation)."""
+        sp = SeedParamsT(band, cap, step, min_votes, window)
+        out = SeedOutT(win_pos_ptr or None, votes_ptr or None, hits_ptr or None, flags_ptr or None)
+        alt = SeedAltT(win_pos1_ptr or None, votes1_ptr or None, flags1_ptr or None)
+        check(lib().msw_seed_candidates_device(
+            self.handle, index.handle, ctypes.c_void_p(reads_ptr or None), ctypes.c_void_p(rc_reads_ptr or None),
+            ctypes.c_void_p(read_len_ptr or None), read_stride, rc_stride, n, max_read_len, ctypes.byref(sp), sep,
+            ctypes.byref(out), ctypes.byref(alt), ctypes.c_void_p(stream or None)))
+
+    def seed_candidates(self, index: "Index", reads: np.ndarray, read_len: np.ndarray, both_strands: bool = True,
+                        band: int = 16, cap: int = 4096, step: int = 1, min_votes: int = 1, window: int = 0,
+                        sep: int = 0, chunk_reads: int = 0):
+        """Two candidate loci per read of a host batch (msw_seed_candidates).
+        Returns ((win_pos, votes, hits, flags), (win_pos1, votes1, flags1)):
+        the first tuple is :meth:`seed_reads`' result, the second the best
+        other band at least ``sep`` diagonals away (0 = the window length),
+        win_pos1 -1 and votes1 0 where there is none."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        B = reads.shape[0]
+        if read_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        win_pos, votes = np.empty(B, np.int64), np.empty(B, np.uint32)
+        hits, flags = np.empty(B, np.uint32), np.empty(B, np.uint8)
+        win_pos1, votes1, flags1 = np.empty(B, np.int64), np.empty(B, np.uint32), np.empty(B, np.uint8)
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0, None, None, B)
+        sp = SeedParamsT(band, cap, step, min_votes, window)
+        out = SeedOutT(_fresh_ptr(win_pos), _fresh_ptr(votes), _fresh_ptr(hits), _fresh_ptr(flags))
+        alt = SeedAltT(_fresh_ptr(win_pos1), _fresh_ptr(votes1), _fresh_ptr(flags1))
+        check(lib().msw_seed_candidates(self.handle, index.handle, ctypes.byref(batch), 1 if both_strands else 0,
+                                        ctypes.byref(sp), sep, ctypes.byref(out), ctypes.byref(alt), chunk_reads))
+        return (win_pos, votes, hits, flags), (win_pos1, votes1, flags1)
+
+    def mapq_select_device(self, primary: dict, alt: dict, read_len_ptr: int, n: int, match: int,
+                           sub_score_ptr: int, mapq_ptr: int, cand_ptr: int, oriented_stride: int = 0,
+                           stream: int = 0) -> None:
+        """Enqueue the choice between two scored candidates per read
+        (msw_mapq_select_device).  ``primary`` / ``alt``: raw device pointers
+        under the keys score, end_i, end_j, win_len, strand, oriented, win_pos
+        (absent or 0 = NULL); the winner lands in the primary's arrays."""
+        keys = ("score", "end_i", "end_j", "win_len", "strand", "oriented", "win_pos")
+        c0 = CandT(*[primary.get(k) or None for k in keys])
+        c1 = CandT(*[alt.get(k) or None for k in keys])
+        check(lib().msw_mapq_select_device(self.handle, ctypes.byref(c0), ctypes.byref(c1), oriented_stride,
+                                           ctypes.c_void_p(read_len_ptr or None), n, match,
+                                           ctypes.c_void_p(sub_score_ptr or None), ctypes.c_void_p(mapq_ptr or None),
+                                           ctypes.c_void_p(cand_ptr or None), ctypes.c_void_p(stream or None)))
 
     # -- HBM-resident batches ----------------------------------------------------------
     def align_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int,

@@ -8,12 +8,20 @@ batches of a lane file settled:
   n_reads x 24 B i64 ref_pos, i32 score, i32 nm, u32 n_ops, i16 end_i, i16 end_j
   n_ops x u32    packed ops in read order (len << 4 | op, M=0 I=1 D=2 S=4)
   flags bit 0:   n_reads x u8 strand (0 / 1), zero-padded to a multiple of 4 B
+  flags bit 1:   n_reads x u8 mapq (0 .. 60), zero-padded to a multiple of 4 B,
+                 then n_reads x i32 sub_score (after the strand bytes, if any)
 
 Flag bit 0 (``--both-strands``): the block carries one strand byte per read; a
 strand-1 record's end_i and CIGAR are in the coordinates of the read's reverse
 complement (include/msw.h, "Both strands").  A block without the flag is byte
 for byte what it was before the flag existed (the field was 8 zero bytes), and
-a file may hold both kinds.  Every other flag bit is refused.
+a file may hold both kinds.
+
+Flag bit 1 (``--mapq``): the block carries a mapping quality and the score of
+the read's other candidate locus per read (include/msw.h, "Candidates and
+mapping quality").  Reads from blocks without it have mapq 255 (SAM's
+"unavailable") and sub_score 0.  A block without bit 1 is byte for byte what
+it was before the bit existed.  Every other flag bit is refused.
 """
 from __future__ import annotations
 
@@ -26,6 +34,9 @@ from .aligner import CigarList
 MAGIC = b"MSWA"
 VERSION = 1
 FLAG_STRAND = 1
+FLAG_MAPQ = 2
+MAPQ_MAX = 60
+MAPQ_UNAVAILABLE = 255
 HEADER = np.dtype([("magic", "S4"), ("version", "<u4"), ("first_read", "<u8"), ("n_reads", "<u4"),
                    ("n_ops", "<u4"), ("flags", "<u4"), ("zero", "<u4")])
 RECORD = np.dtype([("ref_pos", "<i8"), ("score", "<i4"), ("nm", "<i4"), ("n_ops", "<u4"), ("end_i", "<i2"),
@@ -35,19 +46,23 @@ assert HEADER.itemsize == 32 and RECORD.itemsize == 24
 
 class Alignments(NamedTuple):
     """Per-read arrays in read order; ``cigars[p]`` is a uint32 array;
-    ``strand`` is 0 for reads from blocks without strand bytes."""
+    ``strand`` is 0 for reads from blocks without strand bytes; ``mapq`` is
+    255 and ``sub_score`` 0 for reads from blocks without flag bit 1."""
     ref_pos: np.ndarray
     score: np.ndarray
     nm: np.ndarray
     end_i: np.ndarray
     end_j: np.ndarray
     cigars: CigarList
-    strand: np.ndarray
+    mapq: np.ndarray
+    sub_score: np.ndarray
+    strand: np.ndarray          # stays the last field
 
 
 class AlnBlock(NamedTuple):
     """One block to write: reads first_read .. first_read + len(score).  With
-    ``strand`` (0 / 1 per read) the block is written with flag bit 0."""
+    ``strand`` (0 / 1 per read) the block is written with flag bit 0; with
+    ``mapq`` (0 .. 60) and ``sub_score``, which go together, with flag bit 1."""
     first_read: int
     ref_pos: Sequence
     score: Sequence
@@ -56,6 +71,8 @@ class AlnBlock(NamedTuple):
     end_j: Sequence
     cigars: Sequence
     strand: Optional[Sequence] = None
+    mapq: Optional[Sequence] = None
+    sub_score: Optional[Sequence] = None
 
 
 def write_alignments(path, blocks: Sequence[AlnBlock]) -> None:
@@ -83,15 +100,26 @@ def write_alignments(path, blocks: Sequence[AlnBlock]) -> None:
                     raise ValueError("a strand byte is neither 0 nor 1")
                 head["flags"] = FLAG_STRAND
                 tail = strand.astype(np.uint8).tobytes() + bytes(-n % 4)
+            if (b.mapq is None) != (b.sub_score is None):
+                raise ValueError("mapq and sub_score go together")
+            if b.mapq is not None:
+                mapq = np.asarray(b.mapq, np.int64).reshape(-1)
+                sub = np.asarray(b.sub_score, np.int64).reshape(-1)
+                if mapq.size != n or sub.size != n:
+                    raise ValueError("block arrays disagree on the number of reads")
+                if ((mapq < 0) | (mapq > MAPQ_MAX)).any():
+                    raise ValueError(f"a mapq is outside [0, {MAPQ_MAX}]")
+                head["flags"] |= FLAG_MAPQ
+                tail += mapq.astype(np.uint8).tobytes() + bytes(-n % 4) + sub.astype("<i4").tobytes()
             f.write(head.tobytes() + rec.tobytes() + ops.tobytes() + tail)
 
 
 def read_alignments(path) -> Alignments:
     """Read an ``.aln`` file back into read order.  Raises ValueError on a bad
     magic or version, an undefined flag bit or non-zero reserved bytes, a
-    truncated block (inside its strand bytes included), a strand byte other
-    than 0 / 1, op counts that do not add up, or blocks that do not tile
-    [0, N) exactly (a gap or an overlap)."""
+    truncated block (inside its strand or mapq bytes included), a strand byte
+    other than 0 / 1, a mapq above 60, non-zero padding, op counts that do not
+    add up, or blocks that do not tile [0, N) exactly (a gap or an overlap)."""
     with open(path, "rb") as f:
         data = f.read()
     blocks = []
@@ -105,15 +133,17 @@ def read_alignments(path) -> Alignments:
         if int(head["version"]) != VERSION:
             raise ValueError(f"{path}: version {int(head['version'])}, expected {VERSION}")
         flags = int(head["flags"])
-        if flags & ~FLAG_STRAND:
-            raise ValueError(f"{path}: undefined flag bits {flags & ~FLAG_STRAND:#x} at byte {at}")
+        if flags & ~(FLAG_STRAND | FLAG_MAPQ):
+            raise ValueError(f"{path}: undefined flag bits {flags & ~(FLAG_STRAND | FLAG_MAPQ):#x} at byte {at}")
         if int(head["zero"]) != 0:
             raise ValueError(f"{path}: reserved header bytes are not zero at byte {at}")
         n, n_ops = int(head["n_reads"]), int(head["n_ops"])
         strand_bytes = (n + 3) // 4 * 4 if flags & FLAG_STRAND else 0
-        size = HEADER.itemsize + n * RECORD.itemsize + n_ops * 4 + strand_bytes
+        mapq_bytes = (n + 3) // 4 * 4 + 4 * n if flags & FLAG_MAPQ else 0
+        size = HEADER.itemsize + n * RECORD.itemsize + n_ops * 4 + strand_bytes + mapq_bytes
         if len(data) - at < size:
-            raise ValueError(f"{path}: truncated block at byte {at} ({len(data) - at} of {size} bytes)")
+            raise ValueError(f"{path}: truncated block at byte {at} ({len(data) - at} of the {size} bytes "
+                             f"its counts and flags {flags:#x} ask for)")
         rec = np.frombuffer(data, RECORD, n, at + HEADER.itemsize)
         ops = np.frombuffer(data, "<u4", n_ops, at + HEADER.itemsize + n * RECORD.itemsize)
         if int(rec["n_ops"].sum(dtype=np.uint64)) != n_ops:
@@ -121,17 +151,26 @@ def read_alignments(path) -> Alignments:
                              f"{int(rec['n_ops'].sum(dtype=np.uint64))} ops, its header says {n_ops}")
         strand = np.zeros(n, np.uint8)
         if flags & FLAG_STRAND:
-            raw = np.frombuffer(data, np.uint8, strand_bytes, at + size - strand_bytes)
+            raw = np.frombuffer(data, np.uint8, strand_bytes, at + size - mapq_bytes - strand_bytes)
             if (raw[:n] > 1).any():
                 raise ValueError(f"{path}: a strand byte of the block at byte {at} is neither 0 nor 1")
             if raw[n:].any():
                 raise ValueError(f"{path}: the strand padding of the block at byte {at} is not zero")
             strand = raw[:n].copy()
-        blocks.append((int(head["first_read"]), rec, ops, strand))
+        mapq, sub = np.full(n, MAPQ_UNAVAILABLE, np.uint8), np.zeros(n, np.int32)
+        if flags & FLAG_MAPQ:
+            raw = np.frombuffer(data, np.uint8, mapq_bytes - 4 * n, at + size - mapq_bytes)
+            if (raw[:n] > MAPQ_MAX).any():
+                raise ValueError(f"{path}: a mapq of the block at byte {at} is above {MAPQ_MAX}")
+            if raw[n:].any():
+                raise ValueError(f"{path}: the mapq padding of the block at byte {at} is not zero")
+            mapq = raw[:n].copy()
+            sub = np.frombuffer(data, "<i4", n, at + size - 4 * n).astype(np.int32)
+        blocks.append((int(head["first_read"]), rec, ops, strand, mapq, sub))
         at += size
     blocks.sort(key=lambda b: (b[0], len(b[1])))  # an empty block sits before the reads at its index
     nxt = 0
-    for first, rec, _, _ in blocks:
+    for first, rec, *_ in blocks:
         if first > nxt:
             raise ValueError(f"{path}: gap: reads {nxt}..{first - 1} are in no block")
         if first < nxt:
@@ -139,10 +178,12 @@ def read_alignments(path) -> Alignments:
         nxt = first + len(rec)
     rec = np.concatenate([b[1] for b in blocks]) if blocks else np.zeros(0, RECORD)
     strand = np.concatenate([b[3] for b in blocks]) if blocks else np.zeros(0, np.uint8)
+    mapq = np.concatenate([b[4] for b in blocks]) if blocks else np.zeros(0, np.uint8)
+    sub = np.concatenate([b[5] for b in blocks]) if blocks else np.zeros(0, np.int32)
     cigars = CigarList()
-    for _, r, ops, _ in blocks:
+    for _, r, ops, *_ in blocks:
         off = np.concatenate([[0], np.cumsum(r["n_ops"], dtype=np.int64)])
         cigars.extend(ops[off[k]:off[k + 1]].astype(np.uint32) for k in range(len(r)))
     cigars.n_cigar = rec["n_ops"].astype(np.int32)
     return Alignments(rec["ref_pos"].astype(np.int64), rec["score"].astype(np.int32), rec["nm"].astype(np.int32),
-                      rec["end_i"].astype(np.int16), rec["end_j"].astype(np.int16), cigars, strand)
+                      rec["end_i"].astype(np.int16), rec["end_j"].astype(np.int16), cigars, mapq, sub, strand)

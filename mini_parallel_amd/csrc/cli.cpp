@@ -88,6 +88,12 @@ void usage() {
         "      --seed-k N               --map: k-mer length, 4..14 (default 12)\n"
         "      --seed-max-occ N         --map: k-mers with more occurrences are ignored, 1..64 (default 64)\n"
         "      --seed-band N            --map: width of the diagonal band that votes together (default 16)\n"
+        "      --mapq                   --map: score a second candidate locus per read as well (the best other\n"
+        "                               seed band at least --seed-sep diagonals away), keep the better-scoring one;\n"
+        "                               .aln blocks then carry a mapping quality (0..60, an uncalibrated heuristic)\n"
+        "                               and the other candidate's score per read\n"
+        "      --seed-sep N             --mapq: least distance between the two candidates' diagonals, at least\n"
+        "                               --seed-band (default 0: the read's window length)\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -131,6 +137,8 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--seed-k") a.seed_k = atoi(v().c_str());
         else if (s == "--seed-max-occ") a.seed_max_occ = atoi(v().c_str());
         else if (s == "--seed-band") a.seed_band = atoi(v().c_str());
+        else if (s == "--mapq") a.mapq = true;
+        else if (s == "--seed-sep") { a.seed_sep = atoi(v().c_str()); a.has_seed_sep = true; }
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -165,6 +173,11 @@ Args parse_args(int argc, char** argv) {
         if (a.seed_max_occ < 1 || a.seed_max_occ > 64) die("error: --seed-max-occ must be 1..64");
         if (a.seed_band < 1) die("error: --seed-band must be at least 1");
     }
+    // refused here, before any file is opened, like --map
+    if (a.mapq && !a.map) die("error: --mapq needs --map");
+    if (a.has_seed_sep && !a.mapq) die("error: --seed-sep needs --mapq");
+    if (a.mapq && a.seed_sep != 0 && a.seed_sep < a.seed_band)
+        die("error: --seed-sep must be 0 (the window length) or at least --seed-band");
     return a;
 }
 
@@ -280,6 +293,8 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
     if (a.map)
         key += "|map|" + std::to_string(a.seed_k) + "|" + std::to_string(a.seed_max_occ) + "|" +
                std::to_string(a.seed_band);
+    // nor does a run with a second candidate and MAPQ resume one without, or one with another separation
+    if (a.mapq) key += "|mapq|" + std::to_string(a.seed_sep);
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -432,7 +447,13 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
       << ", \"teardown_ms\": " << rep.teardown_ms
       << ", \"both_strands\": " << (rep.both_strands ? "true" : "false") << ", \"reverse_reads\": " << rep.reverse_reads
       << ", \"map\": " << (rep.map ? "true" : "false") << ", \"seed_k\": " << (rep.map ? a.seed_k : 0)
-      << ", \"placed_reads\": " << rep.placed_reads
+      << ", \"placed_reads\": " << rep.placed_reads;
+    // --mapq only: reads with MAPQ 0, 1-29, 30-59, 60
+    if (rep.mapq)
+        j << ", \"mapq\": true, \"seed_sep\": " << a.seed_sep << ", \"mapq_histogram\": {\"0\": " << rep.mapq_hist[0]
+          << ", \"1-29\": " << rep.mapq_hist[1] << ", \"30-59\": " << rep.mapq_hist[2] << ", \"60\": " << rep.mapq_hist[3]
+          << "}";
+    j
       << ", \"inflate_bytes_in\": " << rep.gz_in << ", \"inflate_bytes_out\": " << rep.gz_out
       << ", \"reads_per_second\": " << reads / secs << ", \"t_main_unix_ns\": " << in.t_main_ns
       << ", \"t_record_unix_ns\": " << unix_ns() << "}\n";
@@ -470,6 +491,9 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
     printf("Total reads: %llu, total bases: %llu, total score: %lld\n", tot.reads, tot.bases, tot.score);
     if (rep.both_strands) printf("Both strands: %llu reverse reads\n", rep.reverse_reads);
     if (rep.map) printf("Mapped (k = %d): %llu of %llu reads placed\n", a.seed_k, rep.placed_reads, tot.reads);
+    if (rep.mapq)
+        printf("MAPQ: %llu reads at 0, %llu at 1-29, %llu at 30-59, %llu at 60\n", rep.mapq_hist[0], rep.mapq_hist[1],
+               rep.mapq_hist[2], rep.mapq_hist[3]);
     printf("Wall time: %.2f s", rep.wall_ms / 1000.0);
     if (rep.cells) printf(", %.1f GCUPS end-to-end", rep.cells / (rep.wall_ms * 1e6));
     printf("\n");

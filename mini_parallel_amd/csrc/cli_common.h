@@ -76,6 +76,11 @@ struct Args {
     // taking the window position from a pos= tag of the FASTQ header
     bool map = false;
     int seed_k = 12, seed_max_occ = 64, seed_band = 16;
+    // --mapq: --map scores a second candidate locus per read as well, keeps the better one and gives every
+    // record a sub-optimal score and a mapping quality; --seed-sep: the least distance of the second
+    // candidate's diagonal from the first (0: the read's window length)
+    bool mapq = false, has_seed_sep = false;
+    int seed_sep = 0;
     long chunk_size = 1, num_files = -1;
     std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out, alignments_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;

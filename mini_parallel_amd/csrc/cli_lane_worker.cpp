@@ -196,8 +196,22 @@ struct ResultSet {
     int64_t* d_wpos = nullptr;
     uint32_t *d_votes = nullptr, *d_hits = nullptr, *h_votes = nullptr;
     uint8_t* d_flags = nullptr;
+    // --mapq: the second candidate's positions, votes and flags, its scoring
+    // results (and with --both-strands its strand bytes and oriented rows),
+    // and what the selection writes.  The selection leaves the winner in the
+    // set's own arrays above, so everything after it reads those as before.
+    int64_t* d_wpos1 = nullptr;
+    uint32_t* d_votes1 = nullptr;
+    uint8_t* d_flags1 = nullptr;
+    int32_t* d_score1 = nullptr;
+    int16_t *d_ei1 = nullptr, *d_ej1 = nullptr;
+    uint16_t* d_wlen1 = nullptr;
+    uint8_t *d_strand1 = nullptr, *d_oriented1 = nullptr;
+    uint8_t *d_mapq = nullptr, *d_cand = nullptr, *h_mapq = nullptr;
+    int32_t *d_sub = nullptr, *h_sub = nullptr;
     AlnSet aln;
     msw_out_t out() const { return msw_out_t{d_score, d_ei, d_ej}; }
+    msw_out_t out1() const { return msw_out_t{d_score1, d_ei1, d_ej1}; }
 };
 
 class LaneWorker {
@@ -213,6 +227,7 @@ class LaneWorker {
     bool next_batch(size_t fi, void* stream, msw_dev_reads_t* d);
     void settle(ResultSet& r);
     void write_aln_block(ResultSet& r, FileState& f);
+    bool score(ResultSet& r, const msw_dev_reads_t& d, const int64_t* pos, bool alt, void* stream);
     bool submit(ResultSet& r, const msw_dev_reads_t& d, size_t fi, void* stream);
     int open_out(const std::string& dir, const FileState& f, const char* ext);
 
@@ -220,7 +235,7 @@ class LaneWorker {
     WgsRun& run_;
     const Args& a_;
     const int wi_, gi_;
-    const bool aln_, both_, map_;
+    const bool aln_, both_, map_, mapq_;
     const uint64_t batch_;
     Clock::time_point ts0_;
     Ctx ctx_;
@@ -245,7 +260,7 @@ class LaneWorker {
 // prefetch, genome, kernels, result sets.
 LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     : lanes_(lanes), run_(lanes.run), a_(lanes.run.a), wi_(wi), gi_(wi % lanes.run.ngpu), aln_(lanes.aln),
-      both_(lanes.both), map_(lanes.run.a.map), batch_(lanes.batch), ts0_(Clock::now()),
+      both_(lanes.both), map_(lanes.run.a.map), mapq_(lanes.run.a.mapq), batch_(lanes.batch), ts0_(Clock::now()),
       // lean: a GPU-reader worker scores device-resident batches
       // only, so its context makes just the compute stream
       ctx_(lanes.run.devices[gi_].ordinal, MSW_CTX_LEAN) {
@@ -316,6 +331,28 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
             r.h_votes = (uint32_t*)msw_host_alloc(batch_ * 4);
             if (!r.d_wpos || !r.d_votes || !r.d_hits || !r.d_flags || !r.h_votes)
                 die(std::string("GPU lane reader seed buffers: ") + msw_last_error());
+        }
+        if (mapq_) {
+            r.d_wpos1 = (int64_t*)msw_dev_alloc(ctx_.h, batch_ * 8);
+            r.d_votes1 = (uint32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
+            r.d_flags1 = (uint8_t*)msw_dev_alloc(ctx_.h, batch_);
+            r.d_score1 = (int32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
+            r.d_ei1 = (int16_t*)msw_dev_alloc(ctx_.h, batch_ * 2);
+            r.d_ej1 = (int16_t*)msw_dev_alloc(ctx_.h, batch_ * 2);
+            r.d_wlen1 = (uint16_t*)msw_dev_alloc(ctx_.h, batch_ * 2);
+            r.d_mapq = (uint8_t*)msw_dev_alloc(ctx_.h, batch_);
+            r.d_cand = (uint8_t*)msw_dev_alloc(ctx_.h, batch_);
+            r.d_sub = (int32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
+            r.h_mapq = (uint8_t*)msw_host_alloc(batch_);
+            r.h_sub = (int32_t*)msw_host_alloc(batch_ * 4);
+            if (both_) {
+                r.d_strand1 = (uint8_t*)msw_dev_alloc(ctx_.h, batch_);
+                r.d_oriented1 = (uint8_t*)msw_dev_alloc(ctx_.h, batch_ * read_stride());
+            }
+            if (!r.d_wpos1 || !r.d_votes1 || !r.d_flags1 || !r.d_score1 || !r.d_ei1 || !r.d_ej1 || !r.d_wlen1 ||
+                !r.d_mapq || !r.d_cand || !r.d_sub || !r.h_mapq || !r.h_sub ||
+                (both_ && (!r.d_strand1 || !r.d_oriented1)))
+                die(std::string("GPU lane reader candidate buffers: ") + msw_last_error());
         }
     }
     // per-read records of a batch, built here and written from here:
@@ -423,7 +460,8 @@ void LaneWorker::write_aln_block(ResultSet& r, FileState& f) {
     std::vector<uint8_t>& block = r.aln.block;
     block.clear();
     append_aln_block(block, r.first, r.n, r.aln.h.ref_pos, r.h.score, r.aln.h.nm, r.aln.h.off, r.h.end_i, r.h.end_j,
-                     r.aln.h_ops, r.aln.n_ops, both_ ? r.h_strand : nullptr);
+                     r.aln.h_ops, r.aln.n_ops, both_ ? r.h_strand : nullptr, mapq_ ? r.h_mapq : nullptr,
+                     mapq_ ? r.h_sub : nullptr);
     size_t done = 0;
     while (done < block.size()) {
         const ssize_t w = write(f.aln_fd, block.data() + done, block.size() - done);
@@ -476,6 +514,14 @@ void LaneWorker::settle(ResultSet& r) {
             for (uint64_t i = 0; i < r.n; ++i) placed += r.h_votes[i] >= seed_.min_votes;  // win_pos >= 0
             run_.placed_reads += placed;
         }
+        if (mapq_) {
+            unsigned long long hist[4] = {0, 0, 0, 0};
+            for (uint64_t i = 0; i < r.n; ++i) {
+                const uint8_t q = r.h_mapq[i];
+                hist[q == 0 ? 0 : q < 30 ? 1 : q < 60 ? 2 : 3] += 1;
+            }
+            for (int k = 0; k < 4; ++k) run_.mapq_hist[k] += hist[k];
+        }
         if (rec && pwrite(f.scores_fd, rec, r.n * 8, (off_t)(r.first * 8)) != (ssize_t)(r.n * 8)) {
             fprintf(stderr, "  error writing scores for %s\n", f.path.c_str());
             f.failed = true;
@@ -485,6 +531,19 @@ void LaneWorker::settle(ResultSet& r) {
     open_files_[r.fi].first -= 1;
     maybe_finish(r.fi);
     run_.trace_ev(wi_, "settled", r.n);
+}
+
+// One scoring call of batch d at the window positions `pos`, into the set's
+// own result arrays or (alt) into its second candidate's.
+bool LaneWorker::score(ResultSet& r, const msw_dev_reads_t& d, const int64_t* pos, bool alt, void* stream) {
+    msw_out_t o = alt ? r.out1() : r.out();
+    uint16_t* wlen = alt ? r.d_wlen1 : r.d_wlen;
+    return (both_ ? msw_align_reads_strands_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, pos, d.n,
+                                                   window_for(a_, 0), d.max_len, &o, wlen,
+                                                   alt ? r.d_strand1 : r.d_strand, alt ? r.d_oriented1 : r.d_oriented,
+                                                   read_stride(), stream)
+                  : msw_align_reads_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, pos, d.n,
+                                           window_for(a_, 0), d.max_len, &o, wlen, stream)) == MSW_OK;
 }
 
 // Batch d of file fi into result set r on `stream`: scoring, the copy-back
@@ -508,21 +567,38 @@ bool LaneWorker::submit(ResultSet& r, const msw_dev_reads_t& d, size_t fi, void*
     bool seeded = true;
     if (map_) {
         const msw_seed_out_t so{r.d_wpos, r.d_votes, r.d_hits, r.d_flags};
+        const msw_seed_alt_t sa{r.d_wpos1, r.d_votes1, r.d_flags1};
+        const uint8_t* rc_rows = both_ ? r.d_oriented : nullptr;
+        const uint32_t rc_stride = both_ ? read_stride() : 0;
         seeded = (!both_ || msw_revcomp_device(ctx_.h, d.reads, d.read_len, d.read_stride, d.n, r.d_oriented,
                                                read_stride(), stream) == MSW_OK) &&
-                 msw_seed_reads_device(ctx_.h, idx_, d.reads, both_ ? r.d_oriented : nullptr, d.read_len, d.read_stride,
-                                       both_ ? read_stride() : 0, d.n, d.max_len, &seed_, &so, stream) == MSW_OK &&
+                 // --mapq: the candidates call in the seeding call's place
+                 (mapq_ ? msw_seed_candidates_device(ctx_.h, idx_, d.reads, rc_rows, d.read_len, d.read_stride, rc_stride,
+                                                     d.n, d.max_len, &seed_, (uint32_t)a_.seed_sep, &so, &sa, stream)
+                        : msw_seed_reads_device(ctx_.h, idx_, d.reads, rc_rows, d.read_len, d.read_stride, rc_stride, d.n,
+                                                d.max_len, &seed_, &so, stream)) == MSW_OK &&
                  msw_memcpy_d2h_async(ctx_.h, r.h_votes, r.d_votes, d.n * 4, stream) == MSW_OK;
         pos = r.d_wpos;
         da.pos = r.d_wpos;
     }
-    if (!seeded ||
-        (both_ ? msw_align_reads_strands_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, pos, d.n,
-                                                window_for(a_, 0), d.max_len, &o, r.d_wlen, r.d_strand, r.d_oriented,
-                                                read_stride(), stream) != MSW_OK ||
-                     msw_memcpy_d2h_async(ctx_.h, r.h_strand, r.d_strand, d.n, stream) != MSW_OK
-               : msw_align_reads_device(ctx_.h, &sc_, gen_, d.reads, d.read_len, d.read_stride, pos, d.n,
-                                        window_for(a_, 0), d.max_len, &o, r.d_wlen, stream) != MSW_OK) ||
+    // --mapq: both candidates are scored and the selection leaves the better
+    // one in the set's own arrays (scores, end cells, window lengths and
+    // positions, strand bytes, oriented rows), before anything is copied back
+    bool selected = true;
+    if (seeded && mapq_) {
+        const bool ends = sc_.want_coords != 0;
+        const msw_cand_t c0{r.d_score, ends ? r.d_ei : nullptr, ends ? r.d_ej : nullptr, r.d_wlen,
+                            both_ ? r.d_strand : nullptr, both_ ? r.d_oriented : nullptr, r.d_wpos};
+        const msw_cand_t c1{r.d_score1, ends ? r.d_ei1 : nullptr, ends ? r.d_ej1 : nullptr, r.d_wlen1,
+                            both_ ? r.d_strand1 : nullptr, both_ ? r.d_oriented1 : nullptr, r.d_wpos1};
+        selected = score(r, d, r.d_wpos, false, stream) && score(r, d, r.d_wpos1, true, stream) &&
+                   msw_mapq_select_device(ctx_.h, &c0, &c1, read_stride(), d.read_len, d.n, sc_.match, r.d_sub, r.d_mapq,
+                                          r.d_cand, stream) == MSW_OK &&
+                   msw_memcpy_d2h_async(ctx_.h, r.h_mapq, r.d_mapq, d.n, stream) == MSW_OK &&
+                   msw_memcpy_d2h_async(ctx_.h, r.h_sub, r.d_sub, d.n * 4, stream) == MSW_OK;
+    }
+    if (!seeded || !selected || (!mapq_ && !score(r, d, pos, false, stream)) ||
+        (both_ && msw_memcpy_d2h_async(ctx_.h, r.h_strand, r.d_strand, d.n, stream) != MSW_OK) ||
         msw_memcpy_d2h_async(ctx_.h, r.h.score, r.d_score, d.n * 4, stream) != MSW_OK ||
         // end cells only feed --scores-out records
         (sc_.want_coords && (msw_memcpy_d2h_async(ctx_.h, r.h.end_i, r.d_ei, d.n * 2, stream) != MSW_OK ||

@@ -237,6 +237,8 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
     rep.map = a.map;
     rep.placed_reads = placed_reads.load();
     rep.index_ms = ph_index;
+    rep.mapq = a.mapq;
+    for (int k = 0; k < 4; ++k) rep.mapq_hist[k] = mapq_hist[k].load();
     rep.readers = readers;
     rep.host_threads = host_threads;
     rep.gpu = gpu;

@@ -117,6 +117,8 @@ struct WgsReport {
     bool map = false;                          // --map
     unsigned long long placed_reads = 0;       // --map: reads the seeding gave a window (win_pos >= 0)
     double index_ms = 0;                       // --map: the k-mer index build, a phase of the setup split
+    bool mapq = false;                         // --mapq
+    unsigned long long mapq_hist[4] = {0, 0, 0, 0};  // --mapq: reads with MAPQ 0, 1-29, 30-59, 60
 };
 
 // The window of a read of `len` bases: --window, else 2 x read length capped
@@ -156,6 +158,7 @@ struct WgsRun {
     std::atomic<unsigned long long> cells{0};
     std::atomic<unsigned long long> reverse_reads{0};  // --both-strands: strand-1 reads
     std::atomic<unsigned long long> placed_reads{0};   // --map: reads with a window
+    std::atomic<unsigned long long> mapq_hist[4] = {};  // --mapq: reads with MAPQ 0, 1-29, 30-59, 60
     StartGate gate;
     Clock::time_point t_setup, t_all;
     // the clock stops when the last worker has its last results on the host;

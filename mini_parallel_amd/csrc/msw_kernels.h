@@ -348,6 +348,52 @@ hipError_t launch_seed_reads(const SeedParams& p, hipStream_t stream);
 // blocks per CU of seed_reads_kernel at this cap; the query loads the module
 int seed_blocks_per_cu(uint32_t cap);
 
+// Candidates and mapping quality (the contract is in include/msw.h).
+// seed_candidates_kernel (msw_seed.hip): s is what seed_reads_kernel takes and
+// its four outputs are written as that kernel writes them; sep 0 = the read's
+// max(W, band), else sep >= band.  Same LDS as launch_seed_reads.
+struct SeedCandParams {
+    SeedParams s;
+    uint32_t sep;
+    int64_t* win_pos1;
+    uint32_t* votes1;
+    uint8_t* flags1;
+};
+hipError_t launch_seed_candidates(const SeedCandParams& q, hipStream_t stream);
+int seed_candidates_blocks_per_cu(uint32_t cap);
+// mapq_select_kernel (msw_mapq.hip).  Per read the alternate wins iff
+// score_a > score: its score, end cell, win_len, strand, win_pos and oriented
+// row then replace the primary's (row copy: both slabs 16-byte aligned, the one
+// stride a multiple of 16); sub_score is the loser's score, cand 0 / 1, mapq the
+// header's formula.  end_i / end_j (with their _a) null: score only; strand and
+// oriented (with their _a) null: one strand, no row traffic; win_len null: not
+// moved.
+struct MapqSelectParams {
+    int32_t* score;
+    int16_t* end_i;
+    int16_t* end_j;
+    uint16_t* win_len;
+    uint8_t* strand;
+    uint8_t* oriented;
+    int64_t* win_pos;
+    const int32_t* score_a;
+    const int16_t* end_i_a;
+    const int16_t* end_j_a;
+    const uint16_t* win_len_a;
+    const uint8_t* strand_a;
+    const uint8_t* oriented_a;
+    const int64_t* win_pos_a;
+    const uint16_t* read_len;
+    uint64_t oriented_stride;
+    uint64_t n;
+    int32_t match;
+    int32_t* sub_score;
+    uint8_t* mapq;
+    uint8_t* cand;
+};
+hipError_t launch_mapq_select(const MapqSelectParams& p, hipStream_t stream);
+int mapq_blocks_per_cu();
+
 // Both strands (msw_strand.hip; the contract is in include/msw.h).
 // out[p][0, read_len[p]) = the reverse complement of read row p, zeros up to
 // out_stride: every byte of every output row is written.  out 16-byte

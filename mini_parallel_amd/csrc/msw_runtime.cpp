@@ -2731,9 +2731,14 @@ static int check_seed_params(const msw_seed_params_t* sp, uint32_t max_read_len)
     return MSW_OK;
 }
 
-int msw_seed_reads_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
-                          const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
-                          uint32_t max_read_len, const msw_seed_params_t* sp, const msw_seed_out_t* out, void* stream) {
+// The checks of the device seeding calls and the kernel's parameters; *go is
+// false where the call has nothing to launch (n == 0).
+static int seed_device_params(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
+                              const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
+                              uint32_t max_read_len, const msw_seed_params_t* sp, const msw_seed_out_t* out,
+                              msw::SeedParams* pp, bool* go) {
+    msw::SeedParams& p = *pp;
+    *go = false;
     if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
     if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
     int rc;
@@ -2745,7 +2750,6 @@ int msw_seed_reads_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads
     if (rc_reads && (rc_stride == 0 || max_read_len > rc_stride))
         return fail(MSW_E_INVALID, "max_read_len exceeds rc_stride");
     if ((rc = set_device(ctx))) return rc;
-    msw::SeedParams p;
     p.off = x->d_off;
     p.pos = x->d_pos;
     p.reads = reads;
@@ -2764,6 +2768,18 @@ int msw_seed_reads_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads
     p.votes = out->votes;
     p.hits = out->hits;
     p.flags = out->flags;
+    *go = true;
+    return MSW_OK;
+}
+
+int msw_seed_reads_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
+                          const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
+                          uint32_t max_read_len, const msw_seed_params_t* sp, const msw_seed_out_t* out, void* stream) {
+    msw::SeedParams p;
+    bool go;
+    int rc = seed_device_params(ctx, x, reads, rc_reads, read_len, read_stride, rc_stride, n, max_read_len, sp, out, &p,
+                                &go);
+    if (rc || !go) return rc;
     HIP_TRY(msw::launch_seed_reads(p, call_stream(ctx, stream)));
     return MSW_OK;
 }
@@ -2820,6 +2836,285 @@ int msw_seed_reads(msw_ctx* ctx, const msw_index* x, const msw_read_batch_t* b, 
     (void)hipFree(d);
     if (rc) return rc;
     if (e != hipSuccess) return fail(MSW_E_DEVICE, "seeding: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
+// Candidates and mapping quality (include/msw.h; the kernels: msw_seed.hip,
+// msw_mapq.hip).
+int msw_seed_candidates_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
+                               const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
+                               uint32_t max_read_len, const msw_seed_params_t* sp, uint32_t sep,
+                               const msw_seed_out_t* out, const msw_seed_alt_t* alt, void* stream) {
+    msw::SeedCandParams q;
+    bool go;
+    int rc = seed_device_params(ctx, x, reads, rc_reads, read_len, read_stride, rc_stride, n, max_read_len, sp, out,
+                                &q.s, &go);
+    if (rc) return rc;
+    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
+    if (!go) return MSW_OK;
+    if (!alt || !alt->win_pos || !alt->votes || !alt->flags) return fail(MSW_E_INVALID, "NULL array in alt");
+    q.sep = sep;
+    q.win_pos1 = alt->win_pos;
+    q.votes1 = alt->votes;
+    q.flags1 = alt->flags;
+    HIP_TRY(msw::launch_seed_candidates(q, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_seed_candidates(msw_ctx* ctx, const msw_index* x, const msw_read_batch_t* b, int both,
+                        const msw_seed_params_t* sp, uint32_t sep, const msw_seed_out_t* out,
+                        const msw_seed_alt_t* alt, uint64_t chunk_reads) {
+    if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
+    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
+    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
+    const uint64_t n = b->n_pairs;
+    uint32_t max_m = 0;
+    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array");
+    max_u16(b->read_len, n, max_m);
+    int rc;
+    if ((rc = check_seed_params(sp, max_m))) return rc;
+    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
+    if (n == 0) return MSW_OK;
+    if (!b->reads || !out || !out->win_pos || !out->votes || !out->hits || !out->flags || !alt || !alt->win_pos ||
+        !alt->votes || !alt->flags)
+        return fail(MSW_E_INVALID, "NULL array");
+    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
+    const size_t rs = b->read_stride, os = round16((uint32_t)std::max<uint32_t>(max_m, 1));
+    // [reads | rc rows | win_pos, win_pos1 i64 | votes, hits, votes1 u32 | read_len u16 | flags, flags1 u8]
+    const size_t o_rc = (chunk * rs + 255) & ~(size_t)255, o_wp = (o_rc + (both ? chunk * os : 0) + 255) & ~(size_t)255;
+    const size_t o_wp1 = o_wp + chunk * 8, o_votes = o_wp1 + chunk * 8, o_hits = o_votes + chunk * 4,
+                 o_votes1 = o_hits + chunk * 4, o_rl = o_votes1 + chunk * 4, o_fl = o_rl + chunk * 2,
+                 o_fl1 = o_fl + chunk;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, o_fl1 + chunk + 256);
+    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", o_fl1 + chunk, hipGetErrorString(e));
+    hipStream_t st = ctx->compute;
+    rc = MSW_OK;
+    for (uint64_t lo = 0; lo < n && rc == MSW_OK; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_rl);
+        msw_seed_out_t dout = {reinterpret_cast<int64_t*>(d + o_wp), reinterpret_cast<uint32_t*>(d + o_votes),
+                               reinterpret_cast<uint32_t*>(d + o_hits), d + o_fl};
+        msw_seed_alt_t dalt = {reinterpret_cast<int64_t*>(d + o_wp1), reinterpret_cast<uint32_t*>(d + o_votes1),
+                               d + o_fl1};
+        e = hipMemcpyAsync(d, b->reads + lo * rs, c * rs, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rl, b->read_len + lo, c * 2, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) break;
+        if (both && (rc = msw_revcomp_device(ctx, d, d_rl, (uint32_t)rs, c, d + o_rc, (uint32_t)os, st))) break;
+        if ((rc = msw_seed_candidates_device(ctx, x, d, both ? d + o_rc : nullptr, d_rl, (uint32_t)rs, (uint32_t)os, c,
+                                             max_m, sp, sep, &dout, &dalt, st)))
+            break;
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+        };
+        down(out->win_pos + lo, dout.win_pos, c * 8);
+        down(out->votes + lo, dout.votes, c * 4);
+        down(out->hits + lo, dout.hits, c * 4);
+        down(out->flags + lo, dout.flags, c);
+        down(alt->win_pos + lo, dalt.win_pos, c * 8);
+        down(alt->votes + lo, dalt.votes, c * 4);
+        down(alt->flags + lo, dalt.flags, c);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+    }
+    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "candidates: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
+int msw_mapq_select_device(msw_ctx* ctx, const msw_cand_t* pr, const msw_cand_t* al, uint32_t oriented_stride,
+                           const uint16_t* read_len, uint64_t n, int32_t match, int32_t* sub_score, uint8_t* mapq,
+                           uint8_t* cand, void* stream) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    if (match < 0 || match > 64) return fail(MSW_E_RANGE, "mapq select: match=%d outside [0, 64]", match);
+    if (n == 0) return MSW_OK;
+    if (!pr || !al || !pr->score || !al->score || !pr->win_pos || !al->win_pos || !read_len || !sub_score || !mapq ||
+        !cand)
+        return fail(MSW_E_INVALID, "NULL array");
+    const bool coords = pr->end_i || pr->end_j || al->end_i || al->end_j;
+    if (coords && (!pr->end_i || !pr->end_j || !al->end_i || !al->end_j))
+        return fail(MSW_E_INVALID, "end_i / end_j must be given for both candidates or for neither");
+    const bool rows = pr->strand || pr->oriented || al->strand || al->oriented;
+    if (rows && (!pr->strand || !pr->oriented || !al->strand || !al->oriented))
+        return fail(MSW_E_INVALID, "strand / oriented must be given for both candidates or for neither");
+    if ((pr->win_len != nullptr) != (al->win_len != nullptr))
+        return fail(MSW_E_INVALID, "win_len must be given for both candidates or for neither");
+    if (rows && (((uintptr_t)pr->oriented & 15) != 0 || ((uintptr_t)al->oriented & 15) != 0 || oriented_stride == 0 ||
+                 oriented_stride % 16 != 0))
+        return fail(MSW_E_INVALID, "oriented must be 16-byte aligned and oriented_stride a non-zero multiple of 16");
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "mapq select: too many reads in one call");
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    msw::MapqSelectParams p;
+    p.score = pr->score, p.end_i = pr->end_i, p.end_j = pr->end_j, p.win_len = pr->win_len, p.strand = pr->strand;
+    p.oriented = pr->oriented, p.win_pos = pr->win_pos;
+    p.score_a = al->score, p.end_i_a = al->end_i, p.end_j_a = al->end_j, p.win_len_a = al->win_len;
+    p.strand_a = al->strand, p.oriented_a = al->oriented, p.win_pos_a = al->win_pos;
+    p.read_len = read_len;
+    p.oriented_stride = oriented_stride;
+    p.n = n;
+    p.match = match;
+    p.sub_score = sub_score, p.mapq = mapq, p.cand = cand;
+    HIP_TRY(msw::launch_mapq_select(p, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_index* x,
+                  const msw_read_batch_t* b, int both, const msw_seed_params_t* sp, uint32_t sep, msw_out_t* out,
+                  uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint64_t chunk_pairs) {
+    if (!ctx || !g || !x) return fail(MSW_E_INVALID, "ctx/genome/index is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
+    if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
+    msw_scoring_t scc = *sc;
+    scc.want_coords = 1;
+    Scheme sch;
+    int rc;
+    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
+    if ((rc = validate_aln(aln))) return rc;
+    const uint64_t n = b->n_pairs;
+    uint32_t max_m = 0;
+    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array in batch");
+    max_u16(b->read_len, n, max_m);
+    if ((rc = check_seed_params(sp, max_m))) return rc;
+    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
+    *aln->n_overflow = 0;
+    aln->cigar_off[0] = 0;
+    if (n == 0) return MSW_OK;
+    if (!b->reads) return fail(MSW_E_INVALID, "NULL array in batch");
+    if (both && !strand) return fail(MSW_E_INVALID, "strand is NULL");
+    if (!out || !out->score || !out->end_i || !out->end_j)
+        return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
+    if (!mq || !mq->mapq || !mq->sub_score || !mq->cand) return fail(MSW_E_INVALID, "NULL array in mapq");
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
+    const uint32_t window = sp->window;
+    const uint32_t max_n = window ? window : std::min<uint32_t>(2u * max_m, (uint32_t)msw::kMaxWinLen);
+    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    // Simple and synchronous, like msw_align_reads_trace.  Per chunk, all on
+    // the compute stream: upload, (reverse complement,) candidates, the two
+    // scoring calls, the selection, then trace and pack on the winner.
+    const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
+    const size_t rs = b->read_stride, ors = round16(std::max<uint32_t>(max_m, 1)), cs = (size_t)max_m + max_n;
+    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // [reads | rc rows | oriented 0 | oriented 1 | trace rows u32 | 3 x i64 | 8 x 4 B | off u32[c + 2] |
+    //  9 x 2 B | 6 x 1 B]
+    const size_t o_rc = up256(chunk * rs), o_or0 = up256(o_rc + (both ? chunk * ors : 0)),
+                 o_or1 = up256(o_or0 + (both ? chunk * ors : 0)), o_rows = up256(o_or1 + (both ? chunk * ors : 0)),
+                 o_q = up256(o_rows + chunk * cs * 4), o_w = o_q + chunk * 24, o_off = o_w + chunk * 32,
+                 o_h = o_off + (chunk + 2) * 4, o_b = up256(o_h + chunk * 18);
+    const size_t total_bytes = o_b + chunk * 6 + 256;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total_bytes);
+    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
+    uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
+    uint64_t ops_cap = chunk * 8;
+    e = hipMalloc((void**)&d_ops, ops_cap * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
+    }
+    int64_t *d_wp0 = reinterpret_cast<int64_t*>(d + o_q), *d_wp1 = d_wp0 + chunk, *d_ref = d_wp1 + chunk;
+    int32_t* w32 = reinterpret_cast<int32_t*>(d + o_w);
+    int32_t *d_s0 = w32, *d_s1 = w32 + chunk, *d_sub = w32 + 2 * chunk, *d_nc = w32 + 3 * chunk, *d_nm = w32 + 4 * chunk;
+    uint32_t *d_votes = reinterpret_cast<uint32_t*>(w32 + 5 * chunk), *d_hits = d_votes + chunk,
+             *d_votes1 = d_hits + chunk;
+    uint32_t* d_off = reinterpret_cast<uint32_t*>(d + o_off);
+    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
+    uint16_t *d_wl0 = d_rl + chunk, *d_wl1 = d_wl0 + chunk;
+    int16_t *d_ei0 = reinterpret_cast<int16_t*>(d_wl1 + chunk), *d_ej0 = d_ei0 + chunk, *d_ei1 = d_ej0 + chunk,
+            *d_ej1 = d_ei1 + chunk, *d_si = d_ej1 + chunk, *d_sj = d_si + chunk;
+    uint8_t *d_fl = d + o_b, *d_fl1 = d_fl + chunk, *d_st0 = d_fl1 + chunk, *d_st1 = d_st0 + chunk,
+            *d_mapq = d_st1 + chunk, *d_cand = d_mapq + chunk;
+    uint8_t *d_rc = d + o_rc, *d_or0 = d + o_or0, *d_or1 = d + o_or1;
+    hipStream_t st = ctx->compute;
+    std::vector<uint32_t> off(chunk + 1);
+    uint64_t base = 0;  // ops of the chunks before this one
+    rc = MSW_OK;
+    for (uint64_t lo = 0; lo < n && rc == MSW_OK && e == hipSuccess; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        auto up = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+        };
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+        };
+        up(d, b->reads + lo * rs, c * rs);
+        up(d_rl, b->read_len + lo, c * 2);
+        if (e != hipSuccess) break;
+        if (both && (rc = msw_revcomp_device(ctx, d, d_rl, (uint32_t)rs, c, d_rc, (uint32_t)ors, st))) break;
+        const msw_seed_out_t so = {d_wp0, d_votes, d_hits, d_fl};
+        const msw_seed_alt_t sa = {d_wp1, d_votes1, d_fl1};
+        if ((rc = msw_seed_candidates_device(ctx, x, d, both ? d_rc : nullptr, d_rl, (uint32_t)rs, (uint32_t)ors, c,
+                                             max_m, sp, sep, &so, &sa, st)))
+            break;
+        msw_out_t o0 = {d_s0, d_ei0, d_ej0}, o1 = {d_s1, d_ei1, d_ej1};
+        if (both) {
+            if ((rc = msw_align_reads_strands_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp0, c, window, max_m, &o0,
+                                                     d_wl0, d_st0, d_or0, (uint32_t)ors, st)) ||
+                (rc = msw_align_reads_strands_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp1, c, window, max_m, &o1,
+                                                     d_wl1, d_st1, d_or1, (uint32_t)ors, st)))
+                break;
+        } else if ((rc = msw_align_reads_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp0, c, window, max_m, &o0,
+                                                d_wl0, st)) ||
+                   (rc = msw_align_reads_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp1, c, window, max_m, &o1,
+                                                d_wl1, st))) {
+            break;
+        }
+        const msw_cand_t c0 = {d_s0, d_ei0, d_ej0, d_wl0, both ? d_st0 : nullptr, both ? d_or0 : nullptr, d_wp0};
+        const msw_cand_t c1 = {d_s1, d_ei1, d_ej1, d_wl1, both ? d_st1 : nullptr, both ? d_or1 : nullptr, d_wp1};
+        if ((rc = msw_mapq_select_device(ctx, &c0, &c1, (uint32_t)ors, d_rl, c, scc.match, d_sub, d_mapq, d_cand, st)))
+            break;
+        // from here on the reads are the winner's oriented rows
+        const uint8_t* rows = both ? d_or0 : d;
+        const uint32_t rstride = both ? (uint32_t)ors : (uint32_t)rs;
+        msw_trace_t dtr = {d_si, d_sj, d_nc, reinterpret_cast<uint32_t*>(d + o_rows), (uint32_t)cs};
+        if ((rc = msw_trace_reads_device(ctx, &scc, g, rows, d_rl, rstride, d_wp0, c, window, max_m, &o0, &dtr, st)))
+            break;
+        uint64_t total = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            msw_aln_t da = {d_ref, d_nm, d_off, d_ops, ops_cap, d_off + c + 1};
+            if ((rc = msw_aln_pack_device(ctx, g, rows, d_rl, rstride, d_wp0, c, &o0, &dtr, &da, st))) break;
+            down(off.data(), d_off, (c + 1) * 4);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) break;
+            total = off[c];
+            if (total <= ops_cap) break;
+            (void)hipFree(d_ops);
+            d_ops = nullptr;
+            ops_cap = total;
+            if (hipMalloc((void**)&d_ops, ops_cap * 4) != hipSuccess) {
+                d_ops = nullptr;
+                rc = fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the packed ops", (unsigned long long)ops_cap * 4);
+                break;
+            }
+        }
+        if (rc || e != hipSuccess) break;
+        down(out->score + lo, d_s0, c * 4);
+        down(out->end_i + lo, d_ei0, c * 2);
+        down(out->end_j + lo, d_ej0, c * 2);
+        if (both) down(strand + lo, d_st0, c);
+        down(mq->mapq + lo, d_mapq, c);
+        down(mq->sub_score + lo, d_sub, c * 4);
+        down(mq->cand + lo, d_cand, c);
+        down(aln->ref_pos + lo, d_ref, c * 8);
+        down(aln->nm + lo, d_nm, c * 4);
+        const uint64_t room = aln->cigar_cap > base ? aln->cigar_cap - base : 0;
+        down(aln->cigar + base, d_ops, std::min(total, room) * 4);
+        for (uint64_t k = 0; k <= c; ++k) aln->cigar_off[lo + k] = (uint32_t)(base + off[k]);
+        base += total;
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (d_ops) (void)hipFree(d_ops);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "map reads: %s", hipGetErrorString(e));
     return MSW_OK;
 }
 

@@ -102,8 +102,12 @@ struct SeedResult {
 };
 
 // One orientation of one read, by the whole wave (every lane returns the same
-// result).  keys: the block's LDS array, next_pow2(cap) words.
-__device__ SeedResult seed_orientation(const SeedParams& p, const uint8_t* row, int L, uint32_t* keys, int lane) {
+// result).  keys: the block's LDS array, next_pow2(cap) words.  ALT
+// (seed_candidates_kernel): *best2 is the orientation's second band, the same
+// packing, over the keys admissible against the first band at `sep`.
+template <bool ALT>
+__device__ SeedResult seed_orientation(const SeedParams& p, const uint8_t* row, int L, uint32_t* keys, int lane,
+                                       uint32_t sep, uint64_t* best2) {
     const int k = (int)p.k;
     const int n_kmers = L >= k ? L - k + 1 : 0;
     uint32_t run = 0;  // P of the last offset handled so far (wave-uniform)
@@ -138,6 +142,7 @@ __device__ SeedResult seed_orientation(const SeedParams& p, const uint8_t* row, 
     r.best = 0;
     r.hits = hits;
     r.truncated = run > p.cap ? 1u : 0u;
+    if constexpr (ALT) *best2 = 0;
     if (hits == 0) return r;  // wave-uniform
     uint32_t m = 1;
     while (m < hits) m <<= 1;
@@ -177,6 +182,36 @@ __device__ SeedResult seed_orientation(const SeedParams& p, const uint8_t* row, 
         const uint64_t o = __shfl_xor(best, d, 64);
         best = o > best ? o : best;
     }
+    if constexpr (ALT) {
+        // The second band, over the same sorted keys: a key is admissible iff
+        // it is at least sep away from the first band's.  sep >= band, so a
+        // band that starts below the excluded keys ends before the admissible
+        // keys above them: clipping its upper bound is all it takes.
+        const int64_t key0 = (int64_t)(0xFFFFFFFFu - (uint32_t)best);
+        const int64_t below = key0 - (int64_t)sep, above = key0 + (int64_t)sep;  // admissible: <= below, >= above
+        uint64_t b2 = 0;
+        for (uint32_t t = (uint32_t)lane; t < hits; t += 64) {
+            const uint32_t key = keys[t];
+            const int64_t k64 = (int64_t)key;
+            if (k64 > below && k64 < above) continue;
+            uint64_t want = (uint64_t)key + p.band;
+            if (k64 <= below && want > (uint64_t)below + 1u) want = (uint64_t)below + 1u;  // below >= k64 >= 0
+            uint32_t lo = t + 1, hi = hits;
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if ((uint64_t)keys[mid] >= want) hi = mid;
+                else lo = mid + 1;
+            }
+            const uint64_t v = (uint64_t)(lo - t) << 32 | (uint64_t)(0xFFFFFFFFu - key);
+            b2 = v > b2 ? v : b2;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const uint64_t o = __shfl_xor(b2, d, 64);
+            b2 = o > b2 ? o : b2;
+        }
+        *best2 = b2;
+    }
     __syncthreads();  // the next orientation or read refills keys
     r.best = best;
     return r;
@@ -188,11 +223,11 @@ __global__ __launch_bounds__(64) void seed_reads_kernel(SeedParams p) {
     for (uint64_t r = blockIdx.x; r < p.n; r += gridDim.x) {
         const uint32_t rl = p.read_len[r];
         const int L = (int)min((uint64_t)rl, p.read_stride);
-        SeedResult f = seed_orientation(p, p.reads + r * p.read_stride, L, keys, lane);
+        SeedResult f = seed_orientation<false>(p, p.reads + r * p.read_stride, L, keys, lane, 0u, nullptr);
         uint32_t flags = 0;
         if (p.rc_reads) {
             const int Lr = (int)min((uint64_t)rl, p.rc_stride);
-            const SeedResult v = seed_orientation(p, p.rc_reads + r * p.rc_stride, Lr, keys, lane);
+            const SeedResult v = seed_orientation<false>(p, p.rc_reads + r * p.rc_stride, Lr, keys, lane, 0u, nullptr);
             if ((v.best >> 32) > (f.best >> 32)) {  // strictly more votes: ties go forward
                 f = v;
                 flags = 1;
@@ -212,6 +247,72 @@ __global__ __launch_bounds__(64) void seed_reads_kernel(SeedParams p) {
             p.votes[r] = votes;
             p.hits[r] = f.hits;
             p.flags[r] = (uint8_t)(flags | f.truncated << 1);
+        }
+    }
+}
+
+// win_pos of a band that starts at the biased diagonal `key` (the placement rule)
+__device__ __forceinline__ int64_t seed_place(uint32_t key, uint32_t rl, uint32_t window, uint32_t band) {
+    const int64_t d0 = (int64_t)key - 65536;
+    const int64_t W = (int64_t)reads_window_want(window, rl);
+    const int64_t slack = W - ((int64_t)rl + (int64_t)band - 1);
+    const int64_t pad = slack > 0 ? slack / 2 : 0;
+    return d0 - pad > 0 ? d0 - pad : 0;
+}
+
+// Candidates (include/msw.h, "Candidates and mapping quality"): candidate 0 is
+// what seed_reads_kernel writes; candidate 1 is the best of the other bands
+// (the chosen orientation's second, the other orientation's two) that has
+// min_votes and lies sep or more from candidate 0's diagonal.
+__global__ __launch_bounds__(64) void seed_candidates_kernel(SeedCandParams q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t keys[];
+    const SeedParams& p = q.s;
+    const int lane = (int)threadIdx.x;
+    for (uint64_t r = blockIdx.x; r < p.n; r += gridDim.x) {
+        const uint32_t rl = p.read_len[r];
+        const int L = (int)min((uint64_t)rl, p.read_stride);
+        const uint32_t W = reads_window_want(p.window, rl);
+        const uint32_t sep = q.sep ? q.sep : (W > p.band ? W : p.band);
+        uint64_t own2 = 0, oth1 = 0, oth2 = 0;
+        SeedResult f = seed_orientation<true>(p, p.reads + r * p.read_stride, L, keys, lane, sep, &own2);
+        uint32_t flags = 0;
+        if (p.rc_reads) {
+            const int Lr = (int)min((uint64_t)rl, p.rc_stride);
+            const SeedResult v = seed_orientation<true>(p, p.rc_reads + r * p.rc_stride, Lr, keys, lane, sep, &oth2);
+            oth1 = v.best;
+            if ((v.best >> 32) > (f.best >> 32)) {  // strictly more votes: ties go forward
+                oth1 = f.best;
+                f = v;
+                const uint64_t t = own2;
+                own2 = oth2;
+                oth2 = t;
+                flags = 1;
+            }
+        }
+        if (lane == 0) {
+            const uint32_t votes = (uint32_t)(f.best >> 32);
+            const uint32_t key0 = 0xFFFFFFFFu - (uint32_t)f.best;
+            p.win_pos[r] = votes != 0 && votes >= p.min_votes ? seed_place(key0, rl, p.window, p.band) : -1;
+            p.votes[r] = votes;
+            p.hits[r] = f.hits;
+            p.flags[r] = (uint8_t)(flags | f.truncated << 1);
+            // votes << 33 | forward << 32 | ~key: the most votes, then forward, then the smaller diagonal
+            uint64_t pick = 0;
+            const uint64_t band3[3] = {own2, oth1, oth2};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const uint64_t b = band3[c];
+                const uint32_t v = (uint32_t)(b >> 32), key = 0xFFFFFFFFu - (uint32_t)b;
+                const uint32_t orient = c == 0 ? flags : flags ^ 1u;
+                const int64_t gap = (int64_t)key - (int64_t)key0;
+                const bool ok = votes != 0 && v != 0 && v >= p.min_votes && (gap < 0 ? -gap : gap) >= (int64_t)sep;
+                const uint64_t rank = (uint64_t)v << 33 | (uint64_t)(orient ^ 1u) << 32 | (uint64_t)(uint32_t)b;
+                if (ok && rank > pick) pick = rank;
+            }
+            const uint32_t v1 = (uint32_t)(pick >> 33);
+            q.win_pos1[r] = v1 ? seed_place(0xFFFFFFFFu - (uint32_t)pick, rl, p.window, p.band) : -1;
+            q.votes1[r] = v1;
+            q.flags1[r] = v1 ? (uint8_t)(((pick >> 32) & 1u) ^ 1u) : (uint8_t)0;
         }
     }
 }
@@ -276,6 +377,24 @@ hipError_t launch_seed_reads(const SeedParams& p, hipStream_t stream) {
     const unsigned blocks = (unsigned)std::min<uint64_t>(p.n, 1u << 20);
     hipLaunchKernelGGL(seed_reads_kernel, dim3(blocks), dim3(64), seed_lds_bytes(p.cap), stream, p);
     return hipGetLastError();
+}
+
+hipError_t launch_seed_candidates(const SeedCandParams& q, hipStream_t stream) {
+    const SeedParams& p = q.s;
+    if (p.n == 0) return hipSuccess;
+    if (p.cap == 0 || p.cap > kSeedMaxCap || p.step == 0 || p.band == 0 || p.k < 4 || p.k > 14 ||
+        (q.sep != 0 && q.sep < p.band))
+        return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(p.n, 1u << 20);
+    hipLaunchKernelGGL(seed_candidates_kernel, dim3(blocks), dim3(64), seed_lds_bytes(p.cap), stream, q);
+    return hipGetLastError();
+}
+
+int seed_candidates_blocks_per_cu(uint32_t cap) {
+    int a = 0;
+    const hipError_t e =
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, seed_candidates_kernel, 64, seed_lds_bytes(cap));
+    return e == hipSuccess ? a : 0;
 }
 
 int seed_blocks_per_cu(uint32_t cap) {

@@ -14,7 +14,10 @@ One row per process, one JSON line each:
                   revcomp   msw_revcomp_device (what seed2's slab costs to make)
                   score     msw_align_reads_device        } the yardsticks, fed
                   strands   msw_align_reads_strands_device } with the seeded win_pos
-                and the seed kernel's occupancy.
+                  cand1     msw_seed_candidates_device, forward only   } sep 0 (= W)
+                  cand2     msw_seed_candidates_device with the slab   }
+                  select    msw_mapq_select_device on the two strand results
+                and the seed kernels' occupancy.
 
   python3 tools/seed_bench.py --row seed [--reads 40000] [--k 12] [--max-occ 64]
   python3 tools/seed_bench.py --row index --genome-mbases 256 [--k 12]"""
@@ -112,6 +115,31 @@ def main():
         ctx.align_reads_strands_device(genome, d_R.data_ptr(), d_rl.data_ptr(), rs, wpos.data_ptr(), n, W, mr,
                                        score.data_ptr(), strand.data_ptr(), oriented.data_ptr(), ors, sc, 0, 0, 0, s)
 
+    wpos1, votes1, flags1 = z(n, torch.int64), z(n, torch.int32), z(n, torch.uint8)
+    score1, strand1, oriented1 = z(n, torch.int32), z(n, torch.uint8), z(n * ors, torch.uint8)
+    wlen, wlen1 = z(n, torch.int16), z(n, torch.int16)
+    sub, mapq, cand = z(n, torch.int32), z(n, torch.uint8), z(n, torch.uint8)
+
+    def cand_launch(both):
+        ctx.seed_candidates_device(index, d_R.data_ptr(), d_rl.data_ptr(), rs, n, mr, wpos.data_ptr(), votes.data_ptr(),
+                                   hits.data_ptr(), flags.data_ptr(), wpos1.data_ptr(), votes1.data_ptr(),
+                                   flags1.data_ptr(), rc_reads_ptr=rc.data_ptr() if both else 0,
+                                   rc_stride=ors if both else 0, sep=0, **seed_kw)
+
+    def alt_strands_launch():
+        ctx.align_reads_strands_device(genome, d_R.data_ptr(), d_rl.data_ptr(), rs, wpos1.data_ptr(), n, W, mr,
+                                       score1.data_ptr(), strand1.data_ptr(), oriented1.data_ptr(), ors, sc, 0, 0,
+                                       wlen1.data_ptr(), s)
+
+    def select_launch():
+        # in place: after a launch no alternate wins any more, so a repeated launch moves no rows
+        ctx.mapq_select_device(dict(score=score.data_ptr(), win_len=wlen.data_ptr(), strand=strand.data_ptr(),
+                                    oriented=oriented.data_ptr(), win_pos=wpos.data_ptr()),
+                               dict(score=score1.data_ptr(), win_len=wlen1.data_ptr(), strand=strand1.data_ptr(),
+                                    oriented=oriented1.data_ptr(), win_pos=wpos1.data_ptr()),
+                               d_rl.data_ptr(), n, sc.match, sub.data_ptr(), mapq.data_ptr(), cand.data_ptr(),
+                               oriented_stride=ors, stream=s)
+
     def timed(fn):
         for _ in range(args.warmup):
             fn()
@@ -137,6 +165,42 @@ def main():
     rec["strands_ms"] = timed(strands_launch)
     rec["seed1_over_score"] = round(rec["seed1_ms"] / rec["score_ms"], 2)
     rec["seed2_over_strands"] = round(rec["seed2_ms"] / rec["strands_ms"], 2)
+    rec["cand1_ms"] = timed(lambda: cand_launch(False))
+    rec["cand2_ms"] = timed(lambda: cand_launch(True))
+    rec["with_candidate_1"] = int((wpos1.cpu() >= 0).sum())
+    rec["cand1_over_seed1"] = round(rec["cand1_ms"] / rec["seed1_ms"], 2)
+    rec["cand2_over_seed2"] = round(rec["cand2_ms"] / rec["seed2_ms"], 2)
+    strands_launch()
+    alt_strands_launch()
+    torch.cuda.synchronize()
+    score0 = score.clone()                          # candidate 0's scores, before the select replaces the losers'
+    select_launch()                                 # winners to move
+    torch.cuda.synchronize()
+    rec["alternate_wins"] = int(cand.cpu().sum())
+    h = mapq.cpu().numpy()
+    rec["mapq_hist"] = [int((h == 0).sum()), int(((h >= 1) & (h < 30)).sum()), int(((h >= 30) & (h < 60)).sum()),
+                        int((h == 60).sum())]
+    rec["select_ms"] = timed(select_launch)
+
+    def restore():
+        with torch.cuda.stream(st):
+            score.copy_(score0)
+
+    def restore_select():
+        # candidate 0's scores put back: the same alternates win again and their rows are moved again
+        restore()
+        select_launch()
+
+    rec["restore_ms"] = timed(restore)
+    rec["restore_select_ms"] = timed(restore_select)
+    rec["select_moving_ms"] = round(rec["restore_select_ms"] - rec["restore_ms"], 4)
+    torch.cuda.synchronize()
+    rec["alternate_wins_moving"] = int(cand.cpu().sum())
+    for name, sym in (("cand_waves_per_cu", "_ZN3msw29seed_candidates_blocks_per_cuEj"),):
+        fn = getattr(lib(), sym, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_uint32]
+            rec[name] = int(fn(args.cap))
     get = getattr(lib(), "_ZN3msw18seed_blocks_per_cuEj", None)      # the library's occupancy query (C++ symbol)
     if get is not None:
         get.restype, get.argtypes = ctypes.c_int, [ctypes.c_uint32]
