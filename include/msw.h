@@ -597,6 +597,110 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
                   const msw_read_batch_t* batch, int both, const msw_seed_params_t* params, uint32_t sep,
                   msw_out_t* out, uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint64_t chunk_pairs);
 
+/* Pileup: per genome base, what the reads aligned over it show.
+ *
+ * Everything is integers and bytes, so a plain restatement
+ * (tests/pileup_oracle.py) can be compared value for value.
+ *
+ * Counts.  counts[glen][8], uint32, one row per genome base:
+ *   0..3  the aligned read byte is A, C, G, T (upper case only: the k-mer
+ *         codes of "Placing reads")
+ *   4     the aligned read byte is anything else (N, lower case, 0)
+ *   5     the base is deleted in the read (a column of a D run)
+ *   6     an I run follows this base: +1 per run, at g - 1, g being the genome
+ *         coordinate at which the walk stands when it meets the run
+ *   7     the columns of M runs that come from strand-1 reads (a subset of 0..4)
+ * depth(pos) is the sum of channels 0..5.
+ *
+ * Which reads count.  Read p of a batch counts when ref_pos[p] >= 0,
+ * nm[p] >= 0 (an overflowed trace has no ops), cigar_off[p + 1] > cigar_off[p]
+ * and, where a mapq array is given, mapq[p] >= min_mapq.  In the device form a
+ * read whose ops end past aln->cigar_cap does not count either.  A read that
+ * counts adds 1 to reads_used, every other read 1 to reads_skipped.
+ *
+ * The walk.  i = 0 and g = ref_pos[p]; the packed ops
+ * cigar[cigar_off[p] .. cigar_off[p + 1]) in order:
+ *   S len  i += len;
+ *   M len  column k of [0, len) counts when 0 <= g + k < glen and
+ *          i + k < read_len[p]: its channel is the code of rows[p][i + k], and
+ *          channel 7 gets +1 too when strand != NULL and strand[p] != 0; then
+ *          i += len, g += len;
+ *   I len  channel 6 at g - 1 when 0 <= g - 1 < glen; then i += len;
+ *   D len  channel 5 at g + k for the k of [0, len) with 0 <= g + k < glen;
+ *          then g += len;
+ *   any other op code is skipped without effect.
+ * rows are the rows the CIGARs refer to: the oriented slab after a both-strands
+ * call, the reads themselves otherwise.  The column rules make every access
+ * in-bounds for any records (read_len[p] <= row_stride is the caller's), not
+ * only for what msw_aln_pack_device wrote.
+ *
+ * Summary of finished counts for a min_depth >= 1: covered = the positions
+ * with depth > 0; depth_sum; max_depth; minority_ref = the positions with
+ * depth >= min_depth and 2 * counts[pos][code(genome[pos])] < depth (the code
+ * of a genome byte that is not upper-case ACGT is 4).
+ *
+ * The result is a function of the set of records alone: it is bit-reproducible
+ * whatever order the batches and the GPU's atomics ran in.
+ *
+ * State: about 44 bytes of device memory per genome base (the 32-byte row, two
+ * 4-byte difference arrays and a 4-byte mismatch count), so
+ * 176 MB for a 4 Mbase genome.  A pileup belongs to the context of its genome
+ * and is destroyed before it. */
+typedef struct msw_pileup msw_pileup;
+typedef struct {
+    uint64_t covered;
+    uint64_t depth_sum;
+    uint64_t minority_ref;
+    uint64_t reads_used;
+    uint64_t reads_skipped;
+    uint32_t max_depth;
+    uint32_t reserved;
+} msw_pileup_summary_t;
+
+/* An empty pileup over `genome` (the state is zeroed); synchronous.
+ * MSW_E_NOMEM when the state cannot be allocated. */
+int msw_pileup_create(msw_ctx* ctx, const msw_genome* genome, msw_pileup** out);
+void msw_pileup_destroy(msw_pileup* pile);
+
+/* Adds the records of n reads.  Device arrays: rows[n][row_stride] with
+ * read_len as above, aln->ref_pos / nm / cigar_off / cigar / cigar_cap as
+ * msw_aln_pack_device wrote them (aln->n_overflow is not read); strand and
+ * mapq may be NULL.  Enqueued on `stream` (NULL = the context's compute
+ * stream), no host synchronisation; adds on several streams may run at once.
+ * n > 2^31 - 1 is MSW_E_RANGE, min_mapq > 255 too; after msw_pileup_finish
+ * MSW_E_INVALID. */
+int msw_pileup_add_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
+                          uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                          const uint8_t* mapq, uint32_t min_mapq, void* stream);
+
+/* The same from host memory, synchronous, in chunks of `chunk_reads` (0 =
+ * 65536).  `reads` are the reads AS GIVEN to msw_align_reads_strands or
+ * msw_map_reads, and `strand` the bytes that call returned: the reverse
+ * complement of a strand-1 read is taken on the GPU.  With strand == NULL the
+ * rows are what the CIGARs refer to, as in the device form.  aln->cigar_off
+ * must not decrease and the ops of every read must lie inside aln->cigar_cap,
+ * else MSW_E_INVALID. */
+int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len,
+                   uint32_t read_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                   const uint8_t* mapq, uint32_t min_mapq, uint64_t chunk_reads);
+
+/* Folds the state into the counts, once, enqueued on `stream`: every add must
+ * have been enqueued on that stream or have finished.  Afterwards both add
+ * forms return MSW_E_INVALID; a second finish is a no-op. */
+int msw_pileup_finish(msw_ctx* ctx, msw_pileup* pile, void* stream);
+
+/* The finished counts into host_out[glen][8]; synchronous (it waits for the
+ * finish).  Before msw_pileup_finish: MSW_E_INVALID. */
+int msw_pileup_counts(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out);
+/* The counts on the device: channel ch of position pos is
+ * (*counts)[pos * *pos_stride + ch * *ch_stride] (rows of eight: 8 and 1).
+ * Valid at any time; the values are final once the finish has run. */
+int msw_pileup_counts_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** counts, uint64_t* pos_stride,
+                             uint64_t* ch_stride);
+/* The summary above, computed on the GPU; synchronous, only after
+ * msw_pileup_finish (else MSW_E_INVALID); min_depth == 0 is MSW_E_INVALID. */
+int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_pileup_summary_t* out);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

@@ -35,6 +35,8 @@ EXPORTED = (
     "msw_revcomp_device", "msw_align_reads_strands_device", "msw_align_reads_strands",
     "msw_index_create", "msw_index_destroy", "msw_index_info", "msw_seed_reads_device", "msw_seed_reads",
     "msw_seed_candidates_device", "msw_seed_candidates", "msw_mapq_select_device", "msw_map_reads",
+    "msw_pileup_create", "msw_pileup_destroy", "msw_pileup_add_device", "msw_pileup_add", "msw_pileup_finish",
+    "msw_pileup_counts", "msw_pileup_counts_device", "msw_pileup_summary",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -115,6 +117,12 @@ class MapqT(ctypes.Structure):
     _fields_ = [("mapq", ctypes.c_void_p), ("sub_score", ctypes.c_void_p), ("cand", ctypes.c_void_p)]
 
 
+class PileupSummaryT(ctypes.Structure):
+    _fields_ = [("covered", ctypes.c_uint64), ("depth_sum", ctypes.c_uint64), ("minority_ref", ctypes.c_uint64),
+                ("reads_used", ctypes.c_uint64), ("reads_skipped", ctypes.c_uint64), ("max_depth", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 class DevReadsT(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_void_p), ("read_len", ctypes.c_void_p), ("pos", ctypes.c_void_p),
                 ("read_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("first_read", ctypes.c_uint64),
@@ -186,6 +194,17 @@ def _declare(L):
         "msw_map_reads": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.POINTER(ReadBatchT), I,
                               ctypes.POINTER(SeedParamsT), ctypes.c_uint32, ctypes.POINTER(OutT), P,
                               ctypes.POINTER(AlnT), ctypes.POINTER(MapqT), ctypes.c_uint64]),
+        "msw_pileup_create": (I, [P, P, ctypes.POINTER(P)]),
+        "msw_pileup_destroy": (None, [P]),
+        "msw_pileup_add_device": (I, [P, P, P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(AlnT), P, P,
+                                      ctypes.c_uint32, P]),
+        "msw_pileup_add": (I, [P, P, P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(AlnT), P, P,
+                               ctypes.c_uint32, ctypes.c_uint64]),
+        "msw_pileup_finish": (I, [P, P, P]),
+        "msw_pileup_counts": (I, [P, P, P]),
+        "msw_pileup_counts_device": (I, [P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_pileup_summary": (I, [P, P, ctypes.c_uint32, ctypes.POINTER(PileupSummaryT)]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

@@ -26,8 +26,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, AlnT, BatchT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, ReadBatchT,
-                   ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
+from ._lib import (MSW_E_INVALID, AlnT, BatchT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PileupSummaryT,
+                   ReadBatchT, ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
 GPU_MAX_WORK_GROUPS = 1_000_000     # gpu.rs:10
@@ -526,6 +526,13 @@ class Context:
                                             chunk_pairs=chunk_pairs)
         return self.align_reads_trace(genome, reads, read_len, win_pos, win_len, scoring, chunk_pairs=chunk_pairs)
 
+    # -- pileup (include/msw.h, "Pileup") -----------------------------------------------
+    def pileup(self, genome: "Genome") -> "Pileup":
+        """An empty pileup over a resident genome (msw_pileup_create): per
+        base the allele, deletion, insertion and reverse-strand counts of the
+        alignment records added to it."""
+        return Pileup(self, genome)
+
     # -- candidates and mapping quality (include/msw.h) ---------------------------------
     def _map_reads_mapq(self, genome, index, reads, read_len, scoring, both, window, band, cap, step, min_votes,
                         chunk_pairs, sep):
@@ -879,6 +886,113 @@ class Index:
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:
             lib().msw_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Pileup:
+    """Per-base counts of what aligned reads show (msw_pileup_*; include/msw.h,
+    "Pileup"): ``counts()[pos]`` is A, C, G, T, other, deleted, insertions
+    after, reverse-strand columns.  Add records, ``finish()`` once, then read
+    ``counts()`` and ``summary()``."""
+
+    CHANNELS = 8
+
+    def __init__(self, ctx: Context, genome: Genome):
+        h = ctypes.c_void_p()
+        check(lib().msw_pileup_create(ctx.handle, genome.handle, ctypes.byref(h)))
+        self._h = h
+        self.ctx = ctx        # keeps the context and the genome alive for as long as the pileup
+        self.genome = genome
+        self._glen = len(genome)
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        if self._h is None:
+            raise MswError(MSW_E_INVALID, "pileup is closed")
+        return self._h
+
+    def add(self, reads: np.ndarray, read_len: np.ndarray, ref_pos: np.ndarray, nm: np.ndarray, cigars,
+            strand=None, mapq=None, min_mapq: int = 0, chunk_reads: int = 0) -> None:
+        """Add the records of a host batch (msw_pileup_add): ``reads`` and
+        ``read_len`` as they went into :meth:`Context.map_reads`,
+        :meth:`Context.align_reads_strands` (``trace=True``) or
+        :meth:`Context.align_reads_trace`, and ``ref_pos``, ``nm``, ``cigars``
+        (and ``strand``, ``mapq``) as they came back.  With ``strand`` the
+        reverse complement of a strand-1 read is taken on the GPU; without it
+        the rows are what the CIGARs refer to.  With ``mapq``, reads below
+        ``min_mapq`` are skipped."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        ref_pos = np.ascontiguousarray(ref_pos, dtype=np.int64)
+        nm = np.ascontiguousarray(nm, dtype=np.int32)
+        B = reads.shape[0]
+        if not (read_len.shape[0] == ref_pos.shape[0] == nm.shape[0] == len(cigars) == B):
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        off = np.zeros(B + 1, np.uint32)
+        off[1:] = np.cumsum([0 if c is None else len(c) for c in cigars], dtype=np.uint64)
+        parts = [np.asarray(c, np.uint32) for c in cigars if c is not None and len(c)]
+        cig = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1, np.uint32), dtype=np.uint32)
+        opt = {}
+        for name, a in (("strand", strand), ("mapq", mapq)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint8)
+                if a.shape[0] != B:
+                    raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+            opt[name] = a
+        aln = AlnT(_ptr(ref_pos) or None, _ptr(nm) or None, _ptr(off), _ptr(cig), int(off[B]), None)
+        check(lib().msw_pileup_add(self.ctx.handle, self.handle, _ptr(reads) if reads.size else None,
+                                   _ptr(read_len) if B else None, reads.shape[1] if reads.ndim == 2 else 0, B,
+                                   ctypes.byref(aln), _ptr(opt["strand"]) if B else None,
+                                   _ptr(opt["mapq"]) if B else None, min_mapq, chunk_reads))
+
+    def add_device(self, rows_ptr: int, read_len_ptr: int, row_stride: int, n: int, ref_pos_ptr: int, nm_ptr: int,
+                   cigar_off_ptr: int, cigar_ptr: int, cigar_cap: int, strand_ptr: int = 0, mapq_ptr: int = 0,
+                   min_mapq: int = 0, stream: int = 0) -> None:
+        """Enqueue the records of n device-resident reads (raw device
+        pointers, the arrays msw_aln_pack_device wrote) on ``stream``
+        (msw_pileup_add_device).  ``rows_ptr``: the rows the CIGARs refer to."""
+        aln = AlnT(ref_pos_ptr or None, nm_ptr or None, cigar_off_ptr or None, cigar_ptr or None, cigar_cap, None)
+        check(lib().msw_pileup_add_device(self.ctx.handle, self.handle, ctypes.c_void_p(rows_ptr or None),
+                                          ctypes.c_void_p(read_len_ptr or None), row_stride, n, ctypes.byref(aln),
+                                          ctypes.c_void_p(strand_ptr or None), ctypes.c_void_p(mapq_ptr or None),
+                                          min_mapq, ctypes.c_void_p(stream or None)))
+
+    def finish(self, stream: int = 0) -> None:
+        """Fold the state into the counts (msw_pileup_finish); afterwards the
+        pileup takes no more reads.  A second call does nothing."""
+        check(lib().msw_pileup_finish(self.ctx.handle, self.handle, ctypes.c_void_p(stream or None)))
+
+    def counts(self) -> np.ndarray:
+        """uint32[glen][8] on the host (msw_pileup_counts); after finish()."""
+        out = np.empty((self._glen, self.CHANNELS), np.uint32)
+        check(lib().msw_pileup_counts(self.ctx.handle, self.handle, _fresh_ptr(out) or None))
+        return out
+
+    def counts_device(self):
+        """(device pointer, position stride, channel stride) in uint32 words
+        (msw_pileup_counts_device)."""
+        ptr, ps, cs = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().msw_pileup_counts_device(self.ctx.handle, self.handle, ctypes.byref(ptr), ctypes.byref(ps),
+                                             ctypes.byref(cs)))
+        return int(ptr.value or 0), int(ps.value), int(cs.value)
+
+    def summary(self, min_depth: int = 1) -> dict:
+        """covered, depth_sum, max_depth, minority_ref, reads_used and
+        reads_skipped of the finished counts (msw_pileup_summary)."""
+        s = PileupSummaryT()
+        check(lib().msw_pileup_summary(self.ctx.handle, self.handle, min_depth, ctypes.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("covered", "depth_sum", "max_depth", "minority_ref", "reads_used",
+                                                "reads_skipped")}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            lib().msw_pileup_destroy(self._h)
             self._h = None
 
     def __del__(self):

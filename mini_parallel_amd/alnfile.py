@@ -187,3 +187,53 @@ def read_alignments(path) -> Alignments:
     cigars.n_cigar = rec["n_ops"].astype(np.int32)
     return Alignments(rec["ref_pos"].astype(np.int64), rec["score"].astype(np.int32), rec["nm"].astype(np.int32),
                       rec["end_i"].astype(np.int16), rec["end_j"].astype(np.int16), cigars, mapq, sub, strand)
+
+
+# The ``.mpu`` file of ``rustseq_mini --full-wgs --pileup-out``,
+# little-endian: a 32-byte header -- "MSWPILE1", u32 version = 1, u32 channels =
+# 8, u64 genome length, u64 reads_used -- then genome length x 8 u32 counts
+# (include/msw.h, "Pileup").  Dense: 32 bytes per genome base.
+PILEUP_MAGIC = b"MSWPILE1"
+PILEUP_VERSION = 1
+PILEUP_CHANNELS = 8
+PILEUP_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("channels", "<u4"), ("glen", "<u8"),
+                          ("reads_used", "<u8")])
+assert PILEUP_HEADER.itemsize == 32
+
+
+def write_pileup(path, counts, reads_used: int) -> None:
+    """Write uint32 ``counts[glen][8]`` and the number of reads behind them."""
+    counts = np.asarray(counts)
+    if counts.ndim != 2 or counts.shape[1] != PILEUP_CHANNELS:
+        raise ValueError(f"counts must be [glen][{PILEUP_CHANNELS}]")
+    if counts.size and (counts.min() < 0 or counts.max() > 0xFFFFFFFF):
+        raise ValueError("a count does not fit 32 bits")
+    head = np.zeros(1, PILEUP_HEADER)
+    head["magic"], head["version"], head["channels"] = PILEUP_MAGIC, PILEUP_VERSION, PILEUP_CHANNELS
+    head["glen"], head["reads_used"] = counts.shape[0], int(reads_used)
+    with open(path, "wb") as f:
+        f.write(head.tobytes())
+        f.write(np.ascontiguousarray(counts, dtype="<u4").tobytes())
+
+
+def read_pileup(path):
+    """-> (counts uint32[glen][8], reads_used).  Raises ValueError on a bad
+    magic, version or channel count, and on a size that does not match the
+    header's genome length (truncated, or bytes after the counts)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < PILEUP_HEADER.itemsize:
+        raise ValueError(f"{path}: truncated header")
+    head = np.frombuffer(data, PILEUP_HEADER, 1)[0]
+    if bytes(head["magic"]) != PILEUP_MAGIC:
+        raise ValueError(f"{path}: bad magic")
+    if int(head["version"]) != PILEUP_VERSION:
+        raise ValueError(f"{path}: version {int(head['version'])}, expected {PILEUP_VERSION}")
+    if int(head["channels"]) != PILEUP_CHANNELS:
+        raise ValueError(f"{path}: {int(head['channels'])} channels, expected {PILEUP_CHANNELS}")
+    glen = int(head["glen"])
+    want = PILEUP_HEADER.itemsize + glen * PILEUP_CHANNELS * 4
+    if len(data) != want:
+        raise ValueError(f"{path}: {len(data)} bytes, the header's genome length {glen} asks for {want}")
+    counts = np.frombuffer(data, "<u4", glen * PILEUP_CHANNELS, PILEUP_HEADER.itemsize)
+    return counts.reshape(glen, PILEUP_CHANNELS).astype(np.uint32), int(head["reads_used"])

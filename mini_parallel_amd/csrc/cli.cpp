@@ -94,6 +94,15 @@ void usage() {
         "                               and the other candidate's score per read\n"
         "      --seed-sep N             --mapq: least distance between the two candidates' diagonals, at least\n"
         "                               --seed-band (default 0: the read's window length)\n"
+        "      --pileup-out PATH        --alignments-out: also write the pileup of the run's records, per genome\n"
+        "                               base the reads showing A, C, G, T or something else, deleting it,\n"
+        "                               inserting after it, and the reverse-strand share (one dense .mpu file,\n"
+        "                               32 bytes per base, DESIGN.md 4.14).  One pileup covers one run: not with\n"
+        "                               a checkpoint that already lists completed files\n"
+        "      --pileup-min-mapq N      --pileup-out with --mapq: reads below this MAPQ do not count, 0..60\n"
+        "                               (default 0)\n"
+        "      --pileup-min-depth N     --pileup-out: least depth of a position in the summary's minority_ref\n"
+        "                               (default 4)\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -139,6 +148,9 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--seed-band") a.seed_band = atoi(v().c_str());
         else if (s == "--mapq") a.mapq = true;
         else if (s == "--seed-sep") { a.seed_sep = atoi(v().c_str()); a.has_seed_sep = true; }
+        else if (s == "--pileup-out") a.pileup_out = v();
+        else if (s == "--pileup-min-mapq") { a.pileup_min_mapq = atoi(v().c_str()); a.has_pileup_min_mapq = true; }
+        else if (s == "--pileup-min-depth") { a.pileup_min_depth = atoi(v().c_str()); a.has_pileup_min_depth = true; }
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -178,6 +190,15 @@ Args parse_args(int argc, char** argv) {
     if (a.has_seed_sep && !a.mapq) die("error: --seed-sep needs --mapq");
     if (a.mapq && a.seed_sep != 0 && a.seed_sep < a.seed_band)
         die("error: --seed-sep must be 0 (the window length) or at least --seed-band");
+    // refused here, before any file is opened, like --mapq
+    if (!a.pileup_out.empty() && a.alignments_out.empty())
+        die("error: --pileup-out needs --alignments-out (the records are made there)");
+    if (a.has_pileup_min_mapq && (a.pileup_out.empty() || !a.mapq))
+        die("error: --pileup-min-mapq needs --pileup-out and --mapq");
+    if (a.has_pileup_min_mapq && (a.pileup_min_mapq < 0 || a.pileup_min_mapq > 60))
+        die("error: --pileup-min-mapq must be 0..60");
+    if (a.has_pileup_min_depth && a.pileup_out.empty()) die("error: --pileup-min-depth needs --pileup-out");
+    if (a.has_pileup_min_depth && a.pileup_min_depth < 1) die("error: --pileup-min-depth must be at least 1");
     return a;
 }
 
@@ -295,6 +316,8 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
                std::to_string(a.seed_band);
     // nor does a run with a second candidate and MAPQ resume one without, or one with another separation
     if (a.mapq) key += "|mapq|" + std::to_string(a.seed_sep);
+    // a pileup covers the files of one run: its run never resumes one without, or one with another threshold
+    if (!a.pileup_out.empty()) key += "|pileup|" + std::to_string(a.pileup_min_mapq);
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -453,6 +476,15 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
         j << ", \"mapq\": true, \"seed_sep\": " << a.seed_sep << ", \"mapq_histogram\": {\"0\": " << rep.mapq_hist[0]
           << ", \"1-29\": " << rep.mapq_hist[1] << ", \"30-59\": " << rep.mapq_hist[2] << ", \"60\": " << rep.mapq_hist[3]
           << "}";
+    // --pileup-out only
+    if (rep.pileup.on) {
+        const PileupReport& p = rep.pileup;
+        j << ", \"pileup\": {\"path\": \"" << json_escape(a.pileup_out) << "\", \"min_mapq\": " << a.pileup_min_mapq
+          << ", \"min_depth\": " << a.pileup_min_depth << ", \"reads_used\": " << p.reads_used
+          << ", \"reads_skipped\": " << p.reads_skipped << ", \"covered\": " << p.covered
+          << ", \"depth_sum\": " << p.depth_sum << ", \"max_depth\": " << p.max_depth
+          << ", \"minority_ref\": " << p.minority_ref << ", \"pileup_ms\": " << p.ms << "}";
+    }
     j
       << ", \"inflate_bytes_in\": " << rep.gz_in << ", \"inflate_bytes_out\": " << rep.gz_out
       << ", \"reads_per_second\": " << reads / secs << ", \"t_main_unix_ns\": " << in.t_main_ns
@@ -475,6 +507,11 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
     ck.path = a.checkpoint_dir + "/checkpoint_" + ck.run_id + ".json";
     ck.total_files = files.size();
     if (ck.load()) printf("Resuming run %s from %s\n", ck.run_id.c_str(), ck.path.c_str());
+    if (!a.pileup_out.empty())
+        for (const auto& kv : ck.files)
+            if (kv.second.completed)
+                die("error: --pileup-out covers the files of one run, but " + ck.path +
+                    " already lists a completed file: remove the checkpoint to run all files again");
     const std::vector<Device> workers = worker_devices(devices, a.num_gpus);
     const WgsReport rep = run_full_wgs(a, workers, files, gidx, n_lane_files, ck, ref);
     WgsTotals tot;
@@ -494,6 +531,11 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
     if (rep.mapq)
         printf("MAPQ: %llu reads at 0, %llu at 1-29, %llu at 30-59, %llu at 60\n", rep.mapq_hist[0], rep.mapq_hist[1],
                rep.mapq_hist[2], rep.mapq_hist[3]);
+    if (rep.pileup.on)
+        printf("Pileup: %llu reads used, %llu skipped, %llu bases covered, depth sum %llu, max depth %llu, %llu "
+               "positions with the reference base in the minority at depth >= %d, %.1f ms -> %s\n",
+               rep.pileup.reads_used, rep.pileup.reads_skipped, rep.pileup.covered, rep.pileup.depth_sum,
+               rep.pileup.max_depth, rep.pileup.minority_ref, a.pileup_min_depth, rep.pileup.ms, a.pileup_out.c_str());
     printf("Wall time: %.2f s", rep.wall_ms / 1000.0);
     if (rep.cells) printf(", %.1f GCUPS end-to-end", rep.cells / (rep.wall_ms * 1e6));
     printf("\n");

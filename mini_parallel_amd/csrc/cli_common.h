@@ -81,6 +81,11 @@ struct Args {
     // candidate's diagonal from the first (0: the read's window length)
     bool mapq = false, has_seed_sep = false;
     int seed_sep = 0;
+    // --pileup-out: the per-base allele counts of the run's records (one .mpu file); reads below
+    // --pileup-min-mapq do not count, --pileup-min-depth is the summary's least depth
+    std::string pileup_out;
+    bool has_pileup_min_mapq = false, has_pileup_min_depth = false;
+    int pileup_min_mapq = 0, pileup_min_depth = 4;
     long chunk_size = 1, num_files = -1;
     std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out, alignments_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;

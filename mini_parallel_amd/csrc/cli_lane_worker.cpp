@@ -18,6 +18,7 @@ struct LaneEnv {
     const Args* a;
     uint64_t batch;
     int gi;
+    msw_pileup* pile;  // --pileup-out: this worker's pileup, else null
 };
 
 // The pinned result block of a set: score i32 | ei i16 | ej i16 | rlen u16 | wlen u16, each [batch]
@@ -135,7 +136,12 @@ struct AlnSet {
     // traced and packed once more at the exact stride, so the file's
     // alignments are always complete; then the packed ops actually used are
     // copied back and set_fence covers everything settle reads.
-    void finish(const LaneEnv& e, const msw_out_t& o, uint64_t n, FileState& f, uint64_t* set_fence) {
+    // With --pileup-out the settled records go into the worker's pileup
+    // here, on the batch's stream: after the retrace and the ops growth, so
+    // every read has its final ops exactly once, and before the ops copy-back
+    // (strand / mapq: the set's bytes on the device, or null).
+    void finish(const LaneEnv& e, const msw_out_t& o, uint64_t n, FileState& f, uint64_t* set_fence,
+                const uint8_t* strand, const uint8_t* mapq) {
         if (!pending) return;
         pending = false;
         ok = false;
@@ -155,6 +161,11 @@ struct AlnSet {
                 continue;
             }
             break;
+        }
+        if (good && e.pile) {
+            const msw_aln_t al{d_ref, d_nm, d_off, d_ops, ops_cap, d_off + e.batch + 1};
+            good = msw_pileup_add_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al, strand, mapq,
+                                         (uint32_t)e.a->pileup_min_mapq, stream) == MSW_OK;
         }
         if (good) {
             n_ops = h.off[n];
@@ -227,6 +238,7 @@ class LaneWorker {
     bool next_batch(size_t fi, void* stream, msw_dev_reads_t* d);
     void settle(ResultSet& r);
     void write_aln_block(ResultSet& r, FileState& f);
+    void collect_pileup();
     bool score(ResultSet& r, const msw_dev_reads_t& d, const int64_t* pos, bool alt, void* stream);
     bool submit(ResultSet& r, const msw_dev_reads_t& d, size_t fi, void* stream);
     int open_out(const std::string& dir, const FileState& f, const char* ext);
@@ -245,6 +257,7 @@ class LaneWorker {
     msw_scoring_t sc_;
     msw_genome* gen_ = nullptr;
     msw_index* idx_ = nullptr;  // --map
+    msw_pileup* pile_ = nullptr;  // --pileup-out
     msw_seed_params_t seed_{};
     LaneEnv env_;
     ResultSet res_[2];
@@ -305,7 +318,10 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     if (msw_ctx_prepare(ctx_.h, &sc_) != MSW_OK) die(std::string("GPU kernel load: ") + msw_last_error());
     const double t_kl = ms_since(tk0);
     const auto tres0 = Clock::now();
-    env_ = LaneEnv{ctx_.h, &sc_, gen_, &a_, batch_, gi_};
+    // --pileup-out: this worker's pileup of the genome just uploaded, before the clock
+    if (lanes_.pileup && msw_pileup_create(ctx_.h, gen_, &pile_) != MSW_OK)
+        die(std::string("GPU pileup error: ") + msw_last_error());
+    env_ = LaneEnv{ctx_.h, &sc_, gen_, &a_, batch_, gi_, pile_};
     if (aln_) aln_stride_ = (uint32_t)std::min(4480L, std::max(1L, atol(env_or("MSW_CLI_CIGAR_STRIDE", "16").c_str())));
     for (ResultSet& r : res_) {
         r.d_score = (int32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
@@ -436,7 +452,9 @@ bool LaneWorker::open_next(size_t* fi_out) {
 }
 
 void LaneWorker::finish_alignments(ResultSet& r) {
-    if (aln_ && r.live) r.aln.finish(env_, r.out(), r.n, *run_.st[r.fi], &r.fence);
+    if (aln_ && r.live)
+        r.aln.finish(env_, r.out(), r.n, *run_.st[r.fi], &r.fence, both_ ? r.d_strand : nullptr,
+                     mapq_ ? r.d_mapq : nullptr);
 }
 
 // The reader's next batch of file fi on `stream`; false (after reader_done)
@@ -472,6 +490,32 @@ void LaneWorker::write_aln_block(ResultSet& r, FileState& f) {
         fprintf(stderr, "  error writing alignments for %s\n", f.path.c_str());
         f.failed = true;
     }
+}
+
+// --pileup-out, after the clock has stopped: fold this worker's pileup (every
+// add has finished: both sets are settled), copy the counts out and add them
+// to the run's.
+void LaneWorker::collect_pileup() {
+    const size_t words = (size_t)msw_genome_length(gen_) * 8;
+    std::vector<uint32_t> mine(words);
+    msw_pileup_summary_t s;
+    const bool ok = msw_pileup_finish(ctx_.h, pile_, nullptr) == MSW_OK &&
+                    msw_pileup_counts(ctx_.h, pile_, mine.data()) == MSW_OK &&
+                    msw_pileup_summary(ctx_.h, pile_, 1, &s) == MSW_OK;
+    if (!ok) fprintf(stderr, "  GPU %d pileup error: %s\n", gi_, msw_last_error());
+    std::lock_guard<std::mutex> lk(lanes_.pile_mu);
+    if (!ok) {
+        lanes_.pile_failed = true;
+        return;
+    }
+    if (lanes_.pile_sum.empty()) {
+        lanes_.pile_sum.swap(mine);
+    } else {
+        uint32_t* sum = lanes_.pile_sum.data();
+        for (size_t k = 0; k < words; ++k) sum[k] += mine[k];
+    }
+    lanes_.pile_used += s.reads_used;
+    lanes_.pile_skipped += s.reads_skipped;
 }
 
 // host side of a finished batch: sums, cells, per-read records, then this
@@ -663,6 +707,7 @@ void LaneWorker::run() {
     settle(res_[cur_]);
     settle(res_[cur_ ^ 1]);
     run_.mark_done();
+    if (pile_) collect_pileup();
     msw_ctx_stats(ctx_.h, &lanes_.gstats[(size_t)wi_], 0);
     lanes_.gstats[(size_t)wi_].alg_bytes = alg_local_;
     // the reader, result sets, genome and context stay allocated:

@@ -230,7 +230,8 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
     const long long d = t_done_ns.load();
     rep.wall_ms = d ? std::chrono::duration<double, std::milli>(Clock::time_point(Clock::duration(d)) - t_all).count()
                     : total;
-    rep.teardown_ms = total - rep.wall_ms;
+    rep.pileup = pileup;
+    rep.teardown_ms = total - rep.wall_ms - pileup.ms;
     rep.cells = cells.load();
     rep.both_strands = a.both_strands;
     rep.reverse_reads = reverse_reads.load();
@@ -258,8 +259,49 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
 // ---------------------------------------------------------------------------
 LaneRun::LaneRun(WgsRun& run_, bool aln_, bool per_read_, bool both_, uint64_t batch_, int nworkers_)
     : run(run_), aln(aln_), per_read(per_read_), both(both_), batch(batch_), nworkers(nworkers_),
-      started(new std::atomic<int>[run_.st.size()]), gstats((size_t)nworkers_, msw_stats_t{}) {
+      started(new std::atomic<int>[run_.st.size()]), gstats((size_t)nworkers_, msw_stats_t{}),
+      pileup(!run_.a.pileup_out.empty()) {
     for (size_t i = 0; i < run.st.size(); ++i) started[i] = 0;
+}
+
+// --pileup-out, after the workers have joined: the summary of the summed
+// counts (include/msw.h, "Pileup") and the .mpu file -- a 32-byte header
+// ("MSWPILE1", u32 version 1, u32 channels 8, u64 genome length, u64
+// reads_used), then the rows.  The phase runs from the stop of the clock.
+static void write_pileup(WgsRun& run, LaneRun& lanes) {
+    const std::string& g = run.genome();
+    const uint64_t glen = g.size();
+    std::vector<uint32_t>& c = lanes.pile_sum;
+    if (lanes.pile_failed || c.size() != glen * 8) die("error: the pileup could not be read back from the GPUs");
+    PileupReport& p = run.pileup;
+    p.on = true;
+    p.reads_used = lanes.pile_used;
+    p.reads_skipped = lanes.pile_skipped;
+    const unsigned long long min_depth = (unsigned long long)run.a.pileup_min_depth;
+    for (uint64_t pos = 0; pos < glen; ++pos) {
+        const uint32_t* row = c.data() + pos * 8;
+        const unsigned long long depth = (unsigned long long)row[0] + row[1] + row[2] + row[3] + row[4] + row[5];
+        const char b = g[pos];
+        const int code = b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4;
+        p.covered += depth > 0;
+        p.depth_sum += depth;
+        p.max_depth = std::max(p.max_depth, depth);
+        p.minority_ref += depth >= min_depth && 2ull * row[code] < depth;
+    }
+    FILE* f = fopen(run.a.pileup_out.c_str(), "wb");
+    if (!f) die("error: cannot create " + run.a.pileup_out);
+    unsigned char head[32];
+    memcpy(head, "MSWPILE1", 8);
+    const uint32_t version = 1, channels = 8;
+    const uint64_t used = p.reads_used;
+    memcpy(head + 8, &version, 4);
+    memcpy(head + 12, &channels, 4);
+    memcpy(head + 16, &glen, 8);
+    memcpy(head + 24, &used, 8);
+    const bool ok = fwrite(head, 1, 32, f) == 32 && fwrite(c.data(), 4, c.size(), f) == c.size();
+    if (fclose(f) != 0 || !ok) die("error: writing " + run.a.pileup_out);
+    const long long d = run.t_done_ns.load();
+    p.ms = d ? std::chrono::duration<double, std::milli>(Clock::now() - Clock::time_point(Clock::duration(d))).count() : 0.0;
 }
 
 static WgsReport run_gpu_lanes(WgsRun& run, bool aln, bool per_read) {
@@ -283,6 +325,7 @@ static WgsReport run_gpu_lanes(WgsRun& run, bool aln, bool per_read) {
     for (int wi = 0; wi < lanes.nworkers; ++wi) workers.emplace_back(lane_worker, std::ref(lanes), wi);
     run.start_clock(lanes.nworkers);
     for (auto& t : workers) t.join();
+    if (lanes.pileup) write_pileup(run, lanes);
     return run.report(0, lanes.nworkers, lanes.gstats, true, lanes.gz_in.load(), lanes.gz_out.load());
 }
 

@@ -92,8 +92,17 @@ struct StartGate {
     }
 };
 
+// --pileup-out: the summary of the run's pileup and the time of its phase
+// (fold, copy-out, sum over the workers, summary, file), after the clock.
+struct PileupReport {
+    bool on = false;
+    unsigned long long reads_used = 0, reads_skipped = 0, covered = 0, depth_sum = 0, max_depth = 0, minority_ref = 0;
+    double ms = 0;
+};
+
 struct WgsReport {
     std::vector<FileCheckpoint> results;
+    PileupReport pileup;
     double wall_ms = 0;
     unsigned long long cells = 0;
     int readers = 0;
@@ -159,6 +168,7 @@ struct WgsRun {
     std::atomic<unsigned long long> reverse_reads{0};  // --both-strands: strand-1 reads
     std::atomic<unsigned long long> placed_reads{0};   // --map: reads with a window
     std::atomic<unsigned long long> mapq_hist[4] = {};  // --mapq: reads with MAPQ 0, 1-29, 30-59, 60
+    PileupReport pileup;  // --pileup-out: filled after the workers have joined
     StartGate gate;
     Clock::time_point t_setup, t_all;
     // the clock stops when the last worker has its last results on the host;
@@ -201,6 +211,12 @@ struct LaneRun {
     std::unique_ptr<std::atomic<int>[]> started;
     std::atomic<unsigned long long> gz_in{0}, gz_out{0};
     std::vector<msw_stats_t> gstats;  // per worker
+    // --pileup-out: the workers' finished counts [glen][8] summed on the host, and their read counters
+    const bool pileup;
+    std::mutex pile_mu;
+    std::vector<uint32_t> pile_sum;
+    unsigned long long pile_used = 0, pile_skipped = 0;
+    bool pile_failed = false;
 
     static constexpr size_t kNone = ~(size_t)0;
     LaneRun(WgsRun& run, bool aln, bool per_read, bool both, uint64_t batch, int nworkers);

@@ -313,6 +313,52 @@ hipError_t launch_aln_pack(const AlnParams& p, hipStream_t stream);
 // words).  No block waits for another: the levels are separate launches.
 hipError_t scan_in_place(uint32_t* data, uint64_t count, uint32_t* tmp, hipStream_t st);
 
+// Pileup (msw_pileup.hip; the contract is in include/msw.h, "Pileup").  The
+// state of one pileup and, for an add, one batch of records.  Channel ch of
+// position pos is counts[pos * pos_mul + ch * ch_mul]: rows of eight
+// (pos_mul 8, ch_mul 1) or eight planes (pos_mul 1, ch_mul glen).
+constexpr uint32_t kPileupReadSlots = 32;
+constexpr uint32_t kPileupReadSlotWords = 16;  // u64 words between two counters
+struct PileupParams {
+    const uint8_t* genome;
+    uint64_t glen;
+    uint32_t* counts;
+    uint64_t pos_mul, ch_mul;
+    uint32_t* d_all;          // [glen + 1] differences of the M-column depth, modulo 2^32
+    uint32_t* d_rev;          // [glen + 1] the same for strand-1 reads
+    uint32_t* mism;           // [glen] M columns whose read byte differs from the genome byte
+    // reads used / skipped: kPileupReadSlots slots of two counters, each counter on a 128-byte line of its own
+    // (counter c of slot s at reads[(s * 2 + c) * kPileupReadSlotWords]); a block adds to slot blockIdx % slots
+    unsigned long long* reads;
+    // the batch (launch_pileup_add only)
+    const uint8_t* rows;
+    const uint16_t* read_len;
+    uint64_t row_stride;
+    uint64_t n;
+    const int64_t* ref_pos;
+    const int32_t* nm;
+    const uint32_t* cigar_off;  // [n + 1]
+    const uint32_t* cigar;      // op k of the stream is cigar[k - cigar_base]
+    uint32_t cigar_base;        // reads whose ops start before it are skipped
+    uint64_t cigar_cap;         // reads whose ops end past it are skipped
+    const uint8_t* strand;      // or null
+    const uint8_t* mapq;        // or null
+    uint32_t min_mapq;
+    uint32_t orient;            // 1: the rows are the reads as given; a strand-1 row is read as its reverse complement
+};
+// u32 words of scan temporaries pileup_finish needs for a genome of glen bases
+uint64_t pileup_scan_tmp_words(uint64_t glen);
+hipError_t launch_pileup_add(const PileupParams& p, hipStream_t stream);
+// blocks per CU of pileup_add_kernel; the query loads the module
+int pileup_blocks_per_cu();
+// scans d_all and d_rev in place and folds them and mism into counts
+hipError_t launch_pileup_finish(const PileupParams& p, uint32_t* scan_tmp, hipStream_t stream);
+// stats[4] (device): covered, depth_sum, minority_ref, max_depth of finished counts
+hipError_t launch_pileup_summary(const PileupParams& p, uint32_t min_depth, unsigned long long* stats,
+                                 hipStream_t stream);
+// out[m][8] = the rows of positions [pos0, pos0 + m), whatever the layout
+hipError_t launch_pileup_rows(const PileupParams& p, uint64_t pos0, uint64_t m, uint32_t* out, hipStream_t stream);
+
 // Placing reads (msw_seed.hip; the contract is in include/msw.h).
 constexpr uint32_t kSeedMaxCap = 8192;      // keys one read's LDS array holds (32 KiB)
 constexpr uint32_t kSeedMaxOcc = 64;

@@ -88,6 +88,7 @@ struct Options {
     std::string wave_trace;       // MSW_WAVE_TRACE=file: per-block placement records
     uint64_t chunk = 65536;       // GPU_CHUNK_SIZE_READS: default pairs per staged chunk (aligner.rs:9-15)
     uint64_t gz_group_bytes = 1024ull << 20;  // MSW_GZ_GROUP_MB: output bytes per msw_bgzf_inflate launch
+    bool pileup_planes = false;   // MSW_PILEUP_PLANES=1: a pileup's device counts as eight planes, not rows of eight
 };
 
 Options read_options() {
@@ -120,6 +121,8 @@ Options read_options() {
     }
     const char* gz = getenv("MSW_GZ_GROUP_MB");
     if (gz && atoll(gz) > 0) o.gz_group_bytes = (uint64_t)atoll(gz) << 20;
+    const char* pp = getenv("MSW_PILEUP_PLANES");
+    o.pileup_planes = pp && *pp == '1';
     return o;
 }
 
@@ -3115,6 +3118,284 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
     if (d_ops) (void)hipFree(d_ops);
     if (rc) return rc;
     if (e != hipSuccess) return fail(MSW_E_DEVICE, "map reads: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
+// Pileup (include/msw.h, "Pileup"; the kernels: msw_pileup.hip).
+struct msw_pileup {
+    const msw_ctx* ctx = nullptr;  // identity only
+    int device = 0;
+    // one allocation: counts [glen][8] | the read counters' slots + stats u64[4] | d_all [glen + 1] | d_rev [glen + 1] |
+    // mism [glen] | the scan's block sums
+    uint8_t* d_state = nullptr;
+    msw::PileupParams p{};         // the state's part; an add fills in its batch
+    unsigned long long* d_stats = nullptr;
+    uint32_t* d_scan_tmp = nullptr;
+    bool finished = false;
+    hipEvent_t fin = nullptr;      // recorded behind the fold
+};
+
+static int check_pileup(const msw_ctx* ctx, const msw_pileup* pile) {
+    if (!ctx || !pile) return fail(MSW_E_INVALID, "ctx/pileup is NULL");
+    if (pile->ctx != ctx) return fail(MSW_E_INVALID, "pileup belongs to another context");
+    return MSW_OK;
+}
+
+int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
+    if (!ctx || !g || !out) return fail(MSW_E_INVALID, "ctx/genome/out is NULL");
+    *out = nullptr;
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    const uint64_t glen = g->len;
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    const uint64_t read_words = (uint64_t)msw::kPileupReadSlots * 2 * msw::kPileupReadSlotWords;
+    const uint64_t o_reads = (glen * 32 + 127) & ~(uint64_t)127, o_all = o_reads + (read_words + 16) * 8,
+                   o_rev = o_all + up16((glen + 1) * 4),
+                   o_mism = o_rev + up16((glen + 1) * 4), o_tmp = o_mism + up16(glen * 4),
+                   total = o_tmp + up16(msw::pileup_scan_tmp_words(glen) * 4) + 16;
+    msw_pileup* pile = new msw_pileup();
+    pile->ctx = ctx;
+    pile->device = ctx->device;
+    hipError_t e = hipMalloc((void**)&pile->d_state, total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete pile;
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the pileup of %llu bases: %s", (unsigned long long)total,
+                    (unsigned long long)glen, hipGetErrorString(e));
+    }
+    msw::PileupParams& p = pile->p;
+    p.genome = g->d_seq;
+    p.glen = glen;
+    p.counts = reinterpret_cast<uint32_t*>(pile->d_state);
+    const bool planes = ctx->opt.pileup_planes;
+    p.pos_mul = planes ? 1 : 8;
+    p.ch_mul = planes ? glen : 1;
+    p.reads = reinterpret_cast<unsigned long long*>(pile->d_state + o_reads);
+    pile->d_stats = p.reads + read_words;
+    p.d_all = reinterpret_cast<uint32_t*>(pile->d_state + o_all);
+    p.d_rev = reinterpret_cast<uint32_t*>(pile->d_state + o_rev);
+    p.mism = reinterpret_cast<uint32_t*>(pile->d_state + o_mism);
+    pile->d_scan_tmp = reinterpret_cast<uint32_t*>(pile->d_state + o_tmp);
+    // the kernels' code object, loaded here rather than inside the first add (HIP loads a module on first use)
+    (void)msw::pileup_blocks_per_cu();
+    e = hipEventCreateWithFlags(&pile->fin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(pile->d_state, 0, total, ctx->compute);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->compute);
+    if (e != hipSuccess) {
+        msw_pileup_destroy(pile);
+        return fail(MSW_E_DEVICE, "pileup state: %s", hipGetErrorString(e));
+    }
+    *out = pile;
+    return MSW_OK;
+}
+
+void msw_pileup_destroy(msw_pileup* pile) {
+    if (!pile) return;
+    (void)hipSetDevice(pile->device);
+    if (pile->fin) (void)hipEventDestroy(pile->fin);
+    if (pile->d_state) (void)hipFree(pile->d_state);
+    delete pile;
+}
+
+// the checks both add forms share; *go = false: nothing to do
+static int check_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
+                            uint32_t row_stride, uint64_t n, const msw_aln_t* aln, uint32_t min_mapq, bool* go) {
+    *go = false;
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!aln) return fail(MSW_E_INVALID, "aln is NULL");
+    if (pile->finished) return fail(MSW_E_INVALID, "pileup is finished: it takes no more reads");
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "pileup add: n > 2^31-1 in one call");
+    if (min_mapq > 255u) return fail(MSW_E_RANGE, "pileup add: min_mapq %u > 255", min_mapq);
+    if (n == 0) return MSW_OK;
+    if (!rows || !read_len) return fail(MSW_E_INVALID, "NULL array");
+    if (row_stride == 0) return fail(MSW_E_INVALID, "row_stride is 0");
+    if (!aln->ref_pos || !aln->nm || !aln->cigar_off) return fail(MSW_E_INVALID, "NULL array in aln");
+    if (aln->cigar_cap && !aln->cigar) return fail(MSW_E_INVALID, "cigar is NULL with cigar_cap > 0");
+    *go = true;
+    return MSW_OK;
+}
+
+int msw_pileup_add_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
+                          uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                          const uint8_t* mapq, uint32_t min_mapq, void* stream) {
+    int rc;
+    bool go;
+    if ((rc = check_pileup_add(ctx, pile, rows, read_len, row_stride, n, aln, min_mapq, &go)) || !go) return rc;
+    if ((rc = set_device(ctx))) return rc;
+    msw::PileupParams p = pile->p;
+    p.rows = rows;
+    p.read_len = read_len;
+    p.row_stride = row_stride;
+    p.n = n;
+    p.ref_pos = aln->ref_pos;
+    p.nm = aln->nm;
+    p.cigar_off = aln->cigar_off;
+    p.cigar = aln->cigar;
+    p.cigar_cap = aln->cigar_cap;
+    p.strand = strand;
+    p.mapq = mapq;
+    p.min_mapq = min_mapq;
+    HIP_TRY(msw::launch_pileup_add(p, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
+                   uint64_t n, const msw_aln_t* aln, const uint8_t* strand, const uint8_t* mapq, uint32_t min_mapq,
+                   uint64_t chunk_reads) {
+    int rc;
+    bool go;
+    if ((rc = check_pileup_add(ctx, pile, reads, read_len, read_stride, n, aln, min_mapq, &go)) || !go) return rc;
+    const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
+    // the offsets decide what is uploaded: they must be a prefix sum inside the capacity
+    uint64_t max_ops = 0;
+    for (uint64_t lo = 0; lo < n; lo += chunk) {
+        const uint64_t hi = std::min(n, lo + chunk);
+        for (uint64_t k = lo; k < hi; ++k)
+            if (aln->cigar_off[k + 1] < aln->cigar_off[k])
+                return fail(MSW_E_INVALID, "pileup add: cigar_off decreases at read %llu", (unsigned long long)k);
+        max_ops = std::max<uint64_t>(max_ops, aln->cigar_off[hi] - aln->cigar_off[lo]);
+    }
+    if (aln->cigar_off[n] > aln->cigar_cap)
+        return fail(MSW_E_INVALID, "pileup add: the reads hold %u ops, cigar_cap is %llu", aln->cigar_off[n],
+                    (unsigned long long)aln->cigar_cap);
+    for (uint64_t k = 0; k < n; ++k)
+        if (read_len[k] > read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    // [ref i64 | nm i32 | off u32 [c + 1] | ops | rlen u16 | strand | mapq | rows]
+    const size_t rs = read_stride;
+    const size_t o_nm = chunk * 8, o_off = o_nm + chunk * 4, o_ops = up16(o_off + (chunk + 1) * 4),
+                 o_rl = up16(o_ops + max_ops * 4), o_st = up16(o_rl + chunk * 2), o_mq = up16(o_st + chunk),
+                 o_rows = up16(o_mq + chunk), total = o_rows + chunk * rs + 16;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total, hipGetErrorString(e));
+    }
+    hipStream_t st = ctx->compute;
+    msw::PileupParams p = pile->p;
+    p.rows = d + o_rows;
+    p.read_len = reinterpret_cast<const uint16_t*>(d + o_rl);
+    p.row_stride = rs;
+    p.ref_pos = reinterpret_cast<const int64_t*>(d);
+    p.nm = reinterpret_cast<const int32_t*>(d + o_nm);
+    p.cigar_off = reinterpret_cast<const uint32_t*>(d + o_off);
+    p.cigar = reinterpret_cast<const uint32_t*>(d + o_ops);
+    p.cigar_cap = aln->cigar_cap;
+    p.strand = strand ? d + o_st : nullptr;
+    p.mapq = mapq ? d + o_mq : nullptr;
+    p.min_mapq = min_mapq;
+    p.orient = strand ? 1u : 0u;
+    for (uint64_t lo = 0; lo < n && e == hipSuccess; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        auto up = [&](size_t at, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, st);
+        };
+        const uint32_t o0 = aln->cigar_off[lo], o1 = aln->cigar_off[lo + c];
+        up(0, aln->ref_pos + lo, c * 8);
+        up(o_nm, aln->nm + lo, c * 4);
+        up(o_off, aln->cigar_off + lo, (c + 1) * 4);
+        up(o_ops, aln->cigar + o0, (size_t)(o1 - o0) * 4);
+        up(o_rl, read_len + lo, c * 2);
+        if (strand) up(o_st, strand + lo, c);
+        if (mapq) up(o_mq, mapq + lo, c);
+        up(o_rows, reads + lo * rs, c * rs);
+        p.n = c;
+        p.cigar_base = o0;
+        if (e == hipSuccess) e = msw::launch_pileup_add(p, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);  // the buffers are the next chunk's
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup add: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
+int msw_pileup_finish(msw_ctx* ctx, msw_pileup* pile, void* stream) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (pile->finished) return MSW_OK;
+    if ((rc = set_device(ctx))) return rc;
+    hipStream_t st = call_stream(ctx, stream);
+    HIP_TRY(msw::launch_pileup_finish(pile->p, pile->d_scan_tmp, st));
+    HIP_TRY(hipEventRecord(pile->fin, st));
+    pile->finished = true;
+    return MSW_OK;
+}
+
+int msw_pileup_counts_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** counts, uint64_t* pos_stride,
+                             uint64_t* ch_stride) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!counts || !pos_stride || !ch_stride) return fail(MSW_E_INVALID, "NULL output");
+    *counts = pile->p.counts;
+    *pos_stride = pile->p.pos_mul;
+    *ch_stride = pile->p.ch_mul;
+    return MSW_OK;
+}
+
+int msw_pileup_counts(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!pile->finished) return fail(MSW_E_INVALID, "pileup counts before msw_pileup_finish");
+    const uint64_t glen = pile->p.glen;
+    if (glen == 0) return MSW_OK;
+    if (!host_out) return fail(MSW_E_INVALID, "host_out is NULL");
+    if ((rc = set_device(ctx))) return rc;
+    HIP_TRY(hipEventSynchronize(pile->fin));
+    hipStream_t st = ctx->compute;
+    if (pile->p.pos_mul == 8) {
+        HIP_TRY(hipMemcpyAsync(host_out, pile->p.counts, glen * 32, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return MSW_OK;
+    }
+    // planes: rows are made on the GPU, a bounce buffer of them at a time
+    const uint64_t step = std::min<uint64_t>(glen, 1u << 20);
+    uint32_t* bounce = nullptr;
+    hipError_t e = hipMalloc((void**)&bounce, step * 32);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)step * 32, hipGetErrorString(e));
+    }
+    for (uint64_t pos = 0; pos < glen && e == hipSuccess; pos += step) {
+        const uint64_t m = std::min(step, glen - pos);
+        e = msw::launch_pileup_rows(pile->p, pos, m, bounce, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(host_out + pos * 8, bounce, m * 32, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    (void)hipFree(bounce);
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup counts: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
+int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_pileup_summary_t* out) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!out) return fail(MSW_E_INVALID, "out is NULL");
+    if (min_depth == 0) return fail(MSW_E_INVALID, "pileup summary: min_depth is 0");
+    if (!pile->finished) return fail(MSW_E_INVALID, "pileup summary before msw_pileup_finish");
+    if ((rc = set_device(ctx))) return rc;
+    HIP_TRY(hipEventSynchronize(pile->fin));
+    hipStream_t st = ctx->compute;
+    HIP_TRY(msw::launch_pileup_summary(pile->p, min_depth, pile->d_stats, st));
+    // the read counters' slots, then covered, depth_sum, minority_ref, max_depth
+    constexpr uint32_t kWords = msw::kPileupReadSlots * 2 * msw::kPileupReadSlotWords;
+    std::vector<unsigned long long> h(kWords + 4);
+    HIP_TRY(hipMemcpyAsync(h.data(), pile->p.reads, h.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memset(out, 0, sizeof(*out));
+    for (uint32_t s = 0; s < msw::kPileupReadSlots; ++s) {
+        out->reads_used += h[(s * 2 + 0) * msw::kPileupReadSlotWords];
+        out->reads_skipped += h[(s * 2 + 1) * msw::kPileupReadSlotWords];
+    }
+    out->covered = h[kWords];
+    out->depth_sum = h[kWords + 1];
+    out->minority_ref = h[kWords + 2];
+    out->max_depth = (uint32_t)h[kWords + 3];
     return MSW_OK;
 }
 
