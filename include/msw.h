@@ -701,6 +701,109 @@ int msw_pileup_counts_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** co
  * msw_pileup_finish (else MSW_E_INVALID); min_depth == 0 is MSW_E_INVALID. */
 int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_pileup_summary_t* out);
 
+/* Variants: the sites of finished pileup counts at which the sample differs
+ * from the genome, with a genotype.
+ *
+ * Everything is integers, so a plain restatement (tests/variant_oracle.py) can
+ * be compared value for value, and the result is a function of the counts, the
+ * genome bytes and the parameters alone.
+ *
+ * Input.  Finished counts c[glen][8] (the channels of "Pileup") and the genome
+ * bytes.  code() is the pileup's: A 0, C 1, G 2, T 3, anything else 4.
+ * depth(pos) is the sum of channels 0..5 as a 64-bit value; depth(glen) is 0.
+ *
+ * Site kinds.  A position yields at most two records, the column record first.
+ *   Column (MSW_VAR_SNV 0, MSW_VAR_DEL 1), only where r = code(genome[pos]) < 4:
+ *     n = c[0] + c[1] + c[2] + c[3] + c[5] (channel 4 says nothing), ref = c[r];
+ *     the alternative is the channel of {0, 1, 2, 3} \ {r} + {5} with the highest
+ *     count, the lowest channel index on a tie, and a is its count.  Channel 5
+ *     makes the record a DEL (alt 0), any other an SNV with alt the base letter.
+ *   Insertion (MSW_VAR_INS 2), for any genome byte: a = c[6],
+ *     span = min(depth(pos), depth(pos + 1)), ref = span > a ? span - a : 0,
+ *     n = ref + a.  The inserted sequence is not in the pileup: alt is 0.
+ *   The record's depth is n, its ref_count ref, its alt_count a.
+ *
+ * Candidate.  n >= min_depth, a >= min_alt and
+ * 1000 * a >= min_alt_permille * n, all in 64 bits.
+ *
+ * Genotypes.  g: 0 = 0/0, 1 = 0/1, 2 = 1/1; all u64.
+ *   raw[0] = ref * q_hit + a * q_miss
+ *   raw[1] = (ref + a) * q_het
+ *   raw[2] = ref * q_miss + a * q_hit
+ *   (third alleles cost the same under every genotype and are left out)
+ *   post = raw + {0, prior_het, prior_hom}
+ *   gt = argmin post, the lowest g on a tie
+ *   pl[g] = min((raw[g] - min raw + 50) / 100, 2^32 - 1)
+ *   qual  = min((post[0] - min post + 50) / 100, 2^32 - 1)
+ *   gq    = min(99, (second smallest post - smallest post + 50) / 100)
+ *
+ * Emission.  A candidate with gt != 0 and qual >= min_qual becomes a record.
+ * Records are ordered by pos, then kind.
+ *
+ * The costs are -1000 * log10(p) for an error rate e = 0.01: q_hit for an
+ * observation of a homozygous genotype's allele (p = 1 - e), q_miss for one of
+ * the other allele (p = e / 3), q_het for either allele of a heterozygote
+ * (p = (1 - e) / 2 + e / 6); the priors are in the same unit. */
+#define MSW_VAR_SNV 0
+#define MSW_VAR_DEL 1
+#define MSW_VAR_INS 2
+typedef struct {
+    uint32_t min_depth;        /* 4 */
+    uint32_t min_alt;          /* 2 */
+    uint32_t min_alt_permille; /* 200 */
+    uint32_t min_qual;         /* 20 */
+    uint32_t q_hit;            /* 4 */
+    uint32_t q_miss;           /* 2477 */
+    uint32_t q_het;            /* 304 */
+    uint32_t prior_het;        /* 3000 */
+    uint32_t prior_hom;        /* 3301 */
+} msw_call_params_t;
+/* One record, 48 bytes, the same bytes in memory and in the .var file
+ * (little-endian). */
+typedef struct {
+    uint64_t pos;
+    uint32_t depth;      /* n, saturated at 2^32 - 1 */
+    uint32_t ref_count;  /* ref, saturated */
+    uint32_t alt_count;  /* a, saturated */
+    uint32_t qual;
+    uint32_t pl[3];
+    uint8_t kind;        /* MSW_VAR_* */
+    uint8_t ref;         /* the genome byte */
+    uint8_t alt;         /* SNV: 'A', 'C', 'G' or 'T'; else 0 */
+    uint8_t gt;          /* 1 = 0/1, 2 = 1/1 */
+    uint8_t gq;
+    uint8_t pad[7];      /* zeros */
+} msw_variant_t;
+
+/* Fills *params with the defaults noted beside the fields. */
+void msw_call_params_default(msw_call_params_t* params);
+
+/* In every call below: params == NULL selects the defaults; a q_* above 65535,
+ * min_depth == 0 or min_alt_permille above 1000 is MSW_E_INVALID.  Records
+ * past `cap` are not written; the total is always reported.
+ *
+ * Calls on a finished pileup's own counts and genome, enqueued on `stream`
+ * (NULL = the context's compute stream, behind the finish), no host
+ * synchronisation: out_dev[cap] records and *n_total_dev (u64) are device
+ * memory.  out_dev == NULL with cap == 0 runs the count pass alone.  Before
+ * msw_pileup_finish: MSW_E_INVALID.  A genome above 2^31 - 1 bases is
+ * MSW_E_RANGE (a call's record offsets are 32 bits: at most two per base). */
+int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_dev,
+                           uint64_t cap, uint64_t* n_total_dev, void* stream);
+/* The same into host memory, synchronous.  out_host == NULL with cap == 0 runs
+ * the count pass alone and returns the total. */
+int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_host,
+                    uint64_t cap, uint64_t* n_total);
+/* Calls on any host counts_host[glen][8] over genome_host[glen], for example
+ * the sum of several pileups; synchronous.  The rows go through a bounded
+ * device buffer in chunks of chunk_pos positions (0 = 2^20; above 2^24 is
+ * MSW_E_RANGE), each chunk with one row of look-ahead for depth(pos + 1):
+ * record order and totals do not depend on chunk_pos.  glen and the total are
+ * 64-bit and have no other limit. */
+int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
+                    const msw_call_params_t* params, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
+                    uint64_t* n_total);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

@@ -37,6 +37,7 @@ EXPORTED = (
     "msw_seed_candidates_device", "msw_seed_candidates", "msw_mapq_select_device", "msw_map_reads",
     "msw_pileup_create", "msw_pileup_destroy", "msw_pileup_add_device", "msw_pileup_add", "msw_pileup_finish",
     "msw_pileup_counts", "msw_pileup_counts_device", "msw_pileup_summary",
+    "msw_call_params_default", "msw_pileup_call_device", "msw_pileup_call", "msw_call_counts",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -123,6 +124,11 @@ class PileupSummaryT(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class CallParamsT(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("min_depth", "min_alt", "min_alt_permille", "min_qual", "q_hit",
+                                               "q_miss", "q_het", "prior_het", "prior_hom")]
+
+
 class DevReadsT(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_void_p), ("read_len", ctypes.c_void_p), ("pos", ctypes.c_void_p),
                 ("read_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("first_read", ctypes.c_uint64),
@@ -205,6 +211,12 @@ def _declare(L):
         "msw_pileup_counts_device": (I, [P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64),
                                          ctypes.POINTER(ctypes.c_uint64)]),
         "msw_pileup_summary": (I, [P, P, ctypes.c_uint32, ctypes.POINTER(PileupSummaryT)]),
+        "msw_call_params_default": (None, [ctypes.POINTER(CallParamsT)]),
+        "msw_pileup_call_device": (I, [P, P, ctypes.POINTER(CallParamsT), P, ctypes.c_uint64, P, P]),
+        "msw_pileup_call": (I, [P, P, ctypes.POINTER(CallParamsT), P, ctypes.c_uint64,
+                                ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_call_counts": (I, [P, P, ctypes.c_uint64, P, ctypes.POINTER(CallParamsT), ctypes.c_uint64, P,
+                                ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

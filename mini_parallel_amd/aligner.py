@@ -22,11 +22,11 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, AlnT, BatchT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PileupSummaryT,
+from ._lib import (MSW_E_INVALID, AlnT, BatchT, CallParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PileupSummaryT,
                    ReadBatchT, ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
@@ -151,6 +151,66 @@ def _fresh_ptr(a) -> int:
     """Address of a just-allocated (writable, contiguous) array: through the
     buffer protocol, ~3x cheaper than a.ctypes.data."""
     return ctypes.addressof(ctypes.c_char.from_buffer(a)) if a.size else 0
+
+
+# One variant record (msw_variant_t of include/msw.h, "Variants"): 48 bytes, the
+# same in memory and in the .var file.
+VARIANT_DTYPE = np.dtype([("pos", "<u8"), ("depth", "<u4"), ("ref_count", "<u4"), ("alt_count", "<u4"),
+                          ("qual", "<u4"), ("pl", "<u4", (3,)), ("kind", "u1"), ("ref", "u1"), ("alt", "u1"),
+                          ("gt", "u1"), ("gq", "u1"), ("pad", "u1", (7,))])
+assert VARIANT_DTYPE.itemsize == 48
+VAR_SNV, VAR_DEL, VAR_INS = 0, 1, 2
+
+
+@dataclass(frozen=True)
+class CallParams:
+    """The caller's thresholds, costs and priors (msw_call_params_t; the
+    defaults are msw_call_params_default's)."""
+    min_depth: int = 4
+    min_alt: int = 2
+    min_alt_permille: int = 200
+    min_qual: int = 20
+    q_hit: int = 4
+    q_miss: int = 2477
+    q_het: int = 304
+    prior_het: int = 3000
+    prior_hom: int = 3301
+
+    FIELDS = ("min_depth", "min_alt", "min_alt_permille", "min_qual", "q_hit", "q_miss", "q_het", "prior_het",
+              "prior_hom")
+
+    def to_c(self) -> CallParamsT:
+        for k in self.FIELDS:
+            if not 0 <= int(getattr(self, k)) <= 0xFFFFFFFF:
+                raise MswError(MSW_E_INVALID, f"call params: {k} does not fit 32 bits")
+        return CallParamsT(*(int(getattr(self, k)) for k in self.FIELDS))
+
+
+class Variants(NamedTuple):
+    """Variant records as arrays, one entry per record, ordered by pos, then
+    kind (0 SNV, 1 DEL, 2 INS).  ``ref`` is the genome byte, ``alt`` the base
+    letter of an SNV and 0 otherwise, ``gt`` 1 for 0/1 and 2 for 1/1."""
+    pos: np.ndarray        # uint64
+    kind: np.ndarray       # uint8
+    ref: np.ndarray        # uint8
+    alt: np.ndarray        # uint8
+    gt: np.ndarray         # uint8
+    gq: np.ndarray         # uint8
+    qual: np.ndarray       # uint32
+    depth: np.ndarray      # uint32
+    ref_count: np.ndarray  # uint32
+    alt_count: np.ndarray  # uint32
+    pl: np.ndarray         # uint32 [n][3]
+
+    @classmethod
+    def from_records(cls, rec: np.ndarray) -> "Variants":
+        return cls(*(np.ascontiguousarray(rec[k]) for k in cls._fields))
+
+    def to_records(self) -> np.ndarray:
+        rec = np.zeros(len(self.pos), VARIANT_DTYPE)
+        for k in self._fields:
+            rec[k] = getattr(self, k)
+        return rec
 
 
 class Context:
@@ -532,6 +592,33 @@ class Context:
         base the allele, deletion, insertion and reverse-strand counts of the
         alignment records added to it."""
         return Pileup(self, genome)
+
+    # -- variants (include/msw.h, "Variants") -------------------------------------------
+    def call_variants(self, genome, counts, params: Optional[CallParams] = None, chunk_pos: int = 0) -> Variants:
+        """Variant calls from any host ``counts[glen][8]`` over the genome bytes
+        (msw_call_counts), for example the sum of several pileups.  The rows go
+        to the GPU in chunks of ``chunk_pos`` positions (0: about 1 M); the
+        records do not depend on it."""
+        g = np.frombuffer(bytes(genome), np.uint8) if isinstance(genome, (bytes, bytearray)) else \
+            np.ascontiguousarray(genome, dtype=np.uint8)
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        if c.ndim != 2 or c.shape[1] != 8 or c.shape[0] != g.shape[0]:
+            raise MswError(MSW_E_INVALID, "counts must be [len(genome)][8]")
+        q = (params or CallParams()).to_c()
+        total = ctypes.c_uint64()
+
+        def run(out, cap):
+            check(lib().msw_call_counts(self.handle, g.ctypes.data if g.size else None, g.shape[0],
+                                        c.ctypes.data if c.size else None, ctypes.byref(q), chunk_pos,
+                                        _fresh_ptr(out) or None if out is not None else None, cap,
+                                        ctypes.byref(total)))
+            return int(total.value)
+
+        n = run(None, 0)
+        rec = np.zeros(n, VARIANT_DTYPE)
+        if n and run(rec, n) != n:
+            raise MswError(MSW_E_INVALID, "the counts changed between the two calls")
+        return Variants.from_records(rec)
 
     # -- candidates and mapping quality (include/msw.h) ---------------------------------
     def _map_reads_mapq(self, genome, index, reads, read_len, scoring, both, window, band, cap, step, min_votes,
@@ -989,6 +1076,30 @@ class Pileup:
         check(lib().msw_pileup_summary(self.ctx.handle, self.handle, min_depth, ctypes.byref(s)))
         return {k: int(getattr(s, k)) for k in ("covered", "depth_sum", "max_depth", "minority_ref", "reads_used",
                                                 "reads_skipped")}
+
+    def call_device(self, out_ptr: int, cap: int, n_total_ptr: int, params: Optional[CallParams] = None,
+                    stream: int = 0) -> None:
+        """Enqueue the call on ``stream`` (msw_pileup_call_device): up to
+        ``cap`` 48-byte records to the device pointer ``out_ptr`` and the total
+        as a u64 to ``n_total_ptr``; ``out_ptr`` 0 with ``cap`` 0 runs the count
+        pass alone.  No host synchronisation."""
+        q = (params or CallParams()).to_c()
+        check(lib().msw_pileup_call_device(self.ctx.handle, self.handle, ctypes.byref(q),
+                                           ctypes.c_void_p(out_ptr or None), cap, ctypes.c_void_p(n_total_ptr or None),
+                                           ctypes.c_void_p(stream or None)))
+
+    def call(self, params: Optional[CallParams] = None) -> Variants:
+        """Variant calls from the finished counts (msw_pileup_call): one count
+        call, then one call that fills the records."""
+        q = (params or CallParams()).to_c()
+        total = ctypes.c_uint64()
+        check(lib().msw_pileup_call(self.ctx.handle, self.handle, ctypes.byref(q), None, 0, ctypes.byref(total)))
+        n = int(total.value)
+        rec = np.zeros(n, VARIANT_DTYPE)
+        if n:
+            check(lib().msw_pileup_call(self.ctx.handle, self.handle, ctypes.byref(q), _fresh_ptr(rec), n,
+                                        ctypes.byref(total)))
+        return Variants.from_records(rec)
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:

@@ -29,7 +29,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .aligner import CigarList
+from .aligner import VAR_DEL, VAR_INS, VAR_SNV, VARIANT_DTYPE, CallParams, CigarList, Variants
 
 MAGIC = b"MSWA"
 VERSION = 1
@@ -237,3 +237,143 @@ def read_pileup(path):
         raise ValueError(f"{path}: {len(data)} bytes, the header's genome length {glen} asks for {want}")
     counts = np.frombuffer(data, "<u4", glen * PILEUP_CHANNELS, PILEUP_HEADER.itemsize)
     return counts.reshape(glen, PILEUP_CHANNELS).astype(np.uint32), int(head["reads_used"])
+
+
+# The ``.var`` file of ``rustseq_mini --full-wgs --variants-out``,
+# little-endian: a 72-byte header -- "MSWVARS1", u32 version = 1, u32 record size
+# = 48, u64 genome length, u64 record count, the nine u32 of msw_call_params_t in
+# their order, u32 zero -- then the records (msw_variant_t of include/msw.h,
+# "Variants"), ordered by pos, then kind.
+VARIANTS_MAGIC = b"MSWVARS1"
+VARIANTS_VERSION = 1
+VARIANTS_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("record_size", "<u4"), ("glen", "<u8"),
+                            ("count", "<u8"), ("params", "<u4", (9,)), ("reserved", "<u4")])
+assert VARIANTS_HEADER.itemsize == 72
+
+
+def _check_variant_records(path, rec, glen) -> None:
+    if not len(rec):
+        return
+    if int(rec["kind"].max()) > VAR_INS:
+        raise ValueError(f"{path}: a record of unknown kind")
+    if not np.isin(rec["gt"], (1, 2)).all():
+        raise ValueError(f"{path}: a record with a genotype other than 0/1 and 1/1")
+    if rec["pad"].any():
+        raise ValueError(f"{path}: a record's padding is not zero")
+    if int(rec["pos"].max()) >= glen:
+        raise ValueError(f"{path}: a record lies past the genome length {glen}")
+    pos, col = rec["pos"], rec["kind"] != VAR_INS
+    # at most one column record and one insertion per position, the column record first
+    later = (pos[1:] > pos[:-1]) | ((pos[1:] == pos[:-1]) & col[:-1] & ~col[1:])
+    if not later.all():
+        raise ValueError(f"{path}: the records are not ordered by pos, then kind")
+
+
+def write_variants(path, variants: Variants, glen: int, params: Optional[CallParams] = None) -> None:
+    """Write the records of a genome of ``glen`` bases and the parameters they
+    were called with (the defaults when None)."""
+    params = params or CallParams()
+    rec = variants.to_records()
+    _check_variant_records(str(path), rec, int(glen))
+    head = np.zeros(1, VARIANTS_HEADER)
+    head["magic"], head["version"], head["record_size"] = VARIANTS_MAGIC, VARIANTS_VERSION, VARIANT_DTYPE.itemsize
+    head["glen"], head["count"] = int(glen), len(rec)
+    head["params"] = [int(getattr(params, k)) for k in CallParams.FIELDS]
+    with open(path, "wb") as f:
+        f.write(head.tobytes())
+        f.write(rec.tobytes())
+
+
+def read_variants(path):
+    """-> (Variants, genome length, CallParams).  Raises ValueError on a bad
+    magic, version or record size, on a size that does not match the header's
+    record count, and on records that are out of order, past the genome, of an
+    unknown kind or genotype or with non-zero padding."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < VARIANTS_HEADER.itemsize:
+        raise ValueError(f"{path}: truncated header")
+    head = np.frombuffer(data, VARIANTS_HEADER, 1)[0]
+    if bytes(head["magic"]) != VARIANTS_MAGIC:
+        raise ValueError(f"{path}: bad magic")
+    if int(head["version"]) != VARIANTS_VERSION:
+        raise ValueError(f"{path}: version {int(head['version'])}, expected {VARIANTS_VERSION}")
+    if int(head["record_size"]) != VARIANT_DTYPE.itemsize:
+        raise ValueError(f"{path}: record size {int(head['record_size'])}, expected {VARIANT_DTYPE.itemsize}")
+    if int(head["reserved"]) != 0:
+        raise ValueError(f"{path}: the header's reserved word is not zero")
+    glen, count = int(head["glen"]), int(head["count"])
+    want = VARIANTS_HEADER.itemsize + count * VARIANT_DTYPE.itemsize
+    if len(data) != want:
+        raise ValueError(f"{path}: {len(data)} bytes, the header's record count {count} asks for {want}")
+    rec = np.frombuffer(data, VARIANT_DTYPE, count, VARIANTS_HEADER.itemsize)
+    _check_variant_records(str(path), rec, glen)
+    return Variants.from_records(rec), glen, CallParams(*(int(v) for v in head["params"]))
+
+
+def write_vcf(path, variants: Variants, genome, contig: str = "ref", sample: str = "sample") -> None:
+    """VCF 4.2 text of the records over ``genome`` (bytes or a uint8 array).
+    An SNV is written as it is.  Consecutive DEL records (pos, pos + 1, ...
+    with equal genotype) become one deletion with the first record's numbers,
+    anchored at the base before the run, or at the base after it when the run
+    starts at position 0.  An insertion is the symbolic ``<INS>`` at its anchor
+    base: the pileup does not hold the inserted sequence."""
+    g = bytes(genome) if isinstance(genome, (bytes, bytearray)) else np.asarray(genome, np.uint8).tobytes()
+    rec = variants.to_records()
+
+    def seq(lo, hi):
+        return "".join(chr(b) if chr(b).isalpha() else "N" for b in g[lo:hi])
+
+    lines = []  # (POS, order, text)
+
+    def line(vpos, ref, alt, r):
+        gt = "0/1" if int(r["gt"]) == 1 else "1/1"
+        lines.append((vpos, len(lines), "%s\t%d\t.\t%s\t%s\t%d\t.\tDP=%d\tGT:AD:GQ:PL\t%s:%d,%d:%d:%d,%d,%d" % (
+            contig, vpos, ref, alt, int(r["qual"]), int(r["depth"]), gt, int(r["ref_count"]), int(r["alt_count"]),
+            int(r["gq"]), int(r["pl"][0]), int(r["pl"][1]), int(r["pl"][2]))))
+
+    def insertion(r):
+        line(int(r["pos"]) + 1, seq(int(r["pos"]), int(r["pos"]) + 1), "<INS>", r)
+
+    k = 0
+    while k < len(rec):
+        r = rec[k]
+        pos, kind = int(r["pos"]), int(r["kind"])
+        if kind == VAR_SNV:
+            line(pos + 1, seq(pos, pos + 1), chr(int(r["alt"])), r)
+        elif kind == VAR_INS:
+            insertion(r)
+        else:
+            # the run's further DEL records; an insertion record between two of them does not end the run
+            end, j = pos + 1, k + 1
+            while j < len(rec):
+                if int(rec[j]["kind"]) == VAR_DEL and int(rec[j]["pos"]) == end and rec[j]["gt"] == r["gt"]:
+                    end += 1
+                elif not (int(rec[j]["kind"]) == VAR_INS and int(rec[j]["pos"]) == end - 1):
+                    break
+                j += 1
+            if pos > 0:
+                line(pos, seq(pos - 1, end), seq(pos - 1, pos), r)
+            elif end < len(g):
+                line(1, seq(0, end + 1), seq(end, end + 1), r)
+            else:
+                line(1, seq(0, end), "<DEL>", r)  # the whole genome: no base to anchor at
+            for m in range(k + 1, j):
+                if int(rec[m]["kind"]) == VAR_INS:
+                    insertion(rec[m])
+            k = j - 1
+        k += 1
+    lines.sort(key=lambda t: (t[0], t[1]))
+    with open(path, "w") as f:
+        f.write("##fileformat=VCFv4.2\n")
+        f.write("##contig=<ID=%s,length=%d>\n" % (contig, len(g)))
+        f.write('##ALT=<ID=INS,Description="Insertion after this base; the sequence is not known">\n')
+        f.write('##ALT=<ID=DEL,Description="Deletion">\n')
+        f.write('##INFO=<ID=DP,Number=1,Type=Integer,Description="Observations at the site">\n')
+        f.write('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n')
+        f.write('##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Observations of the reference and the alternative">\n')
+        f.write('##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality">\n')
+        f.write('##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Genotype costs, -10 log10 of the likelihood">\n')
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n" % sample)
+        for _, _, text in lines:
+            f.write(text + "\n")

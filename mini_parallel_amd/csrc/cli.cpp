@@ -103,6 +103,14 @@ void usage() {
         "                               (default 0)\n"
         "      --pileup-min-depth N     --pileup-out: least depth of a position in the summary's minority_ref\n"
         "                               (default 4)\n"
+        "      --variants-out PATH      --alignments-out: also call variants from the run's pileup (with or without\n"
+        "                               --pileup-out) and write them as one .var file: SNVs, deleted bases and\n"
+        "                               insertion sites with a genotype (DESIGN.md 4.15).  --pileup-min-mapq\n"
+        "                               applies.  Like a pileup, the calls cover one run\n"
+        "      --call-min-depth N       --variants-out: least observations at a site, at least 1 (default 4)\n"
+        "      --call-min-alt N         --variants-out: least observations of the alternative (default 2)\n"
+        "      --call-min-alt-permille N  --variants-out: least share of the alternative, 0..1000 (default 200)\n"
+        "      --call-min-qual N        --variants-out: least quality of a call (default 20)\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -151,6 +159,11 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--pileup-out") a.pileup_out = v();
         else if (s == "--pileup-min-mapq") { a.pileup_min_mapq = atoi(v().c_str()); a.has_pileup_min_mapq = true; }
         else if (s == "--pileup-min-depth") { a.pileup_min_depth = atoi(v().c_str()); a.has_pileup_min_depth = true; }
+        else if (s == "--variants-out") a.variants_out = v();
+        else if (s == "--call-min-depth") { a.call_min_depth = atol(v().c_str()); a.has_call_flag = true; }
+        else if (s == "--call-min-alt") { a.call_min_alt = atol(v().c_str()); a.has_call_flag = true; }
+        else if (s == "--call-min-alt-permille") { a.call_min_alt_permille = atol(v().c_str()); a.has_call_flag = true; }
+        else if (s == "--call-min-qual") { a.call_min_qual = atol(v().c_str()); a.has_call_flag = true; }
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -193,12 +206,19 @@ Args parse_args(int argc, char** argv) {
     // refused here, before any file is opened, like --mapq
     if (!a.pileup_out.empty() && a.alignments_out.empty())
         die("error: --pileup-out needs --alignments-out (the records are made there)");
-    if (a.has_pileup_min_mapq && (a.pileup_out.empty() || !a.mapq))
+    if (!a.variants_out.empty() && a.alignments_out.empty())
+        die("error: --variants-out needs --alignments-out (the records are made there)");
+    if (a.has_pileup_min_mapq && (!a.wants_pileup() || !a.mapq))
         die("error: --pileup-min-mapq needs --pileup-out and --mapq");
     if (a.has_pileup_min_mapq && (a.pileup_min_mapq < 0 || a.pileup_min_mapq > 60))
         die("error: --pileup-min-mapq must be 0..60");
     if (a.has_pileup_min_depth && a.pileup_out.empty()) die("error: --pileup-min-depth needs --pileup-out");
     if (a.has_pileup_min_depth && a.pileup_min_depth < 1) die("error: --pileup-min-depth must be at least 1");
+    if (a.has_call_flag && a.variants_out.empty()) die("error: the --call-* thresholds need --variants-out");
+    if (a.call_min_depth < 1 || a.call_min_depth > 0xFFFFFFFFl) die("error: --call-min-depth must be 1..4294967295");
+    if (a.call_min_alt < 0 || a.call_min_alt > 0xFFFFFFFFl) die("error: --call-min-alt must be 0..4294967295");
+    if (a.call_min_alt_permille < 0 || a.call_min_alt_permille > 1000) die("error: --call-min-alt-permille must be 0..1000");
+    if (a.call_min_qual < 0 || a.call_min_qual > 0xFFFFFFFFl) die("error: --call-min-qual must be 0..4294967295");
     return a;
 }
 
@@ -318,6 +338,11 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
     if (a.mapq) key += "|mapq|" + std::to_string(a.seed_sep);
     // a pileup covers the files of one run: its run never resumes one without, or one with another threshold
     if (!a.pileup_out.empty()) key += "|pileup|" + std::to_string(a.pileup_min_mapq);
+    // nor do calls, which come from that pileup: the least MAPQ of its reads and the four thresholds
+    if (!a.variants_out.empty())
+        key += "|variants|" + std::to_string(a.pileup_min_mapq) + "," + std::to_string(a.call_min_depth) + "," +
+               std::to_string(a.call_min_alt) + "," + std::to_string(a.call_min_alt_permille) + "," +
+               std::to_string(a.call_min_qual);
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -485,6 +510,18 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
           << ", \"depth_sum\": " << p.depth_sum << ", \"max_depth\": " << p.max_depth
           << ", \"minority_ref\": " << p.minority_ref << ", \"pileup_ms\": " << p.ms << "}";
     }
+    // --variants-out only
+    if (rep.variants.on) {
+        const VariantsReport& v = rep.variants;
+        const msw_call_params_t q = a.call_params();
+        j << ", \"variants\": {\"path\": \"" << json_escape(a.variants_out) << "\", \"min_mapq\": " << a.pileup_min_mapq
+          << ", \"params\": {\"min_depth\": " << q.min_depth << ", \"min_alt\": " << q.min_alt
+          << ", \"min_alt_permille\": " << q.min_alt_permille << ", \"min_qual\": " << q.min_qual
+          << ", \"q_hit\": " << q.q_hit << ", \"q_miss\": " << q.q_miss << ", \"q_het\": " << q.q_het
+          << ", \"prior_het\": " << q.prior_het << ", \"prior_hom\": " << q.prior_hom << "}, \"records\": " << v.total
+          << ", \"snv\": " << v.by_kind[0] << ", \"del\": " << v.by_kind[1] << ", \"ins\": " << v.by_kind[2]
+          << ", \"het\": " << v.by_gt[1] << ", \"hom\": " << v.by_gt[2] << ", \"variants_ms\": " << v.ms << "}";
+    }
     j
       << ", \"inflate_bytes_in\": " << rep.gz_in << ", \"inflate_bytes_out\": " << rep.gz_out
       << ", \"reads_per_second\": " << reads / secs << ", \"t_main_unix_ns\": " << in.t_main_ns
@@ -507,10 +544,11 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
     ck.path = a.checkpoint_dir + "/checkpoint_" + ck.run_id + ".json";
     ck.total_files = files.size();
     if (ck.load()) printf("Resuming run %s from %s\n", ck.run_id.c_str(), ck.path.c_str());
-    if (!a.pileup_out.empty())
+    if (a.wants_pileup())
         for (const auto& kv : ck.files)
             if (kv.second.completed)
-                die("error: --pileup-out covers the files of one run, but " + ck.path +
+                die(std::string("error: ") + (a.pileup_out.empty() ? "--variants-out" : "--pileup-out") +
+                    " covers the files of one run, but " + ck.path +
                     " already lists a completed file: remove the checkpoint to run all files again");
     const std::vector<Device> workers = worker_devices(devices, a.num_gpus);
     const WgsReport rep = run_full_wgs(a, workers, files, gidx, n_lane_files, ck, ref);
@@ -536,6 +574,10 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
                "positions with the reference base in the minority at depth >= %d, %.1f ms -> %s\n",
                rep.pileup.reads_used, rep.pileup.reads_skipped, rep.pileup.covered, rep.pileup.depth_sum,
                rep.pileup.max_depth, rep.pileup.minority_ref, a.pileup_min_depth, rep.pileup.ms, a.pileup_out.c_str());
+    if (rep.variants.on)
+        printf("Variants: %llu records (%llu SNV, %llu DEL, %llu INS; %llu 0/1, %llu 1/1), %.1f ms -> %s\n",
+               rep.variants.total, rep.variants.by_kind[0], rep.variants.by_kind[1], rep.variants.by_kind[2],
+               rep.variants.by_gt[1], rep.variants.by_gt[2], rep.variants.ms, a.variants_out.c_str());
     printf("Wall time: %.2f s", rep.wall_ms / 1000.0);
     if (rep.cells) printf(", %.1f GCUPS end-to-end", rep.cells / (rep.wall_ms * 1e6));
     printf("\n");

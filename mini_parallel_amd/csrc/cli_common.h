@@ -86,6 +86,22 @@ struct Args {
     std::string pileup_out;
     bool has_pileup_min_mapq = false, has_pileup_min_depth = false;
     int pileup_min_mapq = 0, pileup_min_depth = 4;
+    // --variants-out: the variant calls of the run's pileup (one .var file; include/msw.h, "Variants"), with the
+    // thresholds of --call-min-depth / -alt / -alt-permille / -qual over msw_call_params_default
+    std::string variants_out;
+    bool has_call_flag = false;
+    long call_min_depth = 4, call_min_alt = 2, call_min_alt_permille = 200, call_min_qual = 20;
+    msw_call_params_t call_params() const {
+        msw_call_params_t q;
+        msw_call_params_default(&q);
+        q.min_depth = (uint32_t)call_min_depth;
+        q.min_alt = (uint32_t)call_min_alt;
+        q.min_alt_permille = (uint32_t)call_min_alt_permille;
+        q.min_qual = (uint32_t)call_min_qual;
+        return q;
+    }
+    // the workers keep pileups for either output
+    bool wants_pileup() const { return !pileup_out.empty() || !variants_out.empty(); }
     long chunk_size = 1, num_files = -1;
     std::string score_mode = "compat", gap_model = "linear", reference, checkpoint_dir = ".", json, scores_out, alignments_out;
     int match = 2, mismatch = -1, gap_open = 3, gap_extend = -1, window = 0, num_gpus = 1;

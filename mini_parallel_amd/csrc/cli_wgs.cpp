@@ -231,7 +231,8 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
     rep.wall_ms = d ? std::chrono::duration<double, std::milli>(Clock::time_point(Clock::duration(d)) - t_all).count()
                     : total;
     rep.pileup = pileup;
-    rep.teardown_ms = total - rep.wall_ms - pileup.ms;
+    rep.variants = variants;
+    rep.teardown_ms = total - rep.wall_ms - pileup.ms - variants.ms;
     rep.cells = cells.load();
     rep.both_strands = a.both_strands;
     rep.reverse_reads = reverse_reads.load();
@@ -260,7 +261,7 @@ WgsReport WgsRun::report(int readers, int host_threads, const std::vector<msw_st
 LaneRun::LaneRun(WgsRun& run_, bool aln_, bool per_read_, bool both_, uint64_t batch_, int nworkers_)
     : run(run_), aln(aln_), per_read(per_read_), both(both_), batch(batch_), nworkers(nworkers_),
       started(new std::atomic<int>[run_.st.size()]), gstats((size_t)nworkers_, msw_stats_t{}),
-      pileup(!run_.a.pileup_out.empty()) {
+      pileup(run_.a.wants_pileup()) {
     for (size_t i = 0; i < run.st.size(); ++i) started[i] = 0;
 }
 
@@ -304,6 +305,57 @@ static void write_pileup(WgsRun& run, LaneRun& lanes) {
     p.ms = d ? std::chrono::duration<double, std::milli>(Clock::now() - Clock::time_point(Clock::duration(d))).count() : 0.0;
 }
 
+// --variants-out, after the workers have joined and the pileup's phase: one
+// context on the run's first device calls on the summed counts
+// (msw_call_counts: a count call, then a call that fills the records) and the
+// .var file is written -- a 72-byte header ("MSWVARS1", u32 version 1, u32
+// record size 48, u64 genome length, u64 record count, the nine u32 of
+// msw_call_params_t, u32 zero), then the records.
+static void write_variants(WgsRun& run, LaneRun& lanes) {
+    const auto t0 = Clock::now();
+    const long long d = run.t_done_ns.load();
+    // without --pileup-out the phase runs from the stop of the clock
+    const auto from = run.pileup.on || !d ? t0 : Clock::time_point(Clock::duration(d));
+    const std::string& g = run.genome();
+    const uint64_t glen = g.size();
+    if (lanes.pile_failed || lanes.pile_sum.size() != glen * 8) die("error: the pileup could not be read back from the GPUs");
+    const msw_call_params_t q = run.a.call_params();
+    std::vector<msw_variant_t> recs;
+    {
+        Ctx ctx(run.devices[0].ordinal, MSW_CTX_LEAN);
+        uint64_t n = 0, again = 0;
+        const uint8_t* gb = reinterpret_cast<const uint8_t*>(g.data());
+        if (msw_call_counts(ctx.h, gb, glen, lanes.pile_sum.data(), &q, 0, nullptr, 0, &n) != MSW_OK)
+            die(std::string("GPU variant call error: ") + msw_last_error());
+        recs.resize(n);
+        if (n && (msw_call_counts(ctx.h, gb, glen, lanes.pile_sum.data(), &q, 0, recs.data(), n, &again) != MSW_OK ||
+                  again != n))
+            die(std::string("GPU variant call error: ") + msw_last_error());
+    }
+    VariantsReport& v = run.variants;
+    v.on = true;
+    v.total = recs.size();
+    for (const msw_variant_t& r : recs) {
+        if (r.kind < 3) ++v.by_kind[r.kind];
+        if (r.gt < 3) ++v.by_gt[r.gt];
+    }
+    FILE* f = fopen(run.a.variants_out.c_str(), "wb");
+    if (!f) die("error: cannot create " + run.a.variants_out);
+    unsigned char head[72] = {0};
+    memcpy(head, "MSWVARS1", 8);
+    const uint32_t version = 1, rsize = (uint32_t)sizeof(msw_variant_t);
+    const uint64_t count = recs.size();
+    memcpy(head + 8, &version, 4);
+    memcpy(head + 12, &rsize, 4);
+    memcpy(head + 16, &glen, 8);
+    memcpy(head + 24, &count, 8);
+    memcpy(head + 32, &q, 36);
+    static_assert(sizeof(msw_call_params_t) == 36 && sizeof(msw_variant_t) == 48, "the .var layout");
+    const bool ok = fwrite(head, 1, 72, f) == 72 && fwrite(recs.data(), sizeof(msw_variant_t), recs.size(), f) == recs.size();
+    if (fclose(f) != 0 || !ok) die("error: writing " + run.a.variants_out);
+    v.ms = std::chrono::duration<double, std::milli>(Clock::now() - from).count();
+}
+
 static WgsReport run_gpu_lanes(WgsRun& run, bool aln, bool per_read) {
     // reads per scoring launch; wide slabs (MSW_MAX_READ_LEN) keep a batch's
     // slab near 256 MiB (two per worker)
@@ -325,7 +377,8 @@ static WgsReport run_gpu_lanes(WgsRun& run, bool aln, bool per_read) {
     for (int wi = 0; wi < lanes.nworkers; ++wi) workers.emplace_back(lane_worker, std::ref(lanes), wi);
     run.start_clock(lanes.nworkers);
     for (auto& t : workers) t.join();
-    if (lanes.pileup) write_pileup(run, lanes);
+    if (!run.a.pileup_out.empty()) write_pileup(run, lanes);
+    if (!run.a.variants_out.empty()) write_variants(run, lanes);
     return run.report(0, lanes.nworkers, lanes.gstats, true, lanes.gz_in.load(), lanes.gz_out.load());
 }
 

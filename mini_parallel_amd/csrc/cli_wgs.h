@@ -100,9 +100,18 @@ struct PileupReport {
     double ms = 0;
 };
 
+// --variants-out: the calls' totals by kind (SNV, DEL, INS) and genotype (index 1: 0/1, 2: 1/1) and the time of the
+// phase (the call on the summed counts, the file), after the pileup's phase.
+struct VariantsReport {
+    bool on = false;
+    unsigned long long total = 0, by_kind[3] = {0, 0, 0}, by_gt[3] = {0, 0, 0};
+    double ms = 0;
+};
+
 struct WgsReport {
     std::vector<FileCheckpoint> results;
     PileupReport pileup;
+    VariantsReport variants;
     double wall_ms = 0;
     unsigned long long cells = 0;
     int readers = 0;
@@ -169,6 +178,7 @@ struct WgsRun {
     std::atomic<unsigned long long> placed_reads{0};   // --map: reads with a window
     std::atomic<unsigned long long> mapq_hist[4] = {};  // --mapq: reads with MAPQ 0, 1-29, 30-59, 60
     PileupReport pileup;  // --pileup-out: filled after the workers have joined
+    VariantsReport variants;  // --variants-out: likewise
     StartGate gate;
     Clock::time_point t_setup, t_all;
     // the clock stops when the last worker has its last results on the host;
@@ -211,7 +221,7 @@ struct LaneRun {
     std::unique_ptr<std::atomic<int>[]> started;
     std::atomic<unsigned long long> gz_in{0}, gz_out{0};
     std::vector<msw_stats_t> gstats;  // per worker
-    // --pileup-out: the workers' finished counts [glen][8] summed on the host, and their read counters
+    // --pileup-out or --variants-out: the workers' finished counts [glen][8] summed on the host, and their read counters
     const bool pileup;
     std::mutex pile_mu;
     std::vector<uint32_t> pile_sum;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "msw.h"  // msw_call_params_t, msw_variant_t (Variants)
+
 namespace msw {
 
 // Substitution codes: a real byte b becomes b << code_shift (< 0x4000), so two
@@ -358,6 +360,35 @@ hipError_t launch_pileup_summary(const PileupParams& p, uint32_t min_depth, unsi
                                  hipStream_t stream);
 // out[m][8] = the rows of positions [pos0, pos0 + m), whatever the layout
 hipError_t launch_pileup_rows(const PileupParams& p, uint64_t pos0, uint64_t m, uint32_t* out, hipStream_t stream);
+
+// Variants (msw_call.hip; the contract is in include/msw.h, "Variants").  One
+// call over positions [0, m) of a counts slab: channel ch of position k is
+// counts[k * pos_mul + ch * ch_mul] (both pileup layouts, or a plain [m][8]
+// slab), genome[k] its byte, and `rows` >= m the rows that may be read:
+// m + 1 when the slab carries a look-ahead row for depth(m), else depth(m) is 0.
+constexpr uint32_t kCallTile = 256;  // positions per block, one per thread
+struct CallParams {
+    const uint8_t* genome;
+    const uint32_t* counts;
+    uint64_t pos_mul, ch_mul;
+    uint64_t m, rows;
+    uint64_t pos0;             // added to a record's pos
+    msw_call_params_t q;
+    uint32_t* tile_off;        // [tiles + 1]: per-tile record counts, scanned in place; entry `tiles` is the total
+    msw_variant_t* out;        // [cap], or null with cap 0
+    uint64_t cap;
+    unsigned long long* n_total;  // device, or null
+};
+inline uint64_t call_tiles(uint64_t m) { return (m + kCallTile - 1) / kCallTile; }
+// u32 words of tile_off plus the scan's temporaries behind it
+uint64_t call_tmp_words(uint64_t m);
+// count pass, scan, then the emit pass when cap > 0; *n_total = the total either way.  p.tile_off holds
+// call_tmp_words(m) words.
+hipError_t launch_call(const CallParams& p, hipStream_t stream);
+// the stages apart: msw_call_counts reads a chunk's total between the scan and the emit pass
+hipError_t launch_call_count(const CallParams& p, hipStream_t stream);
+hipError_t launch_call_scan(const CallParams& p, hipStream_t stream);
+hipError_t launch_call_emit(const CallParams& p, hipStream_t stream);
 
 // Placing reads (msw_seed.hip; the contract is in include/msw.h).
 constexpr uint32_t kSeedMaxCap = 8192;      // keys one read's LDS array holds (32 KiB)

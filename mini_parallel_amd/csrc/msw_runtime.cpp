@@ -3399,6 +3399,171 @@ int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_p
     return MSW_OK;
 }
 
+// Variants (include/msw.h, "Variants"; the kernels: msw_call.hip).
+void msw_call_params_default(msw_call_params_t* q) {
+    if (!q) return;
+    *q = msw_call_params_t{4, 2, 200, 20, 4, 2477, 304, 3000, 3301};
+}
+
+static int check_call_params(const msw_call_params_t* params, msw_call_params_t* q) {
+    if (params) *q = *params;
+    else msw_call_params_default(q);
+    if (q->q_hit > 65535u || q->q_miss > 65535u || q->q_het > 65535u)
+        return fail(MSW_E_INVALID, "call params: a q_* cost above 65535");
+    if (q->min_depth == 0) return fail(MSW_E_INVALID, "call params: min_depth is 0");
+    if (q->min_alt_permille > 1000u) return fail(MSW_E_INVALID, "call params: min_alt_permille %u > 1000", q->min_alt_permille);
+    return MSW_OK;
+}
+
+static_assert(sizeof(msw_variant_t) == 48, "msw_variant_t is 48 bytes, in memory and in the .var file");
+
+int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_dev,
+                           uint64_t cap, uint64_t* n_total_dev, void* stream) {
+    int rc;
+    msw::CallParams p{};
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if ((rc = check_call_params(params, &p.q))) return rc;
+    if (!pile->finished) return fail(MSW_E_INVALID, "pileup call before msw_pileup_finish");
+    if (cap && !out_dev) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
+    if (pile->p.glen > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "pileup call: genome above 2^31-1 bases");
+    if ((rc = set_device(ctx))) return rc;
+    hipStream_t st = call_stream(ctx, stream);
+    // behind the fold, whatever stream it ran on
+    HIP_TRY(hipStreamWaitEvent(st, pile->fin, 0));
+    p.genome = pile->p.genome;
+    p.counts = pile->p.counts;
+    p.pos_mul = pile->p.pos_mul;
+    p.ch_mul = pile->p.ch_mul;
+    p.m = p.rows = pile->p.glen;
+    p.out = out_dev;
+    p.cap = cap;
+    p.n_total = reinterpret_cast<unsigned long long*>(n_total_dev);
+    HIP_TRY(hipMallocAsync((void**)&p.tile_off, msw::call_tmp_words(p.m) * sizeof(uint32_t), st));
+    hipError_t e = msw::launch_call(p, st);
+    const hipError_t ef = hipFreeAsync(p.tile_off, st);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup call: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
+int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_host,
+                    uint64_t cap, uint64_t* n_total) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
+    if (cap && !out_host) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
+    if ((rc = set_device(ctx))) return rc;
+    // at most two records per base
+    const uint64_t dcap = std::min<uint64_t>(cap, pile->p.glen * 2);
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, 16 + dcap * sizeof(msw_variant_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)(16 + dcap * sizeof(msw_variant_t)),
+                    hipGetErrorString(e));
+    }
+    hipStream_t st = ctx->compute;
+    msw_variant_t* d_out = reinterpret_cast<msw_variant_t*>(d + 16);
+    rc = msw_pileup_call_device(ctx, pile, params, dcap ? d_out : nullptr, dcap, reinterpret_cast<uint64_t*>(d), st);
+    if (rc == MSW_OK) {
+        uint64_t total = 0;
+        e = hipMemcpyAsync(&total, d, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        const uint64_t have = std::min(total, dcap);
+        if (e == hipSuccess && have) e = hipMemcpyAsync(out_host, d_out, have * sizeof(msw_variant_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MSW_E_DEVICE, "pileup call: %s", hipGetErrorString(e));
+        else *n_total = total;
+    } else {
+        (void)hipStreamSynchronize(st);
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
+                    const msw_call_params_t* params, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
+                    uint64_t* n_total) {
+    int rc;
+    msw::CallParams p{};
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
+    if ((rc = check_call_params(params, &p.q))) return rc;
+    if (cap && !out_host) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
+    if (chunk_pos > (1ull << 24)) return fail(MSW_E_RANGE, "call counts: chunk_pos above 2^24");
+    *n_total = 0;
+    if (glen == 0) return MSW_OK;
+    if (!genome_host || !counts_host) return fail(MSW_E_INVALID, "NULL array");
+    if ((rc = set_device(ctx))) return rc;
+    const uint64_t chunk = std::min<uint64_t>(glen, chunk_pos ? chunk_pos : 1ull << 20);
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    // [rows of chunk + 1 positions | genome bytes | total u64 | tile offsets and scan words]
+    const uint64_t o_gen = (chunk + 1) * 32, o_tot = o_gen + up16(chunk), o_tile = o_tot + 16,
+                   bytes = o_tile + up16(msw::call_tmp_words(chunk) * 4);
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)bytes, hipGetErrorString(e));
+    }
+    hipStream_t st = ctx->compute;
+    p.counts = reinterpret_cast<const uint32_t*>(d);
+    p.genome = d + o_gen;
+    p.pos_mul = 8;
+    p.ch_mul = 1;
+    p.n_total = reinterpret_cast<unsigned long long*>(d + o_tot);
+    p.tile_off = reinterpret_cast<uint32_t*>(d + o_tile);
+    msw_variant_t* d_out = nullptr;  // grows to the largest chunk's records that still fit cap
+    uint64_t d_out_cap = 0, total = 0, written = 0;
+    bool nomem = false;
+    for (uint64_t lo = 0; lo < glen && e == hipSuccess; lo += chunk) {
+        const uint64_t m = std::min(chunk, glen - lo);
+        p.m = m;
+        p.rows = lo + m < glen ? m + 1 : m;  // the look-ahead row
+        p.pos0 = lo;
+        p.out = nullptr;
+        p.cap = 0;
+        e = hipMemcpyAsync(d, counts_host + lo * 8, p.rows * 32, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_gen, genome_host + lo, m, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = msw::launch_call_count(p, st);
+        if (e == hipSuccess) e = msw::launch_call_scan(p, st);
+        uint64_t t = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&t, p.n_total, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        const uint64_t want = std::min(t, cap - written);
+        if (want) {
+            if (want > d_out_cap) {
+                if (d_out) (void)hipFree(d_out);
+                d_out = nullptr;
+                d_out_cap = 0;
+                e = hipMalloc((void**)&d_out, want * sizeof(msw_variant_t));
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    nomem = true;
+                    break;
+                }
+                d_out_cap = want;
+            }
+            p.out = d_out;
+            p.cap = want;
+            e = msw::launch_call_emit(p, st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(out_host + written, d_out, want * sizeof(msw_variant_t), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);  // the buffers are the next chunk's
+            written += want;
+        }
+        total += t;
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    if (d_out) (void)hipFree(d_out);
+    (void)hipFree(d);
+    if (nomem) return fail(MSW_E_NOMEM, "hipMalloc for a chunk's records: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "call counts: %s", hipGetErrorString(e));
+    *n_total = total;
+    return MSW_OK;
+}
+
 int msw_memcpy_d2h_async(msw_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     int rc = set_device(ctx);
