@@ -639,8 +639,25 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
  * depth >= min_depth and 2 * counts[pos][code(genome[pos])] < depth (the code
  * of a genome byte that is not upper-case ACGT is 4).
  *
- * The result is a function of the set of records alone: it is bit-reproducible
- * whatever order the batches and the GPU's atomics ran in.
+ * Base qualities (msw_pileup_add_qual[_device]).  quals[n][qual_stride] holds
+ * one byte per base, and its rows are always in the order of the file: byte t
+ * of row p belongs to base t of read p AS GIVEN, in both add forms.  The Phred
+ * value of a byte b is b >= 33 ? b - 33 : 0.  Column k of an M run stands at
+ * read offset i + k of the row the CIGAR refers to; its quality index is
+ * t = i + k for a strand-0 read (or strand == NULL) and
+ * t = read_len[p] - 1 - (i + k) for a strand-1 read, whether `rows` is the
+ * oriented slab (device form) or the reads as given (host form).  A column
+ * that passes the range rules of the walk counts only if t < qual_stride and
+ * phred(quals[p][t]) >= min_baseq.  One that passes the range rules and fails
+ * this test adds to no channel, neither 0..4 nor 7, and adds 1 to the
+ * pileup's low-quality column count (msw_pileup_lowq_columns).  D runs, I
+ * runs, reads_used and reads_skipped are as without qualities.
+ * min_baseq == 0 or quals == NULL is exactly msw_pileup_add[_device];
+ * min_baseq > 93 is MSW_E_RANGE.
+ *
+ * The result is a function of the set of records (with qualities and
+ * threshold, where given) alone: it is bit-reproducible whatever order the
+ * batches and the GPU's atomics ran in.
  *
  * State: about 44 bytes of device memory per genome base (the 32-byte row, two
  * 4-byte difference arrays and a 4-byte mismatch count), so
@@ -683,6 +700,22 @@ int msw_pileup_add_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, c
 int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len,
                    uint32_t read_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
                    const uint8_t* mapq, uint32_t min_mapq, uint64_t chunk_reads);
+
+/* Both adds with the base-quality threshold of "Base qualities" above.  quals
+ * is device memory in the device form (e.g. msw_gfastq_quals, msw_fastq.h) and
+ * host memory in the host form; a quality path of its own runs only when
+ * quals != NULL and min_baseq > 0, otherwise these are the calls above. */
+int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
+                               uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                               const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
+                               uint32_t min_baseq, void* stream);
+int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len,
+                        uint32_t read_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                        const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
+                        uint32_t min_baseq, uint64_t chunk_reads);
+/* The M columns dropped by the threshold so far; synchronous (it waits for the
+ * device), valid before or after msw_pileup_finish. */
+int msw_pileup_lowq_columns(msw_ctx* ctx, msw_pileup* pile, uint64_t* out);
 
 /* Folds the state into the counts, once, enqueued on `stream`: every add must
  * have been enqueued on that stream or have finished.  Afterwards both add

@@ -96,6 +96,39 @@ int msw_is_bgzf(const char* path);
  * ordered with work on the null stream. */
 int msw_gfastq_open(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64_t max_reads, int want_pos,
                     uint64_t span_bytes, msw_gfastq** out);
+/* The same with flags: MSW_GFASTQ_POS is want_pos, MSW_GFASTQ_QUAL keeps the
+ * records' quality lines (msw_gfastq_quals).  Any other bit is MSW_E_INVALID.
+ * msw_gfastq_open is this call with flags = want_pos ? MSW_GFASTQ_POS : 0.
+ *
+ * Quality mode changes nothing in what msw_gfastq_next and msw_gfastq_stats
+ * report over a file -- the reads, lengths, pos, first_read, error codes and
+ * messages are those of a reader without the flag -- except where one batch
+ * ends and the next begins: a span then ends at a whole record, so its last
+ * read may move to the next span.  The boundaries remain deterministic.  Two
+ * more device slabs of max_reads * read_stride bytes are allocated, and the
+ * room in front of a span grows from 64 KiB to hold a partial record (two
+ * lines of read_stride bytes, a header and a '+' line of up to 4 KiB each)
+ * where that is more. */
+#define MSW_GFASTQ_POS 1u
+#define MSW_GFASTQ_QUAL 2u
+int msw_gfastq_open_ex(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64_t max_reads, uint32_t flags,
+                       uint64_t span_bytes, msw_gfastq** out);
+/* *quals = the device pointer of quals[n][read_stride] for the batch that the
+ * last msw_gfastq_next returned, NULL for a reader opened without
+ * MSW_GFASTQ_QUAL (and after the end-of-file call, which has no batch).  It
+ * lives as long as that batch's `reads`: two slabs alternate, so it stays
+ * valid until the call after next, and it is written on the stream the batch
+ * was enqueued on.
+ *
+ * The quality-row rule.  Read r of the file (0-based) is valid line 4r + 2,
+ * counted 1-based over the valid lines of the file as above.  Its quality
+ * line is valid line 4r + 4, with the '\r' of a "\r\n" stripped like any
+ * other line.  Row r holds the first min(length of that line, read_stride)
+ * bytes of the line, zero-padded to read_stride.  If the file ends before
+ * valid line 4r + 4 the row is all zeros.  A quality line longer than the
+ * stride is truncated and one shorter than its sequence leaves zeros; neither
+ * is an error (the host reader has no rule for them). */
+int msw_gfastq_quals(const msw_gfastq* g, const uint8_t** quals);
 /* The next batch, enqueued on `stream` (a hipStream_t; NULL = the context's
  * compute stream) -- scoring launched after it on that stream sees it.  The
  * device arrays stay valid until the call after next (two slabs alternate). */

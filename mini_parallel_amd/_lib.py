@@ -37,13 +37,14 @@ EXPORTED = (
     "msw_seed_candidates_device", "msw_seed_candidates", "msw_mapq_select_device", "msw_map_reads",
     "msw_pileup_create", "msw_pileup_destroy", "msw_pileup_add_device", "msw_pileup_add", "msw_pileup_finish",
     "msw_pileup_counts", "msw_pileup_counts_device", "msw_pileup_summary",
+    "msw_pileup_add_qual_device", "msw_pileup_add_qual", "msw_pileup_lowq_columns",
     "msw_call_params_default", "msw_pileup_call_device", "msw_pileup_call", "msw_call_counts",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
                   "msw_fastq_stats", "msw_fastq_count_bases", "msw_is_bgzf", "msw_gfastq_open",
                   "msw_gfastq_next", "msw_gfastq_stats", "msw_gfastq_close", "msw_bgzf_inflate",
-                  "msw_gfastq_reset", "msw_gfastq_prefetch")
+                  "msw_gfastq_reset", "msw_gfastq_prefetch", "msw_gfastq_open_ex", "msw_gfastq_quals")
 
 
 class MswError(RuntimeError):
@@ -206,6 +207,11 @@ def _declare(L):
                                       ctypes.c_uint32, P]),
         "msw_pileup_add": (I, [P, P, P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(AlnT), P, P,
                                ctypes.c_uint32, ctypes.c_uint64]),
+        "msw_pileup_add_qual_device": (I, [P, P, P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(AlnT), P, P,
+                                           ctypes.c_uint32, P, ctypes.c_uint32, ctypes.c_uint32, P]),
+        "msw_pileup_add_qual": (I, [P, P, P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(AlnT), P, P,
+                                    ctypes.c_uint32, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+        "msw_pileup_lowq_columns": (I, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
         "msw_pileup_finish": (I, [P, P, P]),
         "msw_pileup_counts": (I, [P, P, P]),
         "msw_pileup_counts_device": (I, [P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64),
@@ -262,6 +268,9 @@ def _declare(L):
         "msw_is_bgzf": (I, [ctypes.c_char_p]),
         "msw_gfastq_open": (I, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, I, ctypes.c_uint64,
                                 ctypes.POINTER(P)]),
+        "msw_gfastq_open_ex": (I, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                   ctypes.c_uint64, ctypes.POINTER(P)]),
+        "msw_gfastq_quals": (I, [P, ctypes.POINTER(P)]),
         "msw_gfastq_next": (I, [P, P, ctypes.POINTER(DevReadsT)]),
         "msw_gfastq_stats": (None, [P] + [ctypes.POINTER(ctypes.c_uint64)] * 6),
         "msw_gfastq_close": (None, [P]),

@@ -1005,7 +1005,8 @@ class Pileup:
         return self._h
 
     def add(self, reads: np.ndarray, read_len: np.ndarray, ref_pos: np.ndarray, nm: np.ndarray, cigars,
-            strand=None, mapq=None, min_mapq: int = 0, chunk_reads: int = 0) -> None:
+            strand=None, mapq=None, min_mapq: int = 0, chunk_reads: int = 0, quals=None,
+            min_baseq: int = 0) -> None:
         """Add the records of a host batch (msw_pileup_add): ``reads`` and
         ``read_len`` as they went into :meth:`Context.map_reads`,
         :meth:`Context.align_reads_strands` (``trace=True``) or
@@ -1013,7 +1014,10 @@ class Pileup:
         (and ``strand``, ``mapq``) as they came back.  With ``strand`` the
         reverse complement of a strand-1 read is taken on the GPU; without it
         the rows are what the CIGARs refer to.  With ``mapq``, reads below
-        ``min_mapq`` are skipped."""
+        ``min_mapq`` are skipped.  With ``quals`` (uint8[n, qual_stride], one
+        FASTQ quality byte per base of the reads as given) and
+        ``min_baseq`` > 0, M columns whose Phred value is below ``min_baseq``
+        are dropped (msw_pileup_add_qual; :meth:`lowq_columns` counts them)."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
         ref_pos = np.ascontiguousarray(ref_pos, dtype=np.int64)
@@ -1033,18 +1037,43 @@ class Pileup:
                     raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
             opt[name] = a
         aln = AlnT(_ptr(ref_pos) or None, _ptr(nm) or None, _ptr(off), _ptr(cig), int(off[B]), None)
-        check(lib().msw_pileup_add(self.ctx.handle, self.handle, _ptr(reads) if reads.size else None,
-                                   _ptr(read_len) if B else None, reads.shape[1] if reads.ndim == 2 else 0, B,
-                                   ctypes.byref(aln), _ptr(opt["strand"]) if B else None,
-                                   _ptr(opt["mapq"]) if B else None, min_mapq, chunk_reads))
+        if quals is None and min_baseq == 0:
+            check(lib().msw_pileup_add(self.ctx.handle, self.handle, _ptr(reads) if reads.size else None,
+                                       _ptr(read_len) if B else None, reads.shape[1] if reads.ndim == 2 else 0, B,
+                                       ctypes.byref(aln), _ptr(opt["strand"]) if B else None,
+                                       _ptr(opt["mapq"]) if B else None, min_mapq, chunk_reads))
+            return
+        qs = 0
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            if quals.ndim != 2 or quals.shape[0] != B:
+                raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+            qs = quals.shape[1]
+        check(lib().msw_pileup_add_qual(self.ctx.handle, self.handle, _ptr(reads) if reads.size else None,
+                                        _ptr(read_len) if B else None, reads.shape[1] if reads.ndim == 2 else 0, B,
+                                        ctypes.byref(aln), _ptr(opt["strand"]) if B else None,
+                                        _ptr(opt["mapq"]) if B else None, min_mapq,
+                                        _ptr(quals) if quals is not None and quals.size else None, qs, min_baseq,
+                                        chunk_reads))
 
     def add_device(self, rows_ptr: int, read_len_ptr: int, row_stride: int, n: int, ref_pos_ptr: int, nm_ptr: int,
                    cigar_off_ptr: int, cigar_ptr: int, cigar_cap: int, strand_ptr: int = 0, mapq_ptr: int = 0,
-                   min_mapq: int = 0, stream: int = 0) -> None:
+                   min_mapq: int = 0, stream: int = 0, quals_ptr: int = 0, qual_stride: int = 0,
+                   min_baseq: int = 0) -> None:
         """Enqueue the records of n device-resident reads (raw device
         pointers, the arrays msw_aln_pack_device wrote) on ``stream``
-        (msw_pileup_add_device).  ``rows_ptr``: the rows the CIGARs refer to."""
+        (msw_pileup_add_device).  ``rows_ptr``: the rows the CIGARs refer to.
+        ``quals_ptr``: device quality rows in the order of the reads as given
+        (``GpuFastqReader(with_qual=True)``), with ``min_baseq`` > 0 the
+        threshold of msw_pileup_add_qual_device."""
         aln = AlnT(ref_pos_ptr or None, nm_ptr or None, cigar_off_ptr or None, cigar_ptr or None, cigar_cap, None)
+        if quals_ptr or min_baseq:
+            check(lib().msw_pileup_add_qual_device(
+                self.ctx.handle, self.handle, ctypes.c_void_p(rows_ptr or None), ctypes.c_void_p(read_len_ptr or None),
+                row_stride, n, ctypes.byref(aln), ctypes.c_void_p(strand_ptr or None),
+                ctypes.c_void_p(mapq_ptr or None), min_mapq, ctypes.c_void_p(quals_ptr or None), qual_stride,
+                min_baseq, ctypes.c_void_p(stream or None)))
+            return
         check(lib().msw_pileup_add_device(self.ctx.handle, self.handle, ctypes.c_void_p(rows_ptr or None),
                                           ctypes.c_void_p(read_len_ptr or None), row_stride, n, ctypes.byref(aln),
                                           ctypes.c_void_p(strand_ptr or None), ctypes.c_void_p(mapq_ptr or None),
@@ -1054,6 +1083,13 @@ class Pileup:
         """Fold the state into the counts (msw_pileup_finish); afterwards the
         pileup takes no more reads.  A second call does nothing."""
         check(lib().msw_pileup_finish(self.ctx.handle, self.handle, ctypes.c_void_p(stream or None)))
+
+    def lowq_columns(self) -> int:
+        """M columns dropped by ``min_baseq`` so far (msw_pileup_lowq_columns);
+        synchronous, before or after finish()."""
+        n = ctypes.c_uint64()
+        check(lib().msw_pileup_lowq_columns(self.ctx.handle, self.handle, ctypes.byref(n)))
+        return int(n.value)
 
     def counts(self) -> np.ndarray:
         """uint32[glen][8] on the host (msw_pileup_counts); after finish()."""

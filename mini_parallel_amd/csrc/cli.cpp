@@ -101,6 +101,9 @@ void usage() {
         "                               a checkpoint that already lists completed files\n"
         "      --pileup-min-mapq N      --pileup-out with --mapq: reads below this MAPQ do not count, 0..60\n"
         "                               (default 0)\n"
+        "      --pileup-min-baseq N     --pileup-out or --variants-out: M columns whose base quality (Phred+33 in\n"
+        "                               the lane file's quality line) is below this do not count, 0..93\n"
+        "                               (default 0: the quality lines are not read)\n"
         "      --pileup-min-depth N     --pileup-out: least depth of a position in the summary's minority_ref\n"
         "                               (default 4)\n"
         "      --variants-out PATH      --alignments-out: also call variants from the run's pileup (with or without\n"
@@ -158,6 +161,7 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--seed-sep") { a.seed_sep = atoi(v().c_str()); a.has_seed_sep = true; }
         else if (s == "--pileup-out") a.pileup_out = v();
         else if (s == "--pileup-min-mapq") { a.pileup_min_mapq = atoi(v().c_str()); a.has_pileup_min_mapq = true; }
+        else if (s == "--pileup-min-baseq") { a.pileup_min_baseq = atoi(v().c_str()); a.has_pileup_min_baseq = true; }
         else if (s == "--pileup-min-depth") { a.pileup_min_depth = atoi(v().c_str()); a.has_pileup_min_depth = true; }
         else if (s == "--variants-out") a.variants_out = v();
         else if (s == "--call-min-depth") { a.call_min_depth = atol(v().c_str()); a.has_call_flag = true; }
@@ -212,6 +216,9 @@ Args parse_args(int argc, char** argv) {
         die("error: --pileup-min-mapq needs --pileup-out and --mapq");
     if (a.has_pileup_min_mapq && (a.pileup_min_mapq < 0 || a.pileup_min_mapq > 60))
         die("error: --pileup-min-mapq must be 0..60");
+    if (a.has_pileup_min_baseq && !a.wants_pileup()) die("error: --pileup-min-baseq needs --pileup-out or --variants-out");
+    if (a.has_pileup_min_baseq && (a.pileup_min_baseq < 0 || a.pileup_min_baseq > 93))
+        die("error: --pileup-min-baseq must be 0..93");
     if (a.has_pileup_min_depth && a.pileup_out.empty()) die("error: --pileup-min-depth needs --pileup-out");
     if (a.has_pileup_min_depth && a.pileup_min_depth < 1) die("error: --pileup-min-depth must be at least 1");
     if (a.has_call_flag && a.variants_out.empty()) die("error: the --call-* thresholds need --variants-out");
@@ -343,6 +350,8 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
         key += "|variants|" + std::to_string(a.pileup_min_mapq) + "," + std::to_string(a.call_min_depth) + "," +
                std::to_string(a.call_min_alt) + "," + std::to_string(a.call_min_alt_permille) + "," +
                std::to_string(a.call_min_qual);
+    // nor does either with a base-quality threshold resume one without, or one with another (0 is the run without)
+    if (a.wants_pileup() && a.pileup_min_baseq > 0) key += "|baseq|" + std::to_string(a.pileup_min_baseq);
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -508,7 +517,10 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
           << ", \"min_depth\": " << a.pileup_min_depth << ", \"reads_used\": " << p.reads_used
           << ", \"reads_skipped\": " << p.reads_skipped << ", \"covered\": " << p.covered
           << ", \"depth_sum\": " << p.depth_sum << ", \"max_depth\": " << p.max_depth
-          << ", \"minority_ref\": " << p.minority_ref << ", \"pileup_ms\": " << p.ms << "}";
+          << ", \"minority_ref\": " << p.minority_ref;
+        // --pileup-min-baseq above 0 only: the threshold and the M columns it dropped, over the workers
+        if (a.pileup_min_baseq > 0) j << ", \"min_baseq\": " << a.pileup_min_baseq << ", \"lowq_columns\": " << p.lowq_columns;
+        j << ", \"pileup_ms\": " << p.ms << "}";
     }
     // --variants-out only
     if (rep.variants.on) {
@@ -520,7 +532,9 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
           << ", \"q_hit\": " << q.q_hit << ", \"q_miss\": " << q.q_miss << ", \"q_het\": " << q.q_het
           << ", \"prior_het\": " << q.prior_het << ", \"prior_hom\": " << q.prior_hom << "}, \"records\": " << v.total
           << ", \"snv\": " << v.by_kind[0] << ", \"del\": " << v.by_kind[1] << ", \"ins\": " << v.by_kind[2]
-          << ", \"het\": " << v.by_gt[1] << ", \"hom\": " << v.by_gt[2] << ", \"variants_ms\": " << v.ms << "}";
+          << ", \"het\": " << v.by_gt[1] << ", \"hom\": " << v.by_gt[2];
+        if (a.pileup_min_baseq > 0) j << ", \"min_baseq\": " << a.pileup_min_baseq << ", \"lowq_columns\": " << v.lowq_columns;
+        j << ", \"variants_ms\": " << v.ms << "}";
     }
     j
       << ", \"inflate_bytes_in\": " << rep.gz_in << ", \"inflate_bytes_out\": " << rep.gz_out

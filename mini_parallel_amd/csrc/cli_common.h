@@ -86,6 +86,10 @@ struct Args {
     std::string pileup_out;
     bool has_pileup_min_mapq = false, has_pileup_min_depth = false;
     int pileup_min_mapq = 0, pileup_min_depth = 4;
+    // --pileup-min-baseq: M columns whose base quality (Phred, from the lane file's quality line) is below it
+    // do not count; above 0 the workers' readers keep the quality lines (MSW_GFASTQ_QUAL)
+    bool has_pileup_min_baseq = false;
+    int pileup_min_baseq = 0;
     // --variants-out: the variant calls of the run's pileup (one .var file; include/msw.h, "Variants"), with the
     // thresholds of --call-min-depth / -alt / -alt-permille / -qual over msw_call_params_default
     std::string variants_out;

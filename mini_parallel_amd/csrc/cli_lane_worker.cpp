@@ -19,6 +19,7 @@ struct LaneEnv {
     uint64_t batch;
     int gi;
     msw_pileup* pile;  // --pileup-out: this worker's pileup, else null
+    uint32_t min_baseq;  // --pileup-min-baseq; above 0 the reader keeps quality rows
 };
 
 // The pinned result block of a set: score i32 | ei i16 | ej i16 | rlen u16 | wlen u16, each [batch]
@@ -59,6 +60,8 @@ struct AlnSet {
     uint64_t ops_cap = 0;
     HostAln h;
     msw_dev_reads_t d{};  // the batch's device arrays (valid until the reader's call after next)
+    const uint8_t* quals = nullptr;  // --pileup-min-baseq: the batch's quality rows, of the same lifetime
+    uint32_t qual_stride = 0;
     void* stream = nullptr;
     uint32_t stride = 0;  // of the rows the offsets on the host were packed from
     const uint32_t* rows = nullptr;
@@ -164,8 +167,12 @@ struct AlnSet {
         }
         if (good && e.pile) {
             const msw_aln_t al{d_ref, d_nm, d_off, d_ops, ops_cap, d_off + e.batch + 1};
-            good = msw_pileup_add_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al, strand, mapq,
-                                         (uint32_t)e.a->pileup_min_mapq, stream) == MSW_OK;
+            // the quality rows are the reader's, in the order of the file, whichever way d.reads is oriented
+            good = (e.min_baseq ? msw_pileup_add_qual_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al,
+                                                             strand, mapq, (uint32_t)e.a->pileup_min_mapq, quals,
+                                                             qual_stride, e.min_baseq, stream)
+                                : msw_pileup_add_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al, strand,
+                                                        mapq, (uint32_t)e.a->pileup_min_mapq, stream)) == MSW_OK;
         }
         if (good) {
             n_ops = h.off[n];
@@ -258,6 +265,8 @@ class LaneWorker {
     msw_genome* gen_ = nullptr;
     msw_index* idx_ = nullptr;  // --map
     msw_pileup* pile_ = nullptr;  // --pileup-out
+    uint32_t min_baseq_ = 0;      // --pileup-min-baseq (0: the reader keeps no qualities)
+    const uint8_t* batch_quals_ = nullptr;  // the quality rows of the batch next_batch returned last
     msw_seed_params_t seed_{};
     LaneEnv env_;
     ResultSet res_[2];
@@ -287,7 +296,10 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     if (lanes_.per_read && msw_stream_create(ctx_.h, &streams_[1]) != MSW_OK)
         die(std::string("GPU stream: ") + msw_last_error());
     const double t_ctx = ms_since(ts0_);
-    if (msw_gfastq_open(ctx_.h, nullptr, read_stride(), batch_, 1, 0, &gr_) != MSW_OK)
+    // --pileup-min-baseq above 0: the reader keeps the records' quality lines beside the reads
+    min_baseq_ = lanes_.pileup && a_.pileup_min_baseq > 0 ? (uint32_t)a_.pileup_min_baseq : 0u;
+    if ((min_baseq_ ? msw_gfastq_open_ex(ctx_.h, nullptr, read_stride(), batch_, MSW_GFASTQ_POS | MSW_GFASTQ_QUAL, 0, &gr_)
+                    : msw_gfastq_open(ctx_.h, nullptr, read_stride(), batch_, 1, 0, &gr_)) != MSW_OK)
         die(std::string("GPU lane reader: ") + msw_last_error());
     const double t_rd = ms_since(ts0_) - t_ctx;
     // the first file: claimed now and opened / pinned on the
@@ -321,7 +333,7 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     // --pileup-out: this worker's pileup of the genome just uploaded, before the clock
     if (lanes_.pileup && msw_pileup_create(ctx_.h, gen_, &pile_) != MSW_OK)
         die(std::string("GPU pileup error: ") + msw_last_error());
-    env_ = LaneEnv{ctx_.h, &sc_, gen_, &a_, batch_, gi_, pile_};
+    env_ = LaneEnv{ctx_.h, &sc_, gen_, &a_, batch_, gi_, pile_, min_baseq_};
     if (aln_) aln_stride_ = (uint32_t)std::min(4480L, std::max(1L, atol(env_or("MSW_CLI_CIGAR_STRIDE", "16").c_str())));
     for (ResultSet& r : res_) {
         r.d_score = (int32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
@@ -468,6 +480,8 @@ bool LaneWorker::next_batch(size_t fi, void* stream, msw_dev_reads_t* d) {
         reader_done(fi);
         return false;
     }
+    batch_quals_ = nullptr;
+    if (min_baseq_ && msw_gfastq_quals(gr_, &batch_quals_) != MSW_OK) batch_quals_ = nullptr;
     run_.trace_ev(wi_, "batch", d->n);
     if (d->n == 0) reader_done(fi);
     return d->n != 0;
@@ -499,9 +513,11 @@ void LaneWorker::collect_pileup() {
     const size_t words = (size_t)msw_genome_length(gen_) * 8;
     std::vector<uint32_t> mine(words);
     msw_pileup_summary_t s;
+    uint64_t lowq = 0;
     const bool ok = msw_pileup_finish(ctx_.h, pile_, nullptr) == MSW_OK &&
                     msw_pileup_counts(ctx_.h, pile_, mine.data()) == MSW_OK &&
-                    msw_pileup_summary(ctx_.h, pile_, 1, &s) == MSW_OK;
+                    msw_pileup_summary(ctx_.h, pile_, 1, &s) == MSW_OK &&
+                    (!min_baseq_ || msw_pileup_lowq_columns(ctx_.h, pile_, &lowq) == MSW_OK);
     if (!ok) fprintf(stderr, "  GPU %d pileup error: %s\n", gi_, msw_last_error());
     std::lock_guard<std::mutex> lk(lanes_.pile_mu);
     if (!ok) {
@@ -516,6 +532,7 @@ void LaneWorker::collect_pileup() {
     }
     lanes_.pile_used += s.reads_used;
     lanes_.pile_skipped += s.reads_skipped;
+    lanes_.pile_lowq += lowq;
 }
 
 // host side of a finished batch: sums, cells, per-read records, then this
@@ -649,7 +666,8 @@ bool LaneWorker::submit(ResultSet& r, const msw_dev_reads_t& d, size_t fi, void*
                              msw_memcpy_d2h_async(ctx_.h, r.h.end_j, r.d_ej, d.n * 2, stream) != MSW_OK)) ||
         msw_memcpy_d2h_async(ctx_.h, r.h.read_len, d.read_len, d.n * 2, stream) != MSW_OK ||
         msw_memcpy_d2h_async(ctx_.h, r.h.win_len, r.d_wlen, d.n * 2, stream) != MSW_OK ||
-        (aln_ ? (r.aln.d = da, r.aln.stream = stream, !r.aln.run(env_, o, aln_stride_, r.aln.d_rows, true))
+        (aln_ ? (r.aln.d = da, r.aln.quals = batch_quals_, r.aln.qual_stride = d.read_stride, r.aln.stream = stream,
+                 !r.aln.run(env_, o, aln_stride_, r.aln.d_rows, true))
               : msw_fence_record(ctx_.h, stream, &r.fence) != MSW_OK)) {
         fprintf(stderr, "  GPU %d alignment error: %s\n", gi_, msw_last_error());
         f.failed = true;

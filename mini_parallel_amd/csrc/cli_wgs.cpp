@@ -278,6 +278,7 @@ static void write_pileup(WgsRun& run, LaneRun& lanes) {
     p.on = true;
     p.reads_used = lanes.pile_used;
     p.reads_skipped = lanes.pile_skipped;
+    p.lowq_columns = lanes.pile_lowq;
     const unsigned long long min_depth = (unsigned long long)run.a.pileup_min_depth;
     for (uint64_t pos = 0; pos < glen; ++pos) {
         const uint32_t* row = c.data() + pos * 8;
@@ -334,6 +335,7 @@ static void write_variants(WgsRun& run, LaneRun& lanes) {
     }
     VariantsReport& v = run.variants;
     v.on = true;
+    v.lowq_columns = lanes.pile_lowq;
     v.total = recs.size();
     for (const msw_variant_t& r : recs) {
         if (r.kind < 3) ++v.by_kind[r.kind];

@@ -97,6 +97,7 @@ struct StartGate {
 struct PileupReport {
     bool on = false;
     unsigned long long reads_used = 0, reads_skipped = 0, covered = 0, depth_sum = 0, max_depth = 0, minority_ref = 0;
+    unsigned long long lowq_columns = 0;  // --pileup-min-baseq: M columns under the threshold, over the workers
     double ms = 0;
 };
 
@@ -105,6 +106,7 @@ struct PileupReport {
 struct VariantsReport {
     bool on = false;
     unsigned long long total = 0, by_kind[3] = {0, 0, 0}, by_gt[3] = {0, 0, 0};
+    unsigned long long lowq_columns = 0;  // as PileupReport's (a run may have --variants-out alone)
     double ms = 0;
 };
 
@@ -225,7 +227,7 @@ struct LaneRun {
     const bool pileup;
     std::mutex pile_mu;
     std::vector<uint32_t> pile_sum;
-    unsigned long long pile_used = 0, pile_skipped = 0;
+    unsigned long long pile_used = 0, pile_skipped = 0, pile_lowq = 0;
     bool pile_failed = false;
 
     static constexpr size_t kNone = ~(size_t)0;

@@ -15,7 +15,10 @@
 //           parse phase A (line counts) -> host sizes the line arrays ->
 //           phase B (line ends, UTF-8 pass if needed, lengths, carried state)
 //   emit    per batch of max_reads: sequences into a device slab (two slabs
-//           alternate), enqueued on the caller's stream after the parse
+//           alternate), enqueued on the caller's stream after the parse; a
+//           reader opened with MSW_GFASTQ_QUAL also emits the records'
+//           quality lines into a second pair of slabs, and its spans end at
+//           whole records (what is carried is then a partial record)
 // The reader has its own stream, so the next span inflates while the caller's
 // scoring of the current batch runs.
 #include <hip/hip_runtime.h>
@@ -62,6 +65,7 @@ namespace {
     } while (0)
 
 constexpr uint64_t kCarry = 64u << 10;     // room in front of a span for the previous span's last line
+constexpr uint64_t kQualHeader = 4u << 10;  // quality mode: header and '+' line bytes a carried record may hold
 constexpr uint64_t kPad = 256;             // device buffers: slack past the end for wide loads
 constexpr uint64_t kReadPiece = 8u << 20;  // compressed bytes per fread
 constexpr uint64_t kInPad = 1024;          // past the compressed bytes: the inflate input window reads <= 520 B
@@ -326,6 +330,12 @@ struct msw_gfastq {
     uint32_t stride = 0;
     uint64_t max_reads = 0;
     bool want_pos = false;
+    // MSW_GFASTQ_QUAL: quality rows beside the read rows.  A span then ends
+    // at a record boundary (msw_parse.hip), so what is carried in front of the
+    // next span is a partial record, not a partial line: carry_cap is sized
+    // for one at open, from the stride.
+    bool want_qual = false;
+    uint64_t carry_cap = kCarry;       // room in front of a span
     uint64_t span = kDefaultSpan;
 
     // compressed bytes read but not yet inflated: hc[0, hc_len).  Two ways
@@ -408,7 +418,7 @@ struct msw_gfastq {
     Inflater inf;
     std::vector<msw::GzMember> mem;
 
-    // span buffers: [kCarry | span + kPad]; cur = the parsed one (-1: none yet in this file)
+    // span buffers: [carry_cap | span + kPad]; cur = the parsed one (-1: none yet in this file)
     uint8_t* dout[2] = {nullptr, nullptr};
     int cur = -1;
     uint64_t cur_off = 0, cur_len = 0, tail_start = 0;  // parse window [cur_off, cur_off + cur_len) of dout[cur]
@@ -432,9 +442,12 @@ struct msw_gfastq {
     uint8_t* s_reads[2] = {nullptr, nullptr};
     uint16_t* s_rlen[2] = {nullptr, nullptr};
     int64_t* s_pos[2] = {nullptr, nullptr};
+    uint8_t* s_qual[2] = {nullptr, nullptr};  // quality mode
+    const uint8_t* last_quals = nullptr;      // the last batch's (msw_gfastq_quals)
     int slot = 0;
 
     uint64_t span_reads = 0, span_done = 0, next_first = 0;
+    uint64_t span_valid = 0;                // valid lines of the parsed span (the quality emit's bound)
     uint32_t span_min = 0, span_max = 0;
     uint64_t spans = 0;                     // spans parsed over the reader's life (all files)
     uint64_t bucket_reads = 1;              // reads per span_bmax entry
@@ -515,6 +528,7 @@ void release(msw_gfastq* g) {
         if (g->s_reads[i]) (void)hipFree(g->s_reads[i]);
         if (g->s_rlen[i]) (void)hipFree(g->s_rlen[i]);
         if (g->s_pos[i]) (void)hipFree(g->s_pos[i]);
+        if (g->s_qual[i]) (void)hipFree(g->s_qual[i]);
     }
     if (g->tile_nl) (void)hipFree(g->tile_nl);
     if (g->tile_hi) (void)hipFree(g->tile_hi);
@@ -769,7 +783,7 @@ int next_span(msw_gfastq* g) {
         g->pre_indexed = false;
     } else {
         for (;;) {
-            if ((rc = index_members(g->hc, g->hc_len, kCarry, cap, g->in_cap, g->mem, &used, &obytes))) return rc;
+            if ((rc = index_members(g->hc, g->hc_len, g->carry_cap, cap, g->in_cap, g->mem, &used, &obytes))) return rc;
             const bool full = obytes + 65536 > cap || g->fread_off >= g->fsize || g->hc_len == g->hc_cap;
             if (full) break;
             g->mem.clear();
@@ -792,7 +806,7 @@ int next_span(msw_gfastq* g) {
     // emits and the caller's scoring keep running
     for (int j = 0; j < 2; ++j)
         if (g->emitted_valid[nx][j]) GZ_TRY(hipStreamWaitEvent(s, g->emitted[nx][j], 0));
-    // 2. inflate + CRC into dout[nx] at kCarry (mapped: the upload starts at
+    // 2. inflate + CRC into dout[nx] at carry_cap (mapped: the upload starts at
     // the page boundary below hc, inside the registered window)
     const size_t lead = g->mapped ? (size_t)(g->map_off - g->reg_lo) : 0;
     if (lead)
@@ -819,22 +833,24 @@ int next_span(msw_gfastq* g) {
     }
     if ((rc = g->inf.run(g->hc - lead, used + lead, g->mem, g->dout[nx], s, in_place, pre))) return rc;
     const double t_run = trace ? now_ms() : 0.0;
-    // 3. the previous span's unfinished line goes right in front
+    // 3. the previous span's unfinished line (quality mode: unfinished record) goes right in front
+    const uint64_t kc = g->carry_cap;
     const uint64_t carry = g->cur < 0 ? 0 : g->cur_len - g->tail_start;
-    if (carry > kCarry)
-        return set_error(MSW_E_RANGE, "Error reading %s: a line longer than %llu bytes", g->path.c_str(),
-                         (unsigned long long)kCarry);
+    if (carry > kc)
+        return set_error(MSW_E_RANGE, "Error reading %s: a %s longer than %llu bytes", g->path.c_str(),
+                         g->want_qual ? "record" : "line", (unsigned long long)kc);
     if (carry)
-        GZ_TRY(hipMemcpyAsync(g->dout[nx] + kCarry - carry, g->dout[g->cur] + g->cur_off + g->tail_start, carry,
+        GZ_TRY(hipMemcpyAsync(g->dout[nx] + kc - carry, g->dout[g->cur] + g->cur_off + g->tail_start, carry,
                               hipMemcpyDeviceToDevice, s));
-    // 4. parse phase A over [kCarry - carry, kCarry + obytes), from a 16-byte aligned base
+    // 4. parse phase A over [kc - carry, kc + obytes), from a 16-byte aligned base
     msw::ParseBufs& b = g->pb[nx];
-    const uint64_t base = (kCarry - carry) & ~(uint64_t)15;
+    const uint64_t base = (kc - carry) & ~(uint64_t)15;
     b.buf = g->dout[nx] + base;
-    b.begin = (uint32_t)(kCarry - carry - base);
-    b.len = kCarry + obytes - base;
+    b.begin = (uint32_t)(kc - carry - base);
+    b.len = kc + obytes - base;
     b.eof = last ? 1u : 0u;
     b.want_pos = g->want_pos ? 1u : 0u;
+    b.qual = g->want_qual ? 1u : 0u;
     b.ntiles = (uint32_t)((b.len + msw::kParseTile - 1) / msw::kParseTile);
     if ((rc = grow(&g->tile_nl, &g->tile_cap, (size_t)b.ntiles + 1))) return rc;
     if ((rc = grow(&g->tile_hi, &g->tile_hi_cap, (size_t)b.ntiles + 1))) return rc;
@@ -911,6 +927,7 @@ int next_span(msw_gfastq* g) {
     g->started = true;
     g->at_eof = last;
     g->span_reads = o.reads;
+    g->span_valid = o.valid;
     g->span_done = 0;
     ++g->spans;
     g->span_min = o.min_len;
@@ -921,7 +938,7 @@ int next_span(msw_gfastq* g) {
     g->sp.pending_in = o.pending_in;
     g->sp.any_high = o.any_high;
     g->lines += o.valid;
-    g->errors += o.lines - o.valid;
+    g->errors += o.counted - o.valid;
     g->reads += o.reads;
     g->bases += o.bases;
     upload_ahead(g);
@@ -1047,8 +1064,14 @@ int msw_is_bgzf(const char* path) {
 
 int msw_gfastq_open(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64_t max_reads, int want_pos,
                     uint64_t span_bytes, msw_gfastq** out) {
+    return msw_gfastq_open_ex(ctx, path, read_stride, max_reads, want_pos ? MSW_GFASTQ_POS : 0u, span_bytes, out);
+}
+
+int msw_gfastq_open_ex(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64_t max_reads, uint32_t flags,
+                       uint64_t span_bytes, msw_gfastq** out) {
     if (!ctx || !out) return set_error(MSW_E_INVALID, "ctx/out is NULL");
     *out = nullptr;
+    if (flags & ~(MSW_GFASTQ_POS | MSW_GFASTQ_QUAL)) return set_error(MSW_E_INVALID, "unknown reader flags 0x%x", flags);
     if (read_stride == 0 || read_stride % 16 || read_stride > 32768)
         return set_error(MSW_E_INVALID, "read_stride %u must be a multiple of 16 in [16, 32768]", read_stride);
     if (max_reads == 0) return set_error(MSW_E_INVALID, "max_reads is 0");
@@ -1058,7 +1081,12 @@ int msw_gfastq_open(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64
     g->path = path ? path : "";
     g->stride = read_stride;
     g->max_reads = max_reads;
-    g->want_pos = want_pos != 0;
+    g->want_pos = (flags & MSW_GFASTQ_POS) != 0;
+    g->want_qual = (flags & MSW_GFASTQ_QUAL) != 0;
+    // a whole record less one byte may be carried: two lines of up to the
+    // stride, a header and a '+' line of up to kQualHeader, four line ends
+    if (g->want_qual)
+        g->carry_cap = std::max<uint64_t>(kCarry, (2ull * read_stride + 2 * kQualHeader + 8 + 4095) & ~4095ull);
     {
         const char* et = getenv("MSW_GZ_READ_THREADS");
         g->read_threads = std::max(1, std::min(8, et ? atoi(et) : 4));
@@ -1127,12 +1155,13 @@ int msw_gfastq_open(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64
         // other buffers (~85 ms per 512 MB), not at the first file's read
         if (g->no_map && (rc = ensure_stage(g))) return bail(rc);
     }
-    const size_t ob = (size_t)(kCarry + g->span + kPad);
+    const size_t ob = (size_t)(g->carry_cap + g->span + kPad);
     for (int i = 0; i < 2; ++i) {
         if (hipMalloc((void**)&g->dout[i], ob) != hipSuccess ||
             hipMalloc((void**)&g->s_reads[i], (size_t)max_reads * read_stride + kPad) != hipSuccess ||
             hipMalloc((void**)&g->s_rlen[i], (size_t)max_reads * 2 + kPad) != hipSuccess ||
-            (g->want_pos && hipMalloc((void**)&g->s_pos[i], (size_t)max_reads * 8 + kPad) != hipSuccess))
+            (g->want_pos && hipMalloc((void**)&g->s_pos[i], (size_t)max_reads * 8 + kPad) != hipSuccess) ||
+            (g->want_qual && hipMalloc((void**)&g->s_qual[i], (size_t)max_reads * read_stride + kPad) != hipSuccess))
             return bail(set_error(MSW_E_NOMEM, "hipMalloc failed (GPU lane reader buffers, span %llu MiB)",
                                   (unsigned long long)(g->span >> 20)));
     }
@@ -1146,7 +1175,7 @@ int msw_gfastq_open(msw_ctx* ctx, const char* path, uint32_t read_stride, uint64
     {
         const size_t lines = (size_t)(g->span / 32) + 1024;
         const size_t members = (size_t)(g->span / 32768) + 1024;  // BGZF members hold <= 64 KiB
-        const size_t tiles = (size_t)((kCarry + g->span + 16 + msw::kParseTile - 1) / msw::kParseTile) + 1;
+        const size_t tiles = (size_t)((g->carry_cap + g->span + 16 + msw::kParseTile - 1) / msw::kParseTile) + 1;
         if (!g->no_map) {
             g->d_ahead_cap = g->in_cap + 4096 + kInPad;
             if (hipMalloc((void**)&g->d_ahead, g->d_ahead_cap) != hipSuccess) {
@@ -1194,12 +1223,12 @@ int msw_gfastq_prefetch(msw_gfastq* g, const char* path) {
     g->pf.path = path;
     g->pf.done.store(false, std::memory_order_relaxed);
     const size_t cap = g->in_cap;
-    const uint64_t span = g->span;
+    const uint64_t span = g->span, out_base = g->carry_cap;
     const int device = g->device;
     msw_gfastq::Prefetch* p = &g->pf;
     std::atomic<bool>* gate = &g->first_span_in;
     try {
-        p->th = std::thread([p, cap, span, device, gate]() {
+        p->th = std::thread([p, cap, span, out_base, device, gate]() {
             struct Done {
                 std::atomic<bool>& d;
                 ~Done() { d.store(true, std::memory_order_release); }
@@ -1237,7 +1266,7 @@ int msw_gfastq_prefetch(msw_gfastq* g, const char* path) {
             // fresh file (hc = the window, full on the first pass); an error
             // leaves it to next_span, which reports it
             p->mem.clear();
-            p->indexed = index_members(p->map, (size_t)hi, kCarry, span, cap, p->mem, &p->used, &p->obytes) == 0;
+            p->indexed = index_members(p->map, (size_t)hi, out_base, span, cap, p->mem, &p->used, &p->obytes) == 0;
         });
     } catch (const std::exception&) {
         g->pf.path.clear();  // no thread to spare: reset opens it then
@@ -1249,6 +1278,7 @@ int msw_gfastq_next(msw_gfastq* g, void* stream, msw_dev_reads_t* out) {
     if (!g || !out) return set_error(MSW_E_INVALID, "reader/out is NULL");
     memset(out, 0, sizeof(*out));
     out->read_stride = g->stride;
+    g->last_quals = nullptr;
     if (g->failed)
         return set_error(g->failed, g->path.empty() ? "GPU lane reader: no file (msw_gfastq_reset first)"
                                                     : "Error reading %s: the reader failed earlier",
@@ -1272,6 +1302,10 @@ int msw_gfastq_next(msw_gfastq* g, void* stream, msw_dev_reads_t* out) {
     GZ_TRY(hipStreamWaitEvent(cs, g->parsed, 0));
     GZ_TRY(msw::launch_emit_reads(g->pb[g->cur], g->sp, g->span_done, n, g->s_reads[k], g->s_rlen[k],
                                   g->want_pos ? g->s_pos[k] : nullptr, cs));
+    if (g->want_qual) {
+        GZ_TRY(msw::launch_emit_quals(g->pb[g->cur], g->sp, g->span_valid, g->span_done, n, g->s_qual[k], cs));
+        g->last_quals = g->s_qual[k];
+    }
     {
         const int j = g->emit_slot[g->cur];
         g->emit_slot[g->cur] ^= 1;
@@ -1288,6 +1322,12 @@ int msw_gfastq_next(msw_gfastq* g, void* stream, msw_dev_reads_t* out) {
     out->max_len = g->span_bmax[std::min<uint64_t>(g->span_done / g->bucket_reads, msw::kLenBuckets - 1)];
     g->span_done += n;
     g->next_first += n;
+    return MSW_OK;
+}
+
+int msw_gfastq_quals(const msw_gfastq* g, const uint8_t** quals) {
+    if (!g || !quals) return set_error(MSW_E_INVALID, "reader/quals is NULL");
+    *quals = g->last_quals;
     return MSW_OK;
 }
 

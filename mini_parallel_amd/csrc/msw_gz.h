@@ -81,7 +81,7 @@ struct ParseState {   // device-resident, carried from span to span
 struct ParseOut {     // per span, read back by the host
     uint64_t lines;         // complete lines in the span (incl. invalid ones; + a final line at EOF)
     uint64_t newlines;      // '\n' bytes in the span
-    uint64_t tail_start;    // first byte after the last newline (the carry), len at EOF
+    uint64_t tail_start;    // first byte after the last counted line (the carry), len at EOF
     uint64_t valid;         // valid lines in the span
     uint64_t reads;         // reads (sequence lines) in the span
     uint64_t bases;         // sum of their lengths
@@ -98,6 +98,9 @@ struct ParseOut {     // per span, read back by the host
     // (a batch of the reader lies inside one run): the batch's bound, so one
     // long read sends only its own batch to a wider kernel, not the span
     uint32_t bmax[kLenBuckets];
+    // lines the span accounts for: `lines`, or in quality mode the lines through its last counted valid
+    // line (the invalid lines among them are the span's errors; the rest are seen again by the next span)
+    uint64_t counted;
 };
 
 struct ParseBufs {
@@ -106,6 +109,7 @@ struct ParseBufs {
     uint32_t begin;         // < 16: the span starts that far into the aligned base
     uint32_t eof;           // last span of the file: a final line without '\n' counts
     uint32_t want_pos;
+    uint32_t qual;          // quality mode: a span that is not the file's last ends at a record boundary
     uint32_t* tile_nl;      // per tile: newlines, then their exclusive scan
     uint32_t* tile_hi;      // per tile: any byte >= 0x80
     uint32_t ntiles;
@@ -137,5 +141,9 @@ struct EmitSpan {     // facts of the parsed span the emit kernel needs (host co
 // (reads[count][stride], read_len[count], pos[count] when pos != NULL).
 hipError_t launch_emit_reads(const ParseBufs& b, const EmitSpan& sp, uint64_t r_begin, uint64_t count,
                              uint8_t* reads, uint16_t* read_len, int64_t* pos, hipStream_t stream);
+// The quality lines of the same reads into quals[count][stride] (the
+// quality-row rule of msw_fastq.h); valid = ParseOut::valid of the span.
+hipError_t launch_emit_quals(const ParseBufs& b, const EmitSpan& sp, uint64_t valid, uint64_t r_begin, uint64_t count,
+                             uint8_t* quals, hipStream_t stream);
 
 }  // namespace msw

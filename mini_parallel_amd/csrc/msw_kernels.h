@@ -351,6 +351,16 @@ struct PileupParams {
 // u32 words of scan temporaries pileup_finish needs for a genome of glen bases
 uint64_t pileup_scan_tmp_words(uint64_t glen);
 hipError_t launch_pileup_add(const PileupParams& p, hipStream_t stream);
+// The base-quality filter of an add (msw.h, "Base qualities"): a kernel instance of its own takes it
+// beside the params, so the plain add's arguments and code stay as they are.
+struct PileupQual {
+    const uint8_t* quals;       // quals[n][qual_stride], rows in the order of the reads as given
+    uint32_t qual_stride;
+    uint32_t min_baseq;         // 1..93
+    // low-quality columns: kPileupReadSlots counters, one per 128-byte line (slot s at lowq[s * kPileupReadSlotWords])
+    unsigned long long* lowq;
+};
+hipError_t launch_pileup_add_qual(const PileupParams& p, const PileupQual& q, hipStream_t stream);
 // blocks per CU of pileup_add_kernel; the query loads the module
 int pileup_blocks_per_cu();
 // scans d_all and d_rev in place and folds them and mism into counts

@@ -17,8 +17,14 @@
 //   fin     one lane: reads in the span, the carry, the state for the next span
 //   emit    per read, 16 lanes: the sequence into a zero-padded slab row with
 //           16-byte stores, and the header's pos= (after all of the above)
+//   qual    (readers opened with MSW_GFASTQ_QUAL) per read, 16 lanes: the
+//           record's quality line into a row of a second slab, the same way
 // The valid-line numbering continues across spans through ParseState, so a
 // record may straddle two spans (the host carries the unfinished line).
+// Quality mode (ParseBufs::qual) cuts a span at a record instead: every span
+// but the file's last counts valid lines only through the last one whose file
+// number is a multiple of 4, the bytes after it are the carry, and an invalid
+// line behind that cut is left for the next span to count.
 #include <algorithm>
 
 #include "msw_gz.h"
@@ -268,10 +274,11 @@ __global__ __launch_bounds__(256) void k_scan_tiles(ParseBufs b) {
         o->lines = lines;
         o->newlines = tot;
         o->tail_start = 0;
-        o->valid = lines;  // unless the UTF-8 pass says otherwise
+        o->v0 = b.state->valid_lines;
+        // unless the UTF-8 pass says otherwise; quality mode: whole records (v0 % 4 == 0 at every span)
+        o->valid = b.qual && !b.eof ? lines - ((o->v0 + lines) & 3u) : lines;
         o->reads = 0;
         o->bases = 0;
-        o->v0 = b.state->valid_lines;
         o->pending_in = b.state->pending_pos;
         o->any_high = anyh ? 1u : 0u;
         o->overflow = lines > b.line_cap ? 1u : 0u;
@@ -356,7 +363,7 @@ __global__ __launch_bounds__(1024) void k_vscan(ParseBufs b) {
         b.blk[i] = pre;
         pre += c;
     }
-    if (t == 0) o->valid = tot;
+    if (t == 0) o->valid = b.qual && !b.eof ? tot - (uint32_t)((o->v0 + tot) & 3u) : tot;
 }
 
 __global__ __launch_bounds__(256) void k_vapply(ParseBufs b) {
@@ -364,6 +371,8 @@ __global__ __launch_bounds__(256) void k_vapply(ParseBufs b) {
     if (!o->any_high || o->overflow) return;
     const uint64_t nl = o->lines, nch = (nl + kScanChunk - 1) / kScanChunk;
     const uint64_t err0 = b.state->errors;
+    // quality mode: lines after valid line `cut` are behind the span's cut; the next span counts them
+    const uint64_t cut = b.qual && !b.eof ? o->valid : ~0ull;
     for (uint64_t c = blockIdx.x; c < nch; c += gridDim.x) {
         uint32_t f[4], s = 0;
         for (uint32_t i = 0; i < 4; ++i) {
@@ -383,7 +392,7 @@ __global__ __launch_bounds__(256) void k_vapply(ParseBufs b) {
             } else {
                 b.vidx[k] = ~0u;
                 // this line is invalid line number err0 + (k - idx) + 1 of the file
-                if (err0 + (k - idx) == 10) {
+                if (idx < cut && err0 + (k - idx) == 10) {
                     o->err_over = 1;
                     o->err_line = o->v0 + idx;
                 }
@@ -472,7 +481,11 @@ __global__ void k_fin(ParseBufs b) {
     if (o->overflow) return;
     const uint64_t V = o->valid, v0 = o->v0;
     o->reads = reads_in(V, v0);
-    o->tail_start = b.eof ? b.len : (o->newlines ? (uint64_t)b.line_end[o->newlines - 1] + 1 : b.begin);
+    // lines this span accounts for: all of them, or (quality mode) those through its last counted valid line
+    uint64_t counted = o->lines;
+    if (b.qual && !b.eof) counted = V ? (uint64_t)(o->any_high ? b.vline[V - 1] : V - 1) + 1 : 0;
+    o->counted = counted;
+    o->tail_start = b.eof ? b.len : (counted && o->newlines ? (uint64_t)b.line_end[counted - 1] + 1 : b.begin);
     if (o->min_len == 0xFFFFFFFFu) o->min_len = 0;
     int64_t pend = st->pending_pos;
     if (V > 0) {
@@ -485,7 +498,7 @@ __global__ void k_fin(ParseBufs b) {
         }
     }
     st->valid_lines = v0 + V;
-    st->errors += o->lines - V;
+    st->errors += counted - V;
     st->reads += o->reads;
     st->pending_pos = pend;
 }
@@ -534,6 +547,44 @@ __global__ __launch_bounds__(256) void k_emit(ParseBufs b, EmitSpan sp, uint64_t
     }
 }
 
+// The quality line of each read (valid line j + 2 after its sequence line j)
+// into quals[count][stride], the way k_emit writes the sequences: the first
+// min(length, stride) bytes, zero-padded; all zeros when the file ends before
+// that line (only a file's last span has such reads: `valid` is the span's
+// count of valid lines).
+__global__ __launch_bounds__(256) void k_emit_qual(ParseBufs b, EmitSpan sp, uint64_t valid, uint64_t r_begin,
+                                                   uint64_t count, uint8_t* quals) {
+    const bool ascii = !sp.any_high;
+    const uint32_t ph = seq_phase(sp.v0);
+    const uint32_t l16 = threadIdx.x & 15;
+    const uint64_t ng = (uint64_t)gridDim.x * 16;
+    for (uint64_t g = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 4; g < count; g += ng) {
+        const uint64_t j = ph + 4 * (r_begin + g) + 2;
+        uint32_t st = 0, len = 0;
+        if (j < valid) {
+            const uint64_t k = ascii ? j : b.vline[j];
+            uint32_t en;
+            line_bounds(b, k, st, en);
+            len = min(en - st, b.stride);
+        }
+        for (uint32_t c0 = 16u * l16; c0 < b.stride; c0 += 256u) {
+            uint32_t w[4] = {0, 0, 0, 0};
+            if (c0 < len) {
+                const uint64_t a = (uint64_t)st + c0;
+                const uint32_t* p = (const uint32_t*)(b.buf + (a & ~3ull));
+                const uint32_t sh = (uint32_t)(a & 3u);
+                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2], d3 = p[3], d4 = p[4];
+                const uint32_t nb = min(16u, len - c0);
+                w[0] = __builtin_amdgcn_alignbyte(d1, d0, sh) & byte_mask(nb);
+                w[1] = __builtin_amdgcn_alignbyte(d2, d1, sh) & byte_mask(nb > 4 ? nb - 4 : 0);
+                w[2] = __builtin_amdgcn_alignbyte(d3, d2, sh) & byte_mask(nb > 8 ? nb - 8 : 0);
+                w[3] = __builtin_amdgcn_alignbyte(d4, d3, sh) & byte_mask(nb > 12 ? nb - 12 : 0);
+            }
+            *(uint4*)(quals + g * b.stride + c0) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t parse_preload() {
@@ -571,6 +622,14 @@ hipError_t launch_emit_reads(const ParseBufs& b, const EmitSpan& sp, uint64_t r_
     const uint64_t blocks = std::min<uint64_t>((count + 15) / 16, 8192);
     hipLaunchKernelGGL(k_emit, dim3((uint32_t)blocks), dim3(256), 0, stream, b, sp, r_begin, count, reads,
                        read_len, pos);
+    return hipGetLastError();
+}
+
+hipError_t launch_emit_quals(const ParseBufs& b, const EmitSpan& sp, uint64_t valid, uint64_t r_begin, uint64_t count,
+                             uint8_t* quals, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    const uint64_t blocks = std::min<uint64_t>((count + 15) / 16, 8192);
+    hipLaunchKernelGGL(k_emit_qual, dim3((uint32_t)blocks), dim3(256), 0, stream, b, sp, valid, r_begin, count, quals);
     return hipGetLastError();
 }
 

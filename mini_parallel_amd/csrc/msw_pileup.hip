@@ -15,7 +15,9 @@
 //
 // pileup_add_kernel is one wave per read like aln_count_kernel: every lane
 // loads the same record words and the same ops (the walk is wave-uniform, there
-// is no ballot or shuffle), and the lanes split the columns of a run.
+// is no ballot or shuffle), and the lanes split the columns of a run.  With a
+// base-quality threshold (msw_pileup_add_qual*) a second instance of the kernel
+// runs, which also reads one quality byte per column.
 #include <algorithm>
 
 #include "msw_kernels.h"
@@ -36,13 +38,32 @@ __device__ __forceinline__ uint32_t comp_byte(uint32_t b) {
     return c ? c | (b & 0x20u) : b;
 }
 
-__global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p) {
-    __shared__ uint32_t tally[4][2];
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// QUAL: the base-quality filter (msw.h, "Base qualities").  The ranges in the
+// difference arrays stay whole; a column under the threshold takes itself out
+// again with one add to mism[pos] -- whether its byte matches the genome or
+// not, the "same" fold d_all - mism then comes out without it, and a
+// mismatching one simply adds to no channel -- and, for a strand-1 read, one
+// wrapped -1 on channel 7, which the fold's += d_rev brings back in range.
+// Q is empty (the plain add: its arguments and code are what they were without
+// the filter) or one PileupQual.
+__device__ __forceinline__ const PileupQual& qual_of(const PileupQual& q) { return q; }
+
+template <typename... Q>
+__global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p, Q... qual) {
+    constexpr bool QUAL = sizeof...(Q) == 1;
+    __shared__ uint32_t tally[4][QUAL ? 3 : 2];
     const int lane = (int)(threadIdx.x & 63u);
     const uint64_t wave = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint64_t waves = (uint64_t)gridDim.x * 4u;
     const int64_t glen = (int64_t)p.glen;
     uint32_t used = 0, skipped = 0;
+    [[maybe_unused]] uint32_t lowq = 0;  // this lane's columns under the threshold
     for (uint64_t r = wave; r < p.n; r += waves) {
         // wave-uniform: every lane loads the same words
         const int64_t ref = p.ref_pos[r];
@@ -59,6 +80,8 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p) {
         const bool flip = rev && p.orient;  // the row holds the read as given: read its reverse complement
         const uint8_t* rd = p.rows + r * p.row_stride;
         const uint32_t* ops = p.cigar + (o0 - p.cigar_base);
+        [[maybe_unused]] const uint8_t* qrow = nullptr;
+        if constexpr (QUAL) qrow = qual_of(qual...).quals + r * qual_of(qual...).qual_stride;
         int64_t i = 0, g = ref;
         // g only grows: past glen nothing counts any more (an I run at g == glen still marks glen - 1)
         for (uint32_t q = 0; q < o1 - o0 && g <= glen; ++q) {
@@ -80,6 +103,18 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p) {
                     }
                     for (int64_t k = lo + lane; k < hi; k += 64) {
                         const uint32_t rb = flip ? comp_byte(rd[rl - 1 - (i + k)]) : (uint32_t)rd[i + k];
+                        if constexpr (QUAL) {
+                            // 0 <= i + k < rl here, so t is in [0, rl) either way; the quality rows are in the
+                            // order of the reads as given, whatever the orientation of `rows`
+                            const int64_t t = rev ? rl - 1 - (i + k) : i + k;
+                            const uint32_t b = t < (int64_t)qual_of(qual...).qual_stride ? (uint32_t)qrow[t] : 0u;
+                            if ((b >= 33u ? b - 33u : 0u) < qual_of(qual...).min_baseq) {
+                                ++lowq;
+                                atomicAdd(p.mism + (g + k), 1u);
+                                if (rev) atomicAdd(p.counts + (uint64_t)(g + k) * p.pos_mul + 7u * p.ch_mul, 0xFFFFFFFFu);
+                                continue;
+                            }
+                        }
                         if (rb != p.genome[g + k]) {
                             atomicAdd(p.counts + (uint64_t)(g + k) * p.pos_mul + base_code(rb) * p.ch_mul, 1u);
                             atomicAdd(p.mism + (g + k), 1u);
@@ -106,9 +141,12 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p) {
     // One add per block and counter, into the block's slot: adds to one
     // address run one after the other (a counter word per wave measured as the
     // whole launch time, ~12 ns each), adds to different lines side by side.
+    [[maybe_unused]] unsigned long long low_wave = 0;
+    if constexpr (QUAL) low_wave = wave_sum(lowq);  // every lane of the wave is here
     if (lane == 0) {
         tally[threadIdx.x >> 6][0] = used;
         tally[threadIdx.x >> 6][1] = skipped;
+        if constexpr (QUAL) tally[threadIdx.x >> 6][2] = (uint32_t)low_wave;
     }
     __syncthreads();
     if (threadIdx.x < 2) {
@@ -117,7 +155,14 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p) {
             atomicAdd(p.reads + ((blockIdx.x % kPileupReadSlots) * 2u + threadIdx.x) * kPileupReadSlotWords,
                       (unsigned long long)v);
     }
+    if constexpr (QUAL) {
+        if (threadIdx.x == 2) {
+            const unsigned long long v = (unsigned long long)tally[0][2] + tally[1][2] + tally[2][2] + tally[3][2];
+            if (v) atomicAdd(qual_of(qual...).lowq + (blockIdx.x % kPileupReadSlots) * kPileupReadSlotWords, v);
+        }
+    }
 }
+
 
 // counts[pos][code(genome[pos])] += d_all[pos + 1] - mism[pos]; counts[pos][7] += d_rev[pos + 1]
 // (the difference arrays scanned: exclusive, so the inclusive value sits one entry on).
@@ -144,12 +189,6 @@ __global__ __launch_bounds__(256) void pileup_finish_kernel(PileupParams p) {
             p.counts[pos * p.pos_mul + 7u * p.ch_mul] += rev;
         }
     }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
 }
 
 // stats: [0] covered, [1] depth_sum, [2] minority_ref, [3] max_depth
@@ -230,14 +269,21 @@ uint64_t pileup_scan_tmp_words(uint64_t glen) {
 
 int pileup_blocks_per_cu() {
     int a = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, pileup_add_kernel, 256, 0) == hipSuccess ? a : 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, pileup_add_kernel<>, 256, 0) == hipSuccess ? a : 0;
 }
 
 hipError_t launch_pileup_add(const PileupParams& p, hipStream_t stream) {
     if (p.n == 0) return hipSuccess;
     // a wave per read, grid-stride past 2^20 blocks
     const uint64_t blocks = std::min<uint64_t>((p.n + 3) / 4, 1u << 20);
-    hipLaunchKernelGGL(pileup_add_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(pileup_add_kernel<>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_pileup_add_qual(const PileupParams& p, const PileupQual& q, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    const uint64_t blocks = std::min<uint64_t>((p.n + 3) / 4, 1u << 20);
+    hipLaunchKernelGGL(pileup_add_kernel<PileupQual>, dim3((unsigned)blocks), dim3(256), 0, stream, p, q);
     return hipGetLastError();
 }
 

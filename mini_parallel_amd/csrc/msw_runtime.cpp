@@ -3125,11 +3125,12 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
 struct msw_pileup {
     const msw_ctx* ctx = nullptr;  // identity only
     int device = 0;
-    // one allocation: counts [glen][8] | the read counters' slots + stats u64[4] | d_all [glen + 1] | d_rev [glen + 1] |
-    // mism [glen] | the scan's block sums
+    // one allocation: counts [glen][8] | the read counters' slots + stats u64[4] + the low-quality column counter's
+    // slots | d_all [glen + 1] | d_rev [glen + 1] | mism [glen] | the scan's block sums
     uint8_t* d_state = nullptr;
     msw::PileupParams p{};         // the state's part; an add fills in its batch
     unsigned long long* d_stats = nullptr;
+    unsigned long long* d_lowq = nullptr;  // PileupQual::lowq
     uint32_t* d_scan_tmp = nullptr;
     bool finished = false;
     hipEvent_t fin = nullptr;      // recorded behind the fold
@@ -3150,7 +3151,8 @@ int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
     const uint64_t glen = g->len;
     auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
     const uint64_t read_words = (uint64_t)msw::kPileupReadSlots * 2 * msw::kPileupReadSlotWords;
-    const uint64_t o_reads = (glen * 32 + 127) & ~(uint64_t)127, o_all = o_reads + (read_words + 16) * 8,
+    const uint64_t lowq_words = (uint64_t)msw::kPileupReadSlots * msw::kPileupReadSlotWords;
+    const uint64_t o_reads = (glen * 32 + 127) & ~(uint64_t)127, o_all = o_reads + (read_words + 16 + lowq_words) * 8,
                    o_rev = o_all + up16((glen + 1) * 4),
                    o_mism = o_rev + up16((glen + 1) * 4), o_tmp = o_mism + up16(glen * 4),
                    total = o_tmp + up16(msw::pileup_scan_tmp_words(glen) * 4) + 16;
@@ -3173,6 +3175,7 @@ int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
     p.ch_mul = planes ? glen : 1;
     p.reads = reinterpret_cast<unsigned long long*>(pile->d_state + o_reads);
     pile->d_stats = p.reads + read_words;
+    pile->d_lowq = pile->d_stats + 16;
     p.d_all = reinterpret_cast<uint32_t*>(pile->d_state + o_all);
     p.d_rev = reinterpret_cast<uint32_t*>(pile->d_state + o_rev);
     p.mism = reinterpret_cast<uint32_t*>(pile->d_state + o_mism);
@@ -3220,6 +3223,15 @@ static int check_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows,
 int msw_pileup_add_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
                           uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
                           const uint8_t* mapq, uint32_t min_mapq, void* stream) {
+    return msw_pileup_add_qual_device(ctx, pile, rows, read_len, row_stride, n, aln, strand, mapq, min_mapq, nullptr, 0,
+                                      0, stream);
+}
+
+int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
+                               uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                               const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
+                               uint32_t min_baseq, void* stream) {
+    if (min_baseq > 93u) return fail(MSW_E_RANGE, "pileup add: min_baseq %u > 93", min_baseq);
     int rc;
     bool go;
     if ((rc = check_pileup_add(ctx, pile, rows, read_len, row_stride, n, aln, min_mapq, &go)) || !go) return rc;
@@ -3237,13 +3249,29 @@ int msw_pileup_add_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, c
     p.strand = strand;
     p.mapq = mapq;
     p.min_mapq = min_mapq;
-    HIP_TRY(msw::launch_pileup_add(p, call_stream(ctx, stream)));
+    if (quals && min_baseq) {  // else the plain add
+        const msw::PileupQual q{quals, qual_stride, min_baseq, pile->d_lowq};
+        HIP_TRY(msw::launch_pileup_add_qual(p, q, call_stream(ctx, stream)));
+    } else {
+        HIP_TRY(msw::launch_pileup_add(p, call_stream(ctx, stream)));
+    }
     return MSW_OK;
 }
 
 int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
                    uint64_t n, const msw_aln_t* aln, const uint8_t* strand, const uint8_t* mapq, uint32_t min_mapq,
                    uint64_t chunk_reads) {
+    return msw_pileup_add_qual(ctx, pile, reads, read_len, read_stride, n, aln, strand, mapq, min_mapq, nullptr, 0, 0,
+                               chunk_reads);
+}
+
+int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len,
+                        uint32_t read_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
+                        const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
+                        uint32_t min_baseq, uint64_t chunk_reads) {
+    if (min_baseq > 93u) return fail(MSW_E_RANGE, "pileup add: min_baseq %u > 93", min_baseq);
+    if (min_baseq == 0) quals = nullptr;  // the plain add
+    if (!quals) qual_stride = 0;
     int rc;
     bool go;
     if ((rc = check_pileup_add(ctx, pile, reads, read_len, read_stride, n, aln, min_mapq, &go)) || !go) return rc;
@@ -3264,11 +3292,12 @@ int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const u
         if (read_len[k] > read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
     if ((rc = set_device(ctx))) return rc;
     auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    // [ref i64 | nm i32 | off u32 [c + 1] | ops | rlen u16 | strand | mapq | rows]
-    const size_t rs = read_stride;
+    // [ref i64 | nm i32 | off u32 [c + 1] | ops | rlen u16 | strand | mapq | rows | quals]
+    const size_t rs = read_stride, qs = qual_stride;
     const size_t o_nm = chunk * 8, o_off = o_nm + chunk * 4, o_ops = up16(o_off + (chunk + 1) * 4),
                  o_rl = up16(o_ops + max_ops * 4), o_st = up16(o_rl + chunk * 2), o_mq = up16(o_st + chunk),
-                 o_rows = up16(o_mq + chunk), total = o_rows + chunk * rs + 16;
+                 o_rows = up16(o_mq + chunk), o_q = up16(o_rows + chunk * rs),
+                 total = o_q + chunk * qs + 16;
     uint8_t* d = nullptr;
     hipError_t e = hipMalloc((void**)&d, total);
     if (e != hipSuccess) {
@@ -3289,6 +3318,7 @@ int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const u
     p.mapq = mapq ? d + o_mq : nullptr;
     p.min_mapq = min_mapq;
     p.orient = strand ? 1u : 0u;
+    const msw::PileupQual q{d + o_q, qual_stride, min_baseq, pile->d_lowq};
     for (uint64_t lo = 0; lo < n && e == hipSuccess; lo += chunk) {
         const uint64_t c = std::min(chunk, n - lo);
         auto up = [&](size_t at, const void* src, size_t bytes) {
@@ -3303,9 +3333,10 @@ int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const u
         if (strand) up(o_st, strand + lo, c);
         if (mapq) up(o_mq, mapq + lo, c);
         up(o_rows, reads + lo * rs, c * rs);
+        if (quals) up(o_q, quals + lo * qs, c * qs);
         p.n = c;
         p.cigar_base = o0;
-        if (e == hipSuccess) e = msw::launch_pileup_add(p, st);
+        if (e == hipSuccess) e = quals ? msw::launch_pileup_add_qual(p, q, st) : msw::launch_pileup_add(p, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);  // the buffers are the next chunk's
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(st);
@@ -3396,6 +3427,21 @@ int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_p
     out->depth_sum = h[kWords + 1];
     out->minority_ref = h[kWords + 2];
     out->max_depth = (uint32_t)h[kWords + 3];
+    return MSW_OK;
+}
+
+int msw_pileup_lowq_columns(msw_ctx* ctx, msw_pileup* pile, uint64_t* out) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!out) return fail(MSW_E_INVALID, "out is NULL");
+    if ((rc = set_device(ctx))) return rc;
+    // adds may have been enqueued on any stream: wait for all of them
+    HIP_TRY(hipDeviceSynchronize());
+    constexpr uint32_t kWords = msw::kPileupReadSlots * msw::kPileupReadSlotWords;
+    std::vector<unsigned long long> h(kWords);
+    HIP_TRY(hipMemcpy(h.data(), pile->d_lowq, h.size() * 8, hipMemcpyDeviceToHost));
+    *out = 0;
+    for (uint32_t s = 0; s < msw::kPileupReadSlots; ++s) *out += h[s * msw::kPileupReadSlotWords];
     return MSW_OK;
 }
 

@@ -102,11 +102,15 @@ class GpuFastqReader:
     span's inflate."""
 
     def __init__(self, ctx, path: str, stride: int = 256, max_reads: int = 1 << 20, with_pos: bool = False,
-                 span_bytes: int = 0):
-        self.ctx, self.path, self.stride, self.with_pos = ctx, path, stride, with_pos
+                 span_bytes: int = 0, with_qual: bool = False):
+        self.ctx, self.path, self.stride, self.with_pos, self.with_qual = ctx, path, stride, with_pos, with_qual
         h = ctypes.c_void_p()
-        check(lib().msw_gfastq_open(ctx.handle, path.encode(), stride, max_reads, 1 if with_pos else 0,
-                                    span_bytes, ctypes.byref(h)))
+        if with_qual:  # MSW_GFASTQ_POS 1, MSW_GFASTQ_QUAL 2
+            check(lib().msw_gfastq_open_ex(ctx.handle, path.encode(), stride, max_reads, (1 if with_pos else 0) | 2,
+                                           span_bytes, ctypes.byref(h)))
+        else:
+            check(lib().msw_gfastq_open(ctx.handle, path.encode(), stride, max_reads, 1 if with_pos else 0,
+                                        span_bytes, ctypes.byref(h)))
         self._h = h
 
     def close(self) -> None:
@@ -135,8 +139,18 @@ class GpuFastqReader:
         """msw_gfastq_prefetch: open the file the next reset() names ahead of time."""
         check(lib().msw_gfastq_prefetch(self._h, path.encode()))
 
+    def quals_ptr(self) -> int:
+        """msw_gfastq_quals: the device pointer of the last batch's quality
+        rows (uint8[n, stride], the quality-row rule of msw_fastq.h), valid as
+        long as that batch's reads; 0 for a reader without ``with_qual``."""
+        q = ctypes.c_void_p()
+        check(lib().msw_gfastq_quals(self._h, ctypes.byref(q)))
+        return int(q.value or 0)
+
     def next_batch(self, host: bool = True):
-        """-> DevReadsT, or with host=True (seqs u8[n, stride], lens u16[n][, pos i64[n]])."""
+        """-> DevReadsT, or with host=True (seqs u8[n, stride], lens u16[n][, pos i64[n]]).
+        A reader made with ``with_qual=True`` returns four items: seqs, lens,
+        pos (None without ``with_pos``) and the quality rows u8[n, stride]."""
         d = DevReadsT()
         check(lib().msw_gfastq_next(self._h, None, ctypes.byref(d)))
         self.last = d  # the batch's descriptor (n, first_read, min_len / max_len bounds)
@@ -150,10 +164,17 @@ class GpuFastqReader:
         if n:
             check(L.msw_memcpy_d2h(self.ctx.handle, seqs.ctypes.data, d.reads, seqs.nbytes))
             check(L.msw_memcpy_d2h(self.ctx.handle, lens.ctypes.data, d.read_len, lens.nbytes))
+        pos = None
         if self.with_pos:
             pos = np.zeros(n, np.int64)
             if n:
                 check(L.msw_memcpy_d2h(self.ctx.handle, pos.ctypes.data, d.pos, pos.nbytes))
+        if self.with_qual:
+            quals = np.zeros((n, self.stride), np.uint8)
+            if n:
+                check(L.msw_memcpy_d2h(self.ctx.handle, quals.ctypes.data, self.quals_ptr(), quals.nbytes))
+            return seqs, lens, pos, quals
+        if self.with_pos:
             return seqs, lens, pos
         return seqs, lens
 

@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--cli", default="", help="CLI binary (A/B against another build)")
     ap.add_argument("--window", type=int, default=300)
     ap.add_argument("--reuse", action="store_true", help="keep an existing dataset in --dir")
+    ap.add_argument("--cli-args", default="",
+                    help="further CLI arguments, space separated (e.g. '--alignments-out DIR --pileup-out P "
+                         "--pileup-min-baseq 20'); '{dir}' stands for --dir")
     args = ap.parse_args()
 
     from mini_parallel_amd.synthetic import write_wgs_dataset
@@ -80,7 +83,7 @@ def main():
         ts = time.time()
         r = subprocess.run([cli, "--full-wgs", "--gpu", "--score-mode", "sw", "--reference", ds["reference"],
                             "--window", str(args.window), "--checkpoint-dir", args.dir, "--json", rec,
-                            "--num-gpus", str(args.num_gpus)],
+                            "--num-gpus", str(args.num_gpus)] + args.cli_args.format(dir=args.dir).split(),
                            env=env, capture_output=True, text=True, timeout=900)
         wall = time.time() - ts
         if r.stderr:
