@@ -661,8 +661,10 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
  *
  * State: about 44 bytes of device memory per genome base (the 32-byte row, two
  * 4-byte difference arrays and a 4-byte mismatch count), so
- * 176 MB for a 4 Mbase genome.  A pileup belongs to the context of its genome
- * and is destroyed before it. */
+ * 176 MB for a 4 Mbase genome; a MSW_PILEUP_QSUM pileup ("Quality sums and
+ * weighted genotypes" below) holds 24 bytes per base more, about 68 in all and
+ * 272 MB for 4 Mbase.  A pileup belongs to the context of its genome and is
+ * destroyed before it. */
 typedef struct msw_pileup msw_pileup;
 typedef struct {
     uint64_t covered;
@@ -704,7 +706,9 @@ int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const u
 /* Both adds with the base-quality threshold of "Base qualities" above.  quals
  * is device memory in the device form (e.g. msw_gfastq_quals, msw_fastq.h) and
  * host memory in the host form; a quality path of its own runs only when
- * quals != NULL and min_baseq > 0, otherwise these are the calls above. */
+ * quals != NULL and min_baseq > 0, otherwise these are the calls above (a
+ * MSW_PILEUP_QSUM pileup has rules of its own: "Quality sums and weighted
+ * genotypes" below). */
 int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
                                uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
                                const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
@@ -836,6 +840,95 @@ int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* par
 int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
                     const msw_call_params_t* params, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
                     uint64_t* n_total);
+
+/* Quality sums and weighted genotypes: per base and allele the summed Phred
+ * values of the observations, and a caller that charges an observation by its
+ * own error rate instead of one fixed rate.
+ *
+ * Integers throughout; tests/pileup_qsum_oracle.py and
+ * tests/variant_qual_oracle.py restate this section.
+ *
+ * Quality sums.  A pileup created with msw_pileup_create_ex(ctx, genome,
+ * MSW_PILEUP_QSUM, &out) carries qsum[glen][4], uint32, beside its counts.
+ * qsum[pos][c] is the sum of phred(quals[p][t]) over the M columns that count
+ * at pos and whose read byte has code c < 4.  "Count" is the walk, the range
+ * rules and the min_baseq rule of "Base qualities" above, unchanged, with the
+ * same quality index t and the same t < qual_stride rule: a column adds to
+ * qsum exactly when it adds to channel c < 4 of the counts.  A dropped column,
+ * or one whose read byte has code 4, adds nothing; D and I runs add nothing.
+ * Sums are modulo 2^32, like the counts.  The result is a function of the set
+ * of records, qualities and threshold alone.
+ *
+ * Calls on a MSW_PILEUP_QSUM pileup.  msw_pileup_add_qual[_device] needs
+ * quals != NULL (else MSW_E_INVALID, for any n) and accepts min_baseq == 0:
+ * the quality path runs, because the sums need it, and then a column counts
+ * when t < qual_stride.  msw_pileup_add[_device] returns MSW_E_INVALID.
+ * msw_pileup_create_ex with flags 0 is msw_pileup_create; an unknown flag is
+ * MSW_E_INVALID.  On a pileup without the flag every call of "Pileup" behaves
+ * exactly as described there.
+ *
+ * Weighted genotypes.  Site kinds, candidate rule, choice of the alternative
+ * (the highest count), emission, pl, qual, gq, record layout and order are
+ * those of "Variants".  Only raw[] of a COLUMN site changes.  With
+ * r = code(genome[pos]), alt_ch the alternative's channel, all values u64:
+ *   Wref = q_scale * qsum[pos][r] + q_third * ref
+ *   Walt = alt_ch < 4 ? q_scale * qsum[pos][alt_ch] + q_third * a
+ *                     : a * q_miss          (a DEL has no base quality)
+ *   raw[0] = ref * q_hit + Walt
+ *   raw[1] = (ref + a) * q_het
+ *   raw[2] = Wref + a * q_hit
+ * Insertion sites keep the formula of "Variants".  The cost of an observation
+ * with Phred value Q under the other homozygote is
+ * -1000 * log10(10^(-Q/10) / 3) = 100 * Q + 477; at Q20 that is the 2477 of
+ * q_miss, so with every counted base at Phred 20 and the default weights the
+ * records are those of "Variants".  q_hit and q_het stay fixed: they depend
+ * on e too, but for Q20 and better -1000 * log10(1 - e) lies between 0 and 4
+ * and -1000 * log10((1 - e) / 2 + e / 6) between 301 and 304, so the fixed
+ * values are off by a few units per read (what decides a genotype,
+ * q_het - q_hit, by under 3), against the hundreds to thousands per read of
+ * the weighted term.
+ *
+ * State: the flag adds 24 bytes of device memory per genome base (16 for
+ * qsum, a 4-byte difference array and a 4-byte sum over mismatching columns),
+ * allocated only with the flag: about 68 bytes per base, 272 MB for a 4 Mbase
+ * genome. */
+#define MSW_PILEUP_QSUM 1u
+typedef struct {
+    uint32_t q_scale; /* 100 */
+    uint32_t q_third; /* 477 */
+} msw_call_qparams_t;
+/* Fills *qparams with the defaults noted beside the fields. */
+void msw_call_qparams_default(msw_call_qparams_t* qparams);
+
+/* msw_pileup_create with flags: 0 or MSW_PILEUP_QSUM. */
+int msw_pileup_create_ex(msw_ctx* ctx, const msw_genome* genome, uint32_t flags, msw_pileup** out);
+/* The finished quality sums into host_out[glen][4]; synchronous (it waits for
+ * the finish).  Before msw_pileup_finish, or on a pileup without
+ * MSW_PILEUP_QSUM: MSW_E_INVALID. */
+int msw_pileup_qsums(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out);
+/* The sums on the device: channel c of position pos is
+ * (*qsums)[pos * *pos_stride + c * *ch_stride] (rows of four: 4 and 1, in
+ * either layout of the counts).  Valid at any time; the values are final once
+ * the finish has run.  Without MSW_PILEUP_QSUM: MSW_E_INVALID. */
+int msw_pileup_qsums_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** qsums, uint64_t* pos_stride,
+                            uint64_t* ch_stride);
+
+/* The three calls of "Variants" with weighted genotypes; their error rules,
+ * cap, totals and chunking are the same.  qparams == NULL selects the
+ * defaults; a q_scale or q_third above 65535 is MSW_E_INVALID.  The pileup
+ * forms take a finished MSW_PILEUP_QSUM pileup (without the flag:
+ * MSW_E_INVALID); msw_call_counts_qual takes qsums_host[glen][4] beside
+ * counts_host and streams it in the same chunks (the sums need no look-ahead
+ * row). */
+int msw_pileup_call_qual_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params,
+                                const msw_call_qparams_t* qparams, msw_variant_t* out_dev, uint64_t cap,
+                                uint64_t* n_total_dev, void* stream);
+int msw_pileup_call_qual(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params,
+                         const msw_call_qparams_t* qparams, msw_variant_t* out_host, uint64_t cap, uint64_t* n_total);
+int msw_call_counts_qual(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
+                         const uint32_t* qsums_host, const msw_call_params_t* params,
+                         const msw_call_qparams_t* qparams, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
+                         uint64_t* n_total);
 
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);

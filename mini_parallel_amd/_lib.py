@@ -39,6 +39,8 @@ EXPORTED = (
     "msw_pileup_counts", "msw_pileup_counts_device", "msw_pileup_summary",
     "msw_pileup_add_qual_device", "msw_pileup_add_qual", "msw_pileup_lowq_columns",
     "msw_call_params_default", "msw_pileup_call_device", "msw_pileup_call", "msw_call_counts",
+    "msw_call_qparams_default", "msw_pileup_create_ex", "msw_pileup_qsums", "msw_pileup_qsums_device",
+    "msw_pileup_call_qual_device", "msw_pileup_call_qual", "msw_call_counts_qual",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -128,6 +130,13 @@ class PileupSummaryT(ctypes.Structure):
 class CallParamsT(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("min_depth", "min_alt", "min_alt_permille", "min_qual", "q_hit",
                                                "q_miss", "q_het", "prior_het", "prior_hom")]
+
+
+class CallQParamsT(ctypes.Structure):
+    _fields_ = [("q_scale", ctypes.c_uint32), ("q_third", ctypes.c_uint32)]
+
+
+MSW_PILEUP_QSUM = 1
 
 
 class DevReadsT(ctypes.Structure):
@@ -221,6 +230,18 @@ def _declare(L):
         "msw_pileup_call_device": (I, [P, P, ctypes.POINTER(CallParamsT), P, ctypes.c_uint64, P, P]),
         "msw_pileup_call": (I, [P, P, ctypes.POINTER(CallParamsT), P, ctypes.c_uint64,
                                 ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_call_qparams_default": (None, [ctypes.POINTER(CallQParamsT)]),
+        "msw_pileup_create_ex": (I, [P, P, ctypes.c_uint32, ctypes.POINTER(P)]),
+        "msw_pileup_qsums": (I, [P, P, P]),
+        "msw_pileup_qsums_device": (I, [P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64),
+                                        ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_pileup_call_qual_device": (I, [P, P, ctypes.POINTER(CallParamsT), ctypes.POINTER(CallQParamsT), P,
+                                            ctypes.c_uint64, P, P]),
+        "msw_pileup_call_qual": (I, [P, P, ctypes.POINTER(CallParamsT), ctypes.POINTER(CallQParamsT), P,
+                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_call_counts_qual": (I, [P, P, ctypes.c_uint64, P, P, ctypes.POINTER(CallParamsT),
+                                     ctypes.POINTER(CallQParamsT), ctypes.c_uint64, P, ctypes.c_uint64,
+                                     ctypes.POINTER(ctypes.c_uint64)]),
         "msw_call_counts": (I, [P, P, ctypes.c_uint64, P, ctypes.POINTER(CallParamsT), ctypes.c_uint64, P,
                                 ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),

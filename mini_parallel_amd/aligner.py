@@ -26,7 +26,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, AlnT, BatchT, CallParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PileupSummaryT,
+from ._lib import (MSW_E_INVALID, MSW_PILEUP_QSUM, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PileupSummaryT,
                    ReadBatchT, ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
@@ -184,6 +184,23 @@ class CallParams:
             if not 0 <= int(getattr(self, k)) <= 0xFFFFFFFF:
                 raise MswError(MSW_E_INVALID, f"call params: {k} does not fit 32 bits")
         return CallParamsT(*(int(getattr(self, k)) for k in self.FIELDS))
+
+
+@dataclass(frozen=True)
+class QualParams:
+    """The weights of the quality-weighted caller (msw_call_qparams_t): an
+    observation of Phred value Q costs ``q_scale * Q + q_third`` under the
+    other homozygote."""
+    q_scale: int = 100
+    q_third: int = 477
+
+    FIELDS = ("q_scale", "q_third")
+
+    def to_c(self) -> CallQParamsT:
+        for k in self.FIELDS:
+            if not 0 <= int(getattr(self, k)) <= 0xFFFFFFFF:
+                raise MswError(MSW_E_INVALID, f"call qparams: {k} does not fit 32 bits")
+        return CallQParamsT(int(self.q_scale), int(self.q_third))
 
 
 class Variants(NamedTuple):
@@ -587,18 +604,23 @@ class Context:
         return self.align_reads_trace(genome, reads, read_len, win_pos, win_len, scoring, chunk_pairs=chunk_pairs)
 
     # -- pileup (include/msw.h, "Pileup") -----------------------------------------------
-    def pileup(self, genome: "Genome") -> "Pileup":
+    def pileup(self, genome: "Genome", qsum: bool = False) -> "Pileup":
         """An empty pileup over a resident genome (msw_pileup_create): per
         base the allele, deletion, insertion and reverse-strand counts of the
-        alignment records added to it."""
-        return Pileup(self, genome)
+        alignment records added to it.  With ``qsum`` it also carries the
+        per-base quality sums (MSW_PILEUP_QSUM): every add then needs
+        ``quals``, and :meth:`Pileup.call` can weigh the genotypes by them."""
+        return Pileup(self, genome, qsum)
 
     # -- variants (include/msw.h, "Variants") -------------------------------------------
-    def call_variants(self, genome, counts, params: Optional[CallParams] = None, chunk_pos: int = 0) -> Variants:
+    def call_variants(self, genome, counts, params: Optional[CallParams] = None, chunk_pos: int = 0, qsums=None,
+                      qual_params: Optional[QualParams] = None) -> Variants:
         """Variant calls from any host ``counts[glen][8]`` over the genome bytes
         (msw_call_counts), for example the sum of several pileups.  The rows go
         to the GPU in chunks of ``chunk_pos`` positions (0: about 1 M); the
-        records do not depend on it."""
+        records do not depend on it.  With ``qsums[glen][4]`` the genotypes are
+        quality-weighted (msw_call_counts_qual; ``qual_params`` None: the
+        default weights); ``qual_params`` without ``qsums`` is an error."""
         g = np.frombuffer(bytes(genome), np.uint8) if isinstance(genome, (bytes, bytearray)) else \
             np.ascontiguousarray(genome, dtype=np.uint8)
         c = np.ascontiguousarray(counts, dtype=np.uint32)
@@ -606,12 +628,25 @@ class Context:
             raise MswError(MSW_E_INVALID, "counts must be [len(genome)][8]")
         q = (params or CallParams()).to_c()
         total = ctypes.c_uint64()
+        if qsums is None and qual_params is not None:
+            raise MswError(MSW_E_INVALID, "qual_params without qsums")
+        if qsums is not None:
+            w = np.ascontiguousarray(qsums, dtype=np.uint32)
+            if w.ndim != 2 or w.shape[1] != 4 or w.shape[0] != g.shape[0]:
+                raise MswError(MSW_E_INVALID, "qsums must be [len(genome)][4]")
+            qq = (qual_params or QualParams()).to_c()
 
         def run(out, cap):
-            check(lib().msw_call_counts(self.handle, g.ctypes.data if g.size else None, g.shape[0],
-                                        c.ctypes.data if c.size else None, ctypes.byref(q), chunk_pos,
-                                        _fresh_ptr(out) or None if out is not None else None, cap,
-                                        ctypes.byref(total)))
+            out_ptr = _fresh_ptr(out) or None if out is not None else None
+            if qsums is not None:
+                check(lib().msw_call_counts_qual(self.handle, g.ctypes.data if g.size else None, g.shape[0],
+                                                 c.ctypes.data if c.size else None, w.ctypes.data if w.size else None,
+                                                 ctypes.byref(q), ctypes.byref(qq), chunk_pos, out_ptr, cap,
+                                                 ctypes.byref(total)))
+            else:
+                check(lib().msw_call_counts(self.handle, g.ctypes.data if g.size else None, g.shape[0],
+                                            c.ctypes.data if c.size else None, ctypes.byref(q), chunk_pos, out_ptr,
+                                            cap, ctypes.byref(total)))
             return int(total.value)
 
         n = run(None, 0)
@@ -990,10 +1025,14 @@ class Pileup:
 
     CHANNELS = 8
 
-    def __init__(self, ctx: Context, genome: Genome):
+    def __init__(self, ctx: Context, genome: Genome, qsum: bool = False):
         h = ctypes.c_void_p()
-        check(lib().msw_pileup_create(ctx.handle, genome.handle, ctypes.byref(h)))
+        if qsum:
+            check(lib().msw_pileup_create_ex(ctx.handle, genome.handle, MSW_PILEUP_QSUM, ctypes.byref(h)))
+        else:
+            check(lib().msw_pileup_create(ctx.handle, genome.handle, ctypes.byref(h)))
         self._h = h
+        self.qsum = bool(qsum)
         self.ctx = ctx        # keeps the context and the genome alive for as long as the pileup
         self.genome = genome
         self._glen = len(genome)
@@ -1017,7 +1056,8 @@ class Pileup:
         ``min_mapq`` are skipped.  With ``quals`` (uint8[n, qual_stride], one
         FASTQ quality byte per base of the reads as given) and
         ``min_baseq`` > 0, M columns whose Phred value is below ``min_baseq``
-        are dropped (msw_pileup_add_qual; :meth:`lowq_columns` counts them)."""
+        are dropped (msw_pileup_add_qual; :meth:`lowq_columns` counts them).
+        A ``qsum`` pileup needs ``quals`` and takes any ``min_baseq``, 0 too."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
         ref_pos = np.ascontiguousarray(ref_pos, dtype=np.int64)
@@ -1105,6 +1145,22 @@ class Pileup:
                                              ctypes.byref(cs)))
         return int(ptr.value or 0), int(ps.value), int(cs.value)
 
+    def qsums(self) -> np.ndarray:
+        """uint32[glen][4] on the host (msw_pileup_qsums): per base and allele
+        A, C, G, T the summed Phred values of the counted columns; after
+        finish(), on a ``qsum`` pileup."""
+        out = np.empty((self._glen, 4), np.uint32)
+        check(lib().msw_pileup_qsums(self.ctx.handle, self.handle, _fresh_ptr(out) or None))
+        return out
+
+    def qsums_device(self):
+        """(device pointer, position stride, channel stride) in uint32 words
+        (msw_pileup_qsums_device)."""
+        ptr, ps, cs = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().msw_pileup_qsums_device(self.ctx.handle, self.handle, ctypes.byref(ptr), ctypes.byref(ps),
+                                            ctypes.byref(cs)))
+        return int(ptr.value or 0), int(ps.value), int(cs.value)
+
     def summary(self, min_depth: int = 1) -> dict:
         """covered, depth_sum, max_depth, minority_ref, reads_used and
         reads_skipped of the finished counts (msw_pileup_summary)."""
@@ -1114,27 +1170,50 @@ class Pileup:
                                                 "reads_skipped")}
 
     def call_device(self, out_ptr: int, cap: int, n_total_ptr: int, params: Optional[CallParams] = None,
-                    stream: int = 0) -> None:
+                    stream: int = 0, qual_params: Optional[QualParams] = None) -> None:
         """Enqueue the call on ``stream`` (msw_pileup_call_device): up to
         ``cap`` 48-byte records to the device pointer ``out_ptr`` and the total
         as a u64 to ``n_total_ptr``; ``out_ptr`` 0 with ``cap`` 0 runs the count
-        pass alone.  No host synchronisation."""
+        pass alone.  No host synchronisation.  With ``qual_params`` the
+        genotypes are quality-weighted (msw_pileup_call_qual_device), as in
+        :meth:`call`."""
         q = (params or CallParams()).to_c()
+        if qual_params is not None:
+            qq = qual_params.to_c()
+            check(lib().msw_pileup_call_qual_device(self.ctx.handle, self.handle, ctypes.byref(q), ctypes.byref(qq),
+                                                    ctypes.c_void_p(out_ptr or None), cap,
+                                                    ctypes.c_void_p(n_total_ptr or None),
+                                                    ctypes.c_void_p(stream or None)))
+            return
         check(lib().msw_pileup_call_device(self.ctx.handle, self.handle, ctypes.byref(q),
                                            ctypes.c_void_p(out_ptr or None), cap, ctypes.c_void_p(n_total_ptr or None),
                                            ctypes.c_void_p(stream or None)))
 
-    def call(self, params: Optional[CallParams] = None) -> Variants:
+    def call(self, params: Optional[CallParams] = None, qual_params: Optional[QualParams] = None) -> Variants:
         """Variant calls from the finished counts (msw_pileup_call): one count
-        call, then one call that fills the records."""
+        call, then one call that fills the records.  The genotypes are
+        quality-weighted (msw_pileup_call_qual) exactly when ``qual_params`` is
+        given -- ``QualParams()`` for the default weights; without it the call
+        is the unweighted one on a ``qsum`` pileup too, so the flag alone never
+        changes a result.  ``qual_params`` on a pileup without quality sums is
+        MSW_E_INVALID."""
         q = (params or CallParams()).to_c()
         total = ctypes.c_uint64()
-        check(lib().msw_pileup_call(self.ctx.handle, self.handle, ctypes.byref(q), None, 0, ctypes.byref(total)))
+        if qual_params is not None:
+            qq = qual_params.to_c()
+
+            def run(out, cap):
+                check(lib().msw_pileup_call_qual(self.ctx.handle, self.handle, ctypes.byref(q), ctypes.byref(qq), out,
+                                                 cap, ctypes.byref(total)))
+        else:
+            def run(out, cap):
+                check(lib().msw_pileup_call(self.ctx.handle, self.handle, ctypes.byref(q), out, cap,
+                                            ctypes.byref(total)))
+        run(None, 0)
         n = int(total.value)
         rec = np.zeros(n, VARIANT_DTYPE)
         if n:
-            check(lib().msw_pileup_call(self.ctx.handle, self.handle, ctypes.byref(q), _fresh_ptr(rec), n,
-                                        ctypes.byref(total)))
+            run(_fresh_ptr(rec), n)
         return Variants.from_records(rec)
 
     def close(self) -> None:

@@ -29,7 +29,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .aligner import VAR_DEL, VAR_INS, VAR_SNV, VARIANT_DTYPE, CallParams, CigarList, Variants
+from .aligner import VAR_DEL, VAR_INS, VAR_SNV, VARIANT_DTYPE, CallParams, CigarList, QualParams, Variants
 
 MAGIC = b"MSWA"
 VERSION = 1
@@ -239,6 +239,53 @@ def read_pileup(path):
     return counts.reshape(glen, PILEUP_CHANNELS).astype(np.uint32), int(head["reads_used"])
 
 
+# The ``.mqs`` file of ``rustseq_mini --full-wgs --call-baseq --qsum-out``
+# (DESIGN.md 4.17), little-endian: a 32-byte header -- "MSWQSUM1", u32 version =
+# 1, u32 channels = 4, u64 genome length, u64 reads_used -- then genome length x
+# 4 u32 quality sums (include/msw.h, "Quality sums and weighted genotypes").
+QSUM_MAGIC = b"MSWQSUM1"
+QSUM_VERSION = 1
+QSUM_CHANNELS = 4
+
+
+def write_qsums(path, qsums, reads_used: int) -> None:
+    """Write uint32 ``qsums[glen][4]`` and the number of reads behind them."""
+    qsums = np.asarray(qsums)
+    if qsums.ndim != 2 or qsums.shape[1] != QSUM_CHANNELS:
+        raise ValueError(f"qsums must be [glen][{QSUM_CHANNELS}]")
+    if qsums.size and (qsums.min() < 0 or qsums.max() > 0xFFFFFFFF):
+        raise ValueError("a sum does not fit 32 bits")
+    head = np.zeros(1, PILEUP_HEADER)
+    head["magic"], head["version"], head["channels"] = QSUM_MAGIC, QSUM_VERSION, QSUM_CHANNELS
+    head["glen"], head["reads_used"] = qsums.shape[0], int(reads_used)
+    with open(path, "wb") as f:
+        f.write(head.tobytes())
+        f.write(np.ascontiguousarray(qsums, dtype="<u4").tobytes())
+
+
+def read_qsums(path):
+    """-> (qsums uint32[glen][4], reads_used).  Raises ValueError on a bad
+    magic, version or channel count, and on a size that does not match the
+    header's genome length (truncated, or bytes after the sums)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < PILEUP_HEADER.itemsize:
+        raise ValueError(f"{path}: truncated header")
+    head = np.frombuffer(data, PILEUP_HEADER, 1)[0]
+    if bytes(head["magic"]) != QSUM_MAGIC:
+        raise ValueError(f"{path}: bad magic")
+    if int(head["version"]) != QSUM_VERSION:
+        raise ValueError(f"{path}: version {int(head['version'])}, expected {QSUM_VERSION}")
+    if int(head["channels"]) != QSUM_CHANNELS:
+        raise ValueError(f"{path}: {int(head['channels'])} channels, expected {QSUM_CHANNELS}")
+    glen = int(head["glen"])
+    want = PILEUP_HEADER.itemsize + glen * QSUM_CHANNELS * 4
+    if len(data) != want:
+        raise ValueError(f"{path}: {len(data)} bytes, the header's genome length {glen} asks for {want}")
+    qsums = np.frombuffer(data, "<u4", glen * QSUM_CHANNELS, PILEUP_HEADER.itemsize)
+    return qsums.reshape(glen, QSUM_CHANNELS).astype(np.uint32), int(head["reads_used"])
+
+
 # The ``.var`` file of ``rustseq_mini --full-wgs --variants-out`` (DESIGN.md 4.15),
 # little-endian: a 72-byte header -- "MSWVARS1", u32 version = 1, u32 record size
 # = 48, u64 genome length, u64 record count, the nine u32 of msw_call_params_t in
@@ -249,6 +296,12 @@ VARIANTS_VERSION = 1
 VARIANTS_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("record_size", "<u4"), ("glen", "<u8"),
                             ("count", "<u8"), ("params", "<u4", (9,)), ("reserved", "<u4")])
 assert VARIANTS_HEADER.itemsize == 72
+# The quality-weighted ``.var`` (``--call-baseq``): magic
+# "MSWVARQ1" and an 88-byte header -- the 72 bytes above, then q_scale, q_third
+# (msw_call_qparams_t) and two zero words; the records are the same.
+VARIANTS_QUAL_MAGIC = b"MSWVARQ1"
+VARIANTS_QUAL_HEADER = np.dtype(VARIANTS_HEADER.descr + [("qparams", "<u4", (2,)), ("reserved2", "<u4", (2,))])
+assert VARIANTS_QUAL_HEADER.itemsize == 88
 
 
 def _check_variant_records(path, rec, glen) -> None:
@@ -269,16 +322,22 @@ def _check_variant_records(path, rec, glen) -> None:
         raise ValueError(f"{path}: the records are not ordered by pos, then kind")
 
 
-def write_variants(path, variants: Variants, glen: int, params: Optional[CallParams] = None) -> None:
+def write_variants(path, variants: Variants, glen: int, params: Optional[CallParams] = None,
+                   qual_params: Optional[QualParams] = None) -> None:
     """Write the records of a genome of ``glen`` bases and the parameters they
-    were called with (the defaults when None)."""
+    were called with (the defaults when None).  With ``qual_params`` (records
+    of a quality-weighted call) the file is an ``MSWVARQ1`` one, which
+    :func:`read_variants_qual` reads."""
     params = params or CallParams()
     rec = variants.to_records()
     _check_variant_records(str(path), rec, int(glen))
-    head = np.zeros(1, VARIANTS_HEADER)
+    head = np.zeros(1, VARIANTS_HEADER if qual_params is None else VARIANTS_QUAL_HEADER)
     head["magic"], head["version"], head["record_size"] = VARIANTS_MAGIC, VARIANTS_VERSION, VARIANT_DTYPE.itemsize
     head["glen"], head["count"] = int(glen), len(rec)
     head["params"] = [int(getattr(params, k)) for k in CallParams.FIELDS]
+    if qual_params is not None:
+        head["magic"] = VARIANTS_QUAL_MAGIC
+        head["qparams"] = [int(getattr(qual_params, k)) for k in QualParams.FIELDS]
     with open(path, "wb") as f:
         f.write(head.tobytes())
         f.write(rec.tobytes())
@@ -309,6 +368,33 @@ def read_variants(path):
     rec = np.frombuffer(data, VARIANT_DTYPE, count, VARIANTS_HEADER.itemsize)
     _check_variant_records(str(path), rec, glen)
     return Variants.from_records(rec), glen, CallParams(*(int(v) for v in head["params"]))
+
+
+def read_variants_qual(path):
+    """-> (Variants, genome length, CallParams, QualParams) of an ``MSWVARQ1``
+    file.  Raises ValueError as :func:`read_variants` does, and on a non-zero
+    word behind the weights."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < VARIANTS_QUAL_HEADER.itemsize:
+        raise ValueError(f"{path}: truncated header")
+    head = np.frombuffer(data, VARIANTS_QUAL_HEADER, 1)[0]
+    if bytes(head["magic"]) != VARIANTS_QUAL_MAGIC:
+        raise ValueError(f"{path}: bad magic")
+    if int(head["version"]) != VARIANTS_VERSION:
+        raise ValueError(f"{path}: version {int(head['version'])}, expected {VARIANTS_VERSION}")
+    if int(head["record_size"]) != VARIANT_DTYPE.itemsize:
+        raise ValueError(f"{path}: record size {int(head['record_size'])}, expected {VARIANT_DTYPE.itemsize}")
+    if int(head["reserved"]) != 0 or head["reserved2"].any():
+        raise ValueError(f"{path}: a reserved word of the header is not zero")
+    glen, count = int(head["glen"]), int(head["count"])
+    want = VARIANTS_QUAL_HEADER.itemsize + count * VARIANT_DTYPE.itemsize
+    if len(data) != want:
+        raise ValueError(f"{path}: {len(data)} bytes, the header's record count {count} asks for {want}")
+    rec = np.frombuffer(data, VARIANT_DTYPE, count, VARIANTS_QUAL_HEADER.itemsize)
+    _check_variant_records(str(path), rec, glen)
+    return (Variants.from_records(rec), glen, CallParams(*(int(v) for v in head["params"])),
+            QualParams(*(int(v) for v in head["qparams"])))
 
 
 def write_vcf(path, variants: Variants, genome, contig: str = "ref", sample: str = "sample") -> None:

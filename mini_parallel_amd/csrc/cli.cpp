@@ -114,6 +114,9 @@ void usage() {
         "      --call-min-alt N         --variants-out: least observations of the alternative (default 2)\n"
         "      --call-min-alt-permille N  --variants-out: least share of the alternative, 0..1000 (default 200)\n"
         "      --call-min-qual N        --variants-out: least quality of a call (default 20)\n"
+        "      --call-baseq             --variants-out: weigh every observation by its base quality (the lane\n"
+        "                               files' quality lines are read; the .var file is an MSWVARQ1 one)\n"
+        "      --qsum-out PATH          --call-baseq: write the per-base quality sums (.mqs)\n"
         "      --json PATH              write a JSON run record\n"
         "  -h, --help\n");
 }
@@ -168,6 +171,8 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--call-min-alt") { a.call_min_alt = atol(v().c_str()); a.has_call_flag = true; }
         else if (s == "--call-min-alt-permille") { a.call_min_alt_permille = atol(v().c_str()); a.has_call_flag = true; }
         else if (s == "--call-min-qual") { a.call_min_qual = atol(v().c_str()); a.has_call_flag = true; }
+        else if (s == "--call-baseq") a.call_baseq = true;
+        else if (s == "--qsum-out") a.qsum_out = v();
         else if (s == "-h" || s == "--help") { usage(); exit(0); }
         else die("error: unexpected argument '" + s + "' found\n\nFor more information, try '--help'.");
     }
@@ -219,6 +224,8 @@ Args parse_args(int argc, char** argv) {
     if (a.has_pileup_min_baseq && !a.wants_pileup()) die("error: --pileup-min-baseq needs --pileup-out or --variants-out");
     if (a.has_pileup_min_baseq && (a.pileup_min_baseq < 0 || a.pileup_min_baseq > 93))
         die("error: --pileup-min-baseq must be 0..93");
+    if (a.call_baseq && a.variants_out.empty()) die("error: --call-baseq needs --variants-out");
+    if (!a.qsum_out.empty() && !a.call_baseq) die("error: --qsum-out needs --call-baseq");
     if (a.has_pileup_min_depth && a.pileup_out.empty()) die("error: --pileup-min-depth needs --pileup-out");
     if (a.has_pileup_min_depth && a.pileup_min_depth < 1) die("error: --pileup-min-depth must be at least 1");
     if (a.has_call_flag && a.variants_out.empty()) die("error: the --call-* thresholds need --variants-out");
@@ -352,6 +359,8 @@ std::string stable_run_id(const std::string& dir, const std::string& sample, con
                std::to_string(a.call_min_qual);
     // nor does either with a base-quality threshold resume one without, or one with another (0 is the run without)
     if (a.wants_pileup() && a.pileup_min_baseq > 0) key += "|baseq|" + std::to_string(a.pileup_min_baseq);
+    // nor does a run with quality-weighted calls resume one without
+    if (a.call_baseq) key += "|callq";
     uint64_t h = 1469598103934665603ull;
     for (unsigned char c : key) { h ^= c; h *= 1099511628211ull; }
     char buf[32];
@@ -534,6 +543,12 @@ void write_run_record(const Args& a, const std::vector<Device>& devices, const W
           << ", \"snv\": " << v.by_kind[0] << ", \"del\": " << v.by_kind[1] << ", \"ins\": " << v.by_kind[2]
           << ", \"het\": " << v.by_gt[1] << ", \"hom\": " << v.by_gt[2];
         if (a.pileup_min_baseq > 0) j << ", \"min_baseq\": " << a.pileup_min_baseq << ", \"lowq_columns\": " << v.lowq_columns;
+        // --call-baseq only
+        if (a.call_baseq) {
+            msw_call_qparams_t qq;
+            msw_call_qparams_default(&qq);
+            j << ", \"baseq_weighted\": true, \"q_scale\": " << qq.q_scale << ", \"q_third\": " << qq.q_third;
+        }
         j << ", \"variants_ms\": " << v.ms << "}";
     }
     j

@@ -104,6 +104,11 @@ struct Args {
         q.min_qual = (uint32_t)call_min_qual;
         return q;
     }
+    // --call-baseq: the calls weigh every observation by its base quality (include/msw.h, "Quality sums and
+    // weighted genotypes"): the workers' readers keep the quality lines whatever --pileup-min-baseq says, their
+    // pileups carry quality sums, and the .var file is an MSWVARQ1 one; --qsum-out: the summed quality sums (.mqs)
+    bool call_baseq = false;
+    std::string qsum_out;
     // the workers keep pileups for either output
     bool wants_pileup() const { return !pileup_out.empty() || !variants_out.empty(); }
     long chunk_size = 1, num_files = -1;

@@ -20,6 +20,7 @@ struct LaneEnv {
     int gi;
     msw_pileup* pile;  // --pileup-out: this worker's pileup, else null
     uint32_t min_baseq;  // --pileup-min-baseq; above 0 the reader keeps quality rows
+    bool qsum;           // --call-baseq: the pileup carries quality sums, every add goes with the quality rows
 };
 
 // The pinned result block of a set: score i32 | ei i16 | ej i16 | rlen u16 | wlen u16, each [batch]
@@ -168,7 +169,7 @@ struct AlnSet {
         if (good && e.pile) {
             const msw_aln_t al{d_ref, d_nm, d_off, d_ops, ops_cap, d_off + e.batch + 1};
             // the quality rows are the reader's, in the order of the file, whichever way d.reads is oriented
-            good = (e.min_baseq ? msw_pileup_add_qual_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al,
+            good = (e.min_baseq || e.qsum ? msw_pileup_add_qual_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al,
                                                              strand, mapq, (uint32_t)e.a->pileup_min_mapq, quals,
                                                              qual_stride, e.min_baseq, stream)
                                 : msw_pileup_add_device(e.ctx, e.pile, d.reads, d.read_len, d.read_stride, n, &al, strand,
@@ -265,7 +266,8 @@ class LaneWorker {
     msw_genome* gen_ = nullptr;
     msw_index* idx_ = nullptr;  // --map
     msw_pileup* pile_ = nullptr;  // --pileup-out
-    uint32_t min_baseq_ = 0;      // --pileup-min-baseq (0: the reader keeps no qualities)
+    uint32_t min_baseq_ = 0;      // --pileup-min-baseq (0: the reader keeps no qualities, unless qsum_)
+    bool qsum_ = false;           // --call-baseq: quality rows and a MSW_PILEUP_QSUM pileup
     const uint8_t* batch_quals_ = nullptr;  // the quality rows of the batch next_batch returned last
     msw_seed_params_t seed_{};
     LaneEnv env_;
@@ -298,7 +300,9 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     const double t_ctx = ms_since(ts0_);
     // --pileup-min-baseq above 0: the reader keeps the records' quality lines beside the reads
     min_baseq_ = lanes_.pileup && a_.pileup_min_baseq > 0 ? (uint32_t)a_.pileup_min_baseq : 0u;
-    if ((min_baseq_ ? msw_gfastq_open_ex(ctx_.h, nullptr, read_stride(), batch_, MSW_GFASTQ_POS | MSW_GFASTQ_QUAL, 0, &gr_)
+    // --call-baseq: the quality lines too, at --pileup-min-baseq 0 as well
+    qsum_ = lanes_.pileup && a_.call_baseq;
+    if ((min_baseq_ || qsum_ ? msw_gfastq_open_ex(ctx_.h, nullptr, read_stride(), batch_, MSW_GFASTQ_POS | MSW_GFASTQ_QUAL, 0, &gr_)
                     : msw_gfastq_open(ctx_.h, nullptr, read_stride(), batch_, 1, 0, &gr_)) != MSW_OK)
         die(std::string("GPU lane reader: ") + msw_last_error());
     const double t_rd = ms_since(ts0_) - t_ctx;
@@ -331,9 +335,9 @@ LaneWorker::LaneWorker(LaneRun& lanes, int wi)
     const double t_kl = ms_since(tk0);
     const auto tres0 = Clock::now();
     // --pileup-out: this worker's pileup of the genome just uploaded, before the clock
-    if (lanes_.pileup && msw_pileup_create(ctx_.h, gen_, &pile_) != MSW_OK)
+    if (lanes_.pileup && msw_pileup_create_ex(ctx_.h, gen_, qsum_ ? MSW_PILEUP_QSUM : 0u, &pile_) != MSW_OK)
         die(std::string("GPU pileup error: ") + msw_last_error());
-    env_ = LaneEnv{ctx_.h, &sc_, gen_, &a_, batch_, gi_, pile_, min_baseq_};
+    env_ = LaneEnv{ctx_.h, &sc_, gen_, &a_, batch_, gi_, pile_, min_baseq_, qsum_};
     if (aln_) aln_stride_ = (uint32_t)std::min(4480L, std::max(1L, atol(env_or("MSW_CLI_CIGAR_STRIDE", "16").c_str())));
     for (ResultSet& r : res_) {
         r.d_score = (int32_t*)msw_dev_alloc(ctx_.h, batch_ * 4);
@@ -481,7 +485,7 @@ bool LaneWorker::next_batch(size_t fi, void* stream, msw_dev_reads_t* d) {
         return false;
     }
     batch_quals_ = nullptr;
-    if (min_baseq_ && msw_gfastq_quals(gr_, &batch_quals_) != MSW_OK) batch_quals_ = nullptr;
+    if ((min_baseq_ || qsum_) && msw_gfastq_quals(gr_, &batch_quals_) != MSW_OK) batch_quals_ = nullptr;
     run_.trace_ev(wi_, "batch", d->n);
     if (d->n == 0) reader_done(fi);
     return d->n != 0;
@@ -514,8 +518,10 @@ void LaneWorker::collect_pileup() {
     std::vector<uint32_t> mine(words);
     msw_pileup_summary_t s;
     uint64_t lowq = 0;
+    std::vector<uint32_t> mine_q(qsum_ ? words / 2 : 0);
     const bool ok = msw_pileup_finish(ctx_.h, pile_, nullptr) == MSW_OK &&
                     msw_pileup_counts(ctx_.h, pile_, mine.data()) == MSW_OK &&
+                    (!qsum_ || msw_pileup_qsums(ctx_.h, pile_, mine_q.data()) == MSW_OK) &&
                     msw_pileup_summary(ctx_.h, pile_, 1, &s) == MSW_OK &&
                     (!min_baseq_ || msw_pileup_lowq_columns(ctx_.h, pile_, &lowq) == MSW_OK);
     if (!ok) fprintf(stderr, "  GPU %d pileup error: %s\n", gi_, msw_last_error());
@@ -529,6 +535,14 @@ void LaneWorker::collect_pileup() {
     } else {
         uint32_t* sum = lanes_.pile_sum.data();
         for (size_t k = 0; k < words; ++k) sum[k] += mine[k];
+    }
+    if (qsum_) {
+        if (lanes_.qsum_sum.empty()) {
+            lanes_.qsum_sum.swap(mine_q);
+        } else {
+            uint32_t* sum = lanes_.qsum_sum.data();
+            for (size_t k = 0; k < mine_q.size(); ++k) sum[k] += mine_q[k];
+        }
     }
     lanes_.pile_used += s.reads_used;
     lanes_.pile_skipped += s.reads_skipped;

@@ -321,16 +321,26 @@ static void write_variants(WgsRun& run, LaneRun& lanes) {
     const uint64_t glen = g.size();
     if (lanes.pile_failed || lanes.pile_sum.size() != glen * 8) die("error: the pileup could not be read back from the GPUs");
     const msw_call_params_t q = run.a.call_params();
+    // --call-baseq: the weighted call on the summed quality sums (msw_call_counts_qual), an MSWVARQ1 file -- the 72
+    // bytes above, then q_scale, q_third and two zero words -- and, with --qsum-out, the .mqs file: a 32-byte header
+    // ("MSWQSUM1", u32 version 1, u32 channels 4, u64 genome length, u64 reads_used), then the rows of four
+    const bool weighted = run.a.call_baseq;
+    msw_call_qparams_t qq;
+    msw_call_qparams_default(&qq);
+    if (weighted && lanes.qsum_sum.size() != glen * 4) die("error: the quality sums could not be read back from the GPUs");
     std::vector<msw_variant_t> recs;
     {
         Ctx ctx(run.devices[0].ordinal, MSW_CTX_LEAN);
         uint64_t n = 0, again = 0;
         const uint8_t* gb = reinterpret_cast<const uint8_t*>(g.data());
-        if (msw_call_counts(ctx.h, gb, glen, lanes.pile_sum.data(), &q, 0, nullptr, 0, &n) != MSW_OK)
-            die(std::string("GPU variant call error: ") + msw_last_error());
+        auto call = [&](msw_variant_t* out, uint64_t cap, uint64_t* total) {
+            return weighted ? msw_call_counts_qual(ctx.h, gb, glen, lanes.pile_sum.data(), lanes.qsum_sum.data(), &q, &qq, 0,
+                                                   out, cap, total)
+                            : msw_call_counts(ctx.h, gb, glen, lanes.pile_sum.data(), &q, 0, out, cap, total);
+        };
+        if (call(nullptr, 0, &n) != MSW_OK) die(std::string("GPU variant call error: ") + msw_last_error());
         recs.resize(n);
-        if (n && (msw_call_counts(ctx.h, gb, glen, lanes.pile_sum.data(), &q, 0, recs.data(), n, &again) != MSW_OK ||
-                  again != n))
+        if (n && (call(recs.data(), n, &again) != MSW_OK || again != n))
             die(std::string("GPU variant call error: ") + msw_last_error());
     }
     VariantsReport& v = run.variants;
@@ -343,8 +353,9 @@ static void write_variants(WgsRun& run, LaneRun& lanes) {
     }
     FILE* f = fopen(run.a.variants_out.c_str(), "wb");
     if (!f) die("error: cannot create " + run.a.variants_out);
-    unsigned char head[72] = {0};
-    memcpy(head, "MSWVARS1", 8);
+    unsigned char head[88] = {0};
+    const size_t head_bytes = weighted ? 88 : 72;
+    memcpy(head, weighted ? "MSWVARQ1" : "MSWVARS1", 8);
     const uint32_t version = 1, rsize = (uint32_t)sizeof(msw_variant_t);
     const uint64_t count = recs.size();
     memcpy(head + 8, &version, 4);
@@ -352,9 +363,27 @@ static void write_variants(WgsRun& run, LaneRun& lanes) {
     memcpy(head + 16, &glen, 8);
     memcpy(head + 24, &count, 8);
     memcpy(head + 32, &q, 36);
-    static_assert(sizeof(msw_call_params_t) == 36 && sizeof(msw_variant_t) == 48, "the .var layout");
-    const bool ok = fwrite(head, 1, 72, f) == 72 && fwrite(recs.data(), sizeof(msw_variant_t), recs.size(), f) == recs.size();
+    if (weighted) memcpy(head + 72, &qq, 8);
+    static_assert(sizeof(msw_call_params_t) == 36 && sizeof(msw_variant_t) == 48 && sizeof(msw_call_qparams_t) == 8,
+                  "the .var layout");
+    const bool ok = fwrite(head, 1, head_bytes, f) == head_bytes &&
+                    fwrite(recs.data(), sizeof(msw_variant_t), recs.size(), f) == recs.size();
     if (fclose(f) != 0 || !ok) die("error: writing " + run.a.variants_out);
+    if (!run.a.qsum_out.empty()) {
+        FILE* fq = fopen(run.a.qsum_out.c_str(), "wb");
+        if (!fq) die("error: cannot create " + run.a.qsum_out);
+        unsigned char qh[32];
+        memcpy(qh, "MSWQSUM1", 8);
+        const uint32_t channels = 4;
+        const uint64_t used = lanes.pile_used;
+        memcpy(qh + 8, &version, 4);
+        memcpy(qh + 12, &channels, 4);
+        memcpy(qh + 16, &glen, 8);
+        memcpy(qh + 24, &used, 8);
+        const std::vector<uint32_t>& w = lanes.qsum_sum;
+        const bool okq = fwrite(qh, 1, 32, fq) == 32 && fwrite(w.data(), 4, w.size(), fq) == w.size();
+        if (fclose(fq) != 0 || !okq) die("error: writing " + run.a.qsum_out);
+    }
     v.ms = std::chrono::duration<double, std::milli>(Clock::now() - from).count();
 }
 

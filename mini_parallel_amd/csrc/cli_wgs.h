@@ -227,6 +227,7 @@ struct LaneRun {
     const bool pileup;
     std::mutex pile_mu;
     std::vector<uint32_t> pile_sum;
+    std::vector<uint32_t> qsum_sum;   // --call-baseq: the workers' quality sums [glen][4], summed beside the counts
     unsigned long long pile_used = 0, pile_skipped = 0, pile_lowq = 0;
     bool pile_failed = false;
 

@@ -57,11 +57,16 @@ __device__ __forceinline__ u64 row_depth(const Row& r) {
 
 // Candidate, genotypes and emission of one site (ref, a, n); fills the record's
 // numbers when v != nullptr.  All products in 64 bits, as the header states them.
-__device__ __forceinline__ bool call_site(const msw_call_params_t& q, u64 n, u64 ref, u64 a, msw_variant_t* v) {
+// W (msw.h, "Quality sums and weighted genotypes"): walt and wref stand for
+// a * q_miss and ref * q_miss, the cost of the alternative's observations under
+// 0/0 and of the reference's under 1/1; without W they are not read.
+template <bool W>
+__device__ __forceinline__ bool call_site(const msw_call_params_t& q, u64 n, u64 ref, u64 a, u64 wref, u64 walt,
+                                          msw_variant_t* v) {
     if (!(n >= q.min_depth && a >= q.min_alt && 1000ull * a >= (u64)q.min_alt_permille * n)) return false;
-    const u64 raw0 = ref * q.q_hit + a * q.q_miss;
+    const u64 raw0 = ref * q.q_hit + (W ? walt : a * q.q_miss);
     const u64 raw1 = (ref + a) * q.q_het;
-    const u64 raw2 = ref * q.q_miss + a * q.q_hit;
+    const u64 raw2 = (W ? wref : ref * q.q_miss) + a * q.q_hit;
     const u64 post0 = raw0, post1 = raw1 + q.prior_het, post2 = raw2 + q.prior_hom;
     uint32_t gt = 0;
     u64 best = post0;
@@ -89,7 +94,8 @@ __device__ __forceinline__ bool call_site(const msw_call_params_t& q, u64 n, u64
 
 // Both kinds of one position.  Returns bit 0: a column record, bit 1: an
 // insertion record; with EMIT the records go to col / ins.
-template <bool EMIT>
+// W: the position's row of quality sums is one 16-byte load beside the counts row.
+template <bool EMIT, bool W>
 __device__ __forceinline__ uint32_t call_position(const CallParams& p, const Row& r, u64 depth, u64 depth_next,
                                                   uint32_t gbyte, uint64_t pos, msw_variant_t* col,
                                                   msw_variant_t* ins) {
@@ -104,7 +110,16 @@ __device__ __forceinline__ uint32_t call_position(const CallParams& p, const Row
         for (uint32_t ch = 0; ch < 4; ++ch)
             if (ch != rc && (alt_ch == 8 || r.c[ch] > a)) a = r.c[ch], alt_ch = ch;
         if (r.c[5] > a) a = r.c[5], alt_ch = 5;
-        if (call_site(p.q, n, ref, a, EMIT ? col : nullptr)) {
+        u64 wref = 0, walt = 0;
+        if constexpr (W) {
+            const uint4 qs = *reinterpret_cast<const uint4*>(p.qsum + (pos - p.pos0) * 4u);
+            const uint32_t qr = rc == 0 ? qs.x : rc == 1 ? qs.y : rc == 2 ? qs.z : qs.w;
+            const uint32_t qa = alt_ch == 0 ? qs.x : alt_ch == 1 ? qs.y : alt_ch == 2 ? qs.z : qs.w;
+            wref = (u64)p.q_scale * qr + (u64)p.q_third * ref;
+            // a deleted base has no quality
+            walt = alt_ch == 5 ? (u64)a * p.q.q_miss : (u64)p.q_scale * qa + (u64)p.q_third * a;
+        }
+        if (call_site<W>(p.q, n, ref, a, wref, walt, EMIT ? col : nullptr)) {
             bits |= 1u;
             if (EMIT) {
                 col->pos = pos;
@@ -118,7 +133,7 @@ __device__ __forceinline__ uint32_t call_position(const CallParams& p, const Row
         const u64 a = r.c[6];
         const u64 span = std::min(depth, depth_next);
         const u64 ref = span > a ? span - a : 0;
-        if (call_site(p.q, ref + a, ref, a, EMIT ? ins : nullptr)) {
+        if (call_site<false>(p.q, ref + a, ref, a, 0, 0, EMIT ? ins : nullptr)) {
             bits |= 2u;
             if (EMIT) {
                 ins->pos = pos;
@@ -134,7 +149,7 @@ __device__ __forceinline__ uint32_t call_position(const CallParams& p, const Row
 // What both passes share: the thread's row and genome byte (zeros past m), and
 // depth(pos + 1) from the next lane; the wave's last lane and the last position
 // load row pos + 1 themselves when the slab holds it.
-template <bool EMIT>
+template <bool EMIT, bool W>
 __device__ __forceinline__ uint32_t call_thread(const CallParams& p, uint64_t k, msw_variant_t* col,
                                                 msw_variant_t* ins) {
     const bool live = k < p.m;
@@ -160,13 +175,14 @@ __device__ __forceinline__ uint32_t call_thread(const CallParams& p, uint64_t k,
     const u64 depth = row_depth(r);
     u64 depth_next = __shfl_down(depth, 1, 64);  // all 64 lanes, live or not
     if (edge) depth_next = depth_edge;
-    return live ? call_position<EMIT>(p, r, depth, depth_next, gbyte, p.pos0 + k, col, ins) : 0u;
+    return live ? call_position<EMIT, W>(p, r, depth, depth_next, gbyte, p.pos0 + k, col, ins) : 0u;
 }
 
+template <bool W>
 __global__ __launch_bounds__(kCallTile) void call_count_kernel(CallParams p) {
     __shared__ uint32_t wave_n[kCallTile / 64];
     const uint64_t k = (uint64_t)blockIdx.x * kCallTile + threadIdx.x;
-    const uint32_t bits = call_thread<false>(p, k, nullptr, nullptr);
+    const uint32_t bits = call_thread<false, W>(p, k, nullptr, nullptr);
     const uint32_t n = (uint32_t)__popcll(__ballot(bits & 1u)) + (uint32_t)__popcll(__ballot(bits & 2u));
     if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = n;
     __syncthreads();
@@ -180,6 +196,7 @@ __global__ __launch_bounds__(kCallTile) void call_count_kernel(CallParams p) {
     }
 }
 
+template <bool W>
 __global__ __launch_bounds__(kCallTile) void call_emit_kernel(CallParams p) {
     __shared__ uint32_t wave_n[kCallTile / 64];
     const uint64_t k = (uint64_t)blockIdx.x * kCallTile + threadIdx.x;
@@ -187,7 +204,7 @@ __global__ __launch_bounds__(kCallTile) void call_emit_kernel(CallParams p) {
     // a tile without records (most of them: variants are sparse) is not read again; the whole block leaves together
     if (p.tile_off[blockIdx.x + 1] == p.tile_off[blockIdx.x]) return;
     msw_variant_t col = {}, ins = {};  // the padding stays zero
-    const uint32_t bits = call_thread<true>(p, k, &col, &ins);
+    const uint32_t bits = call_thread<true, W>(p, k, &col, &ins);
     const u64 mc = __ballot(bits & 1u), mi = __ballot(bits & 2u);
     const u64 below = lane ? ~0ull >> (64u - lane) : 0ull;
     if (lane == 0) wave_n[wave] = (uint32_t)__popcll(mc) + (uint32_t)__popcll(mi);
@@ -220,7 +237,8 @@ uint64_t call_tmp_words(uint64_t m) {
 
 hipError_t launch_call_count(const CallParams& p, hipStream_t stream) {
     if (p.m == 0) return hipMemsetAsync(p.tile_off, 0, sizeof(uint32_t), stream);
-    hipLaunchKernelGGL(call_count_kernel, dim3((unsigned)call_tiles(p.m)), dim3(kCallTile), 0, stream, p);
+    if (p.qsum) hipLaunchKernelGGL(call_count_kernel<true>, dim3((unsigned)call_tiles(p.m)), dim3(kCallTile), 0, stream, p);
+    else hipLaunchKernelGGL(call_count_kernel<false>, dim3((unsigned)call_tiles(p.m)), dim3(kCallTile), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -235,7 +253,8 @@ hipError_t launch_call_scan(const CallParams& p, hipStream_t stream) {
 
 hipError_t launch_call_emit(const CallParams& p, hipStream_t stream) {
     if (p.m == 0 || p.cap == 0) return hipSuccess;
-    hipLaunchKernelGGL(call_emit_kernel, dim3((unsigned)call_tiles(p.m)), dim3(kCallTile), 0, stream, p);
+    if (p.qsum) hipLaunchKernelGGL(call_emit_kernel<true>, dim3((unsigned)call_tiles(p.m)), dim3(kCallTile), 0, stream, p);
+    else hipLaunchKernelGGL(call_emit_kernel<false>, dim3((unsigned)call_tiles(p.m)), dim3(kCallTile), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -361,10 +361,20 @@ struct PileupQual {
     unsigned long long* lowq;
 };
 hipError_t launch_pileup_add_qual(const PileupParams& p, const PileupQual& q, hipStream_t stream);
+// Quality sums beside the counts (msw.h, "Quality sums and weighted genotypes"): the state of a
+// MSW_PILEUP_QSUM pileup, taken beside the params by a third kernel instance.  min_baseq may be 0 here.
+struct PileupQsum : PileupQual {
+    uint32_t* d_q;              // [glen + 1] differences of the summed Phred values of counted M columns, modulo 2^32
+    uint32_t* qmis;             // [glen] the summed Phred values of counted columns whose read byte differs from the genome byte
+    uint32_t* qsum;             // [glen][4], rows of four
+};
+hipError_t launch_pileup_add_qsum(const PileupParams& p, const PileupQsum& q, hipStream_t stream);
 // blocks per CU of pileup_add_kernel; the query loads the module
 int pileup_blocks_per_cu();
 // scans d_all and d_rev in place and folds them and mism into counts
 hipError_t launch_pileup_finish(const PileupParams& p, uint32_t* scan_tmp, hipStream_t stream);
+// the same, then one more scan over q.d_q and its fold with q.qmis into q.qsum (the quality fields of q are not read)
+hipError_t launch_pileup_finish_qsum(const PileupParams& p, const PileupQsum& q, uint32_t* scan_tmp, hipStream_t stream);
 // stats[4] (device): covered, depth_sum, minority_ref, max_depth of finished counts
 hipError_t launch_pileup_summary(const PileupParams& p, uint32_t min_depth, unsigned long long* stats,
                                  hipStream_t stream);
@@ -388,6 +398,9 @@ struct CallParams {
     msw_variant_t* out;        // [cap], or null with cap 0
     uint64_t cap;
     unsigned long long* n_total;  // device, or null
+    // the weighted calls only (msw.h, "Quality sums and weighted genotypes"): qsum[k * 4 + c], 16-byte aligned
+    const uint32_t* qsum;
+    uint32_t q_scale, q_third;
 };
 inline uint64_t call_tiles(uint64_t m) { return (m + kCallTile - 1) / kCallTile; }
 // u32 words of tile_off plus the scan's temporaries behind it
@@ -399,6 +412,7 @@ hipError_t launch_call(const CallParams& p, hipStream_t stream);
 hipError_t launch_call_count(const CallParams& p, hipStream_t stream);
 hipError_t launch_call_scan(const CallParams& p, hipStream_t stream);
 hipError_t launch_call_emit(const CallParams& p, hipStream_t stream);
+// Every launch above runs the weighted instances when p.qsum != nullptr.
 
 // Placing reads (msw_seed.hip; the contract is in include/msw.h).
 constexpr uint32_t kSeedMaxCap = 8192;      // keys one read's LDS array holds (32 KiB)

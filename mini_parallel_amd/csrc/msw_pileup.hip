@@ -19,6 +19,7 @@
 // base-quality threshold (msw_pileup_add_qual*) a second instance of the kernel
 // runs, which also reads one quality byte per column.
 #include <algorithm>
+#include <type_traits>
 
 #include "msw_kernels.h"
 
@@ -52,11 +53,25 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 // wrapped -1 on channel 7, which the fold's += d_rev brings back in range.
 // Q is empty (the plain add: its arguments and code are what they were without
 // the filter) or one PileupQual.
+//
+// QSUM (a PileupQsum in Q; msw.h, "Quality sums and weighted genotypes"): the
+// Phred sums in the same difference form.  With e_k the Phred value of column k
+// of the run's range [lo, hi) when it counts and 0 when it is dropped, the lane
+// of column k adds e_k - e_(k-1) to d_q[g + k] (e_(lo-1) = 0; the neighbour's
+// byte is a second load, not a shuffle) and the lane of column hi - 1 adds
+// -e_(hi-1) to d_q[g + hi]: a stretch of one quality value costs no atomic.  A
+// counted mismatching column also adds e_k to qmis[pos] and, where its code is
+// below 4, to qsum[pos][code]; the fold is qsum[pos][code(genome[pos])] +=
+// scanned d_q[pos + 1] - qmis[pos].  Here min_baseq may be 0: a column counts
+// when t < qual_stride and its Phred value is at least min_baseq.
 __device__ __forceinline__ const PileupQual& qual_of(const PileupQual& q) { return q; }
+__device__ __forceinline__ const PileupQsum& qsum_of(const PileupQsum& q) { return q; }
+__device__ __forceinline__ uint32_t phred_of(uint32_t b) { return b >= 33u ? b - 33u : 0u; }
 
 template <typename... Q>
 __global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p, Q... qual) {
     constexpr bool QUAL = sizeof...(Q) == 1;
+    constexpr bool QSUM = (std::is_same<Q, PileupQsum>::value || ...);
     __shared__ uint32_t tally[4][QUAL ? 3 : 2];
     const int lane = (int)(threadIdx.x & 63u);
     const uint64_t wave = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -103,7 +118,38 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(PileupParams p, Q... qu
                     }
                     for (int64_t k = lo + lane; k < hi; k += 64) {
                         const uint32_t rb = flip ? comp_byte(rd[rl - 1 - (i + k)]) : (uint32_t)rd[i + k];
-                        if constexpr (QUAL) {
+                        if constexpr (QSUM) {
+                            const PileupQsum& qs = qsum_of(qual...);
+                            const int64_t t = rev ? rl - 1 - (i + k) : i + k;
+                            const uint32_t ph = t < (int64_t)qs.qual_stride ? phred_of(qrow[t]) : 0u;
+                            const bool keep = t < (int64_t)qs.qual_stride && ph >= qs.min_baseq;
+                            const uint32_t e = keep ? ph : 0u;
+                            // column k - 1 of the same range: lo <= k - 1, so its index is in [0, rl) too
+                            uint32_t prev = 0;
+                            if (k > lo) {
+                                const int64_t tp = rev ? t + 1 : t - 1;
+                                if (tp < (int64_t)qs.qual_stride) {
+                                    const uint32_t pp = phred_of(qrow[tp]);
+                                    prev = pp >= qs.min_baseq ? pp : 0u;
+                                }
+                            }
+                            if (e != prev) atomicAdd(qs.d_q + (g + k), e - prev);
+                            if (k == hi - 1 && e) atomicAdd(qs.d_q + (g + hi), 0u - e);
+                            if (!keep) {
+                                ++lowq;
+                                atomicAdd(p.mism + (g + k), 1u);
+                                if (rev) atomicAdd(p.counts + (uint64_t)(g + k) * p.pos_mul + 7u * p.ch_mul, 0xFFFFFFFFu);
+                            } else if (rb != p.genome[g + k]) {
+                                const uint32_t c = base_code(rb);
+                                atomicAdd(p.counts + (uint64_t)(g + k) * p.pos_mul + c * p.ch_mul, 1u);
+                                atomicAdd(p.mism + (g + k), 1u);
+                                if (e) {
+                                    atomicAdd(qs.qmis + (g + k), e);
+                                    if (c < 4u) atomicAdd(qs.qsum + (uint64_t)(g + k) * 4u + c, e);
+                                }
+                            }
+                            continue;
+                        } else if constexpr (QUAL) {
                             // 0 <= i + k < rl here, so t is in [0, rl) either way; the quality rows are in the
                             // order of the reads as given, whatever the orientation of `rows`
                             const int64_t t = rev ? rl - 1 - (i + k) : i + k;
@@ -188,6 +234,15 @@ __global__ __launch_bounds__(256) void pileup_finish_kernel(PileupParams p) {
             p.counts[pos * p.pos_mul + c * p.ch_mul] += same;
             p.counts[pos * p.pos_mul + 7u * p.ch_mul] += rev;
         }
+    }
+}
+
+// qsum[pos][code(genome[pos])] += d_q[pos + 1] - qmis[pos] where that code is below 4 (d_q scanned)
+__global__ __launch_bounds__(256) void pileup_finish_qsum_kernel(PileupParams p, PileupQsum q) {
+    const uint64_t step = (uint64_t)gridDim.x * 256u;
+    for (uint64_t pos = (uint64_t)blockIdx.x * 256u + threadIdx.x; pos < p.glen; pos += step) {
+        const uint32_t c = base_code(p.genome[pos]);
+        if (c < 4u) q.qsum[pos * 4u + c] += q.d_q[pos + 1] - q.qmis[pos];
     }
 }
 
@@ -284,6 +339,22 @@ hipError_t launch_pileup_add_qual(const PileupParams& p, const PileupQual& q, hi
     if (p.n == 0) return hipSuccess;
     const uint64_t blocks = std::min<uint64_t>((p.n + 3) / 4, 1u << 20);
     hipLaunchKernelGGL(pileup_add_kernel<PileupQual>, dim3((unsigned)blocks), dim3(256), 0, stream, p, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_pileup_add_qsum(const PileupParams& p, const PileupQsum& q, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    const uint64_t blocks = std::min<uint64_t>((p.n + 3) / 4, 1u << 20);
+    hipLaunchKernelGGL(pileup_add_kernel<PileupQsum>, dim3((unsigned)blocks), dim3(256), 0, stream, p, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_pileup_finish_qsum(const PileupParams& p, const PileupQsum& q, uint32_t* scan_tmp,
+                                     hipStream_t stream) {
+    hipError_t e = launch_pileup_finish(p, scan_tmp, stream);
+    if (e == hipSuccess) e = scan_in_place(q.d_q, p.glen + 1, scan_tmp, stream);
+    if (e != hipSuccess || p.glen == 0) return e;
+    hipLaunchKernelGGL(pileup_finish_qsum_kernel, dim3(grid_for(p.glen)), dim3(256), 0, stream, p, q);
     return hipGetLastError();
 }
 

@@ -3127,8 +3127,11 @@ struct msw_pileup {
     int device = 0;
     // one allocation: counts [glen][8] | the read counters' slots + stats u64[4] + the low-quality column counter's
     // slots | d_all [glen + 1] | d_rev [glen + 1] | mism [glen] | the scan's block sums
+    // and with MSW_PILEUP_QSUM: | qsum [glen][4] | d_q [glen + 1] | qmis [glen]
     uint8_t* d_state = nullptr;
     msw::PileupParams p{};         // the state's part; an add fills in its batch
+    uint32_t flags = 0;
+    msw::PileupQsum qs{};          // the state's part (d_q, qmis, qsum, lowq), with MSW_PILEUP_QSUM
     unsigned long long* d_stats = nullptr;
     unsigned long long* d_lowq = nullptr;  // PileupQual::lowq
     uint32_t* d_scan_tmp = nullptr;
@@ -3143,8 +3146,14 @@ static int check_pileup(const msw_ctx* ctx, const msw_pileup* pile) {
 }
 
 int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
+    return msw_pileup_create_ex(ctx, g, 0, out);
+}
+
+int msw_pileup_create_ex(msw_ctx* ctx, const msw_genome* g, uint32_t flags, msw_pileup** out) {
     if (!ctx || !g || !out) return fail(MSW_E_INVALID, "ctx/genome/out is NULL");
     *out = nullptr;
+    if (flags & ~MSW_PILEUP_QSUM) return fail(MSW_E_INVALID, "pileup create: unknown flag in 0x%x", flags);
+    const bool qsum = (flags & MSW_PILEUP_QSUM) != 0;
     if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
     int rc = set_device(ctx);
     if (rc) return rc;
@@ -3155,9 +3164,12 @@ int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
     const uint64_t o_reads = (glen * 32 + 127) & ~(uint64_t)127, o_all = o_reads + (read_words + 16 + lowq_words) * 8,
                    o_rev = o_all + up16((glen + 1) * 4),
                    o_mism = o_rev + up16((glen + 1) * 4), o_tmp = o_mism + up16(glen * 4),
-                   total = o_tmp + up16(msw::pileup_scan_tmp_words(glen) * 4) + 16;
+                   o_qsum = o_tmp + up16(msw::pileup_scan_tmp_words(glen) * 4) + 16,
+                   o_dq = o_qsum + (qsum ? glen * 16 : 0), o_qmis = o_dq + (qsum ? up16((glen + 1) * 4) : 0),
+                   total = o_qmis + (qsum ? up16(glen * 4) + 16 : 0);
     msw_pileup* pile = new msw_pileup();
     pile->ctx = ctx;
+    pile->flags = flags;
     pile->device = ctx->device;
     hipError_t e = hipMalloc((void**)&pile->d_state, total);
     if (e != hipSuccess) {
@@ -3180,6 +3192,12 @@ int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
     p.d_rev = reinterpret_cast<uint32_t*>(pile->d_state + o_rev);
     p.mism = reinterpret_cast<uint32_t*>(pile->d_state + o_mism);
     pile->d_scan_tmp = reinterpret_cast<uint32_t*>(pile->d_state + o_tmp);
+    if (qsum) {
+        pile->qs.lowq = pile->d_lowq;
+        pile->qs.qsum = reinterpret_cast<uint32_t*>(pile->d_state + o_qsum);
+        pile->qs.d_q = reinterpret_cast<uint32_t*>(pile->d_state + o_dq);
+        pile->qs.qmis = reinterpret_cast<uint32_t*>(pile->d_state + o_qmis);
+    }
     // the kernels' code object, loaded here rather than inside the first add (HIP loads a module on first use)
     (void)msw::pileup_blocks_per_cu();
     e = hipEventCreateWithFlags(&pile->fin, hipEventDisableTiming);
@@ -3199,6 +3217,13 @@ void msw_pileup_destroy(msw_pileup* pile) {
     if (pile->fin) (void)hipEventDestroy(pile->fin);
     if (pile->d_state) (void)hipFree(pile->d_state);
     delete pile;
+}
+
+// a MSW_PILEUP_QSUM pileup takes no add without qualities
+static int check_pileup_qsum_add(const msw_ctx* ctx, const msw_pileup* pile, const uint8_t* quals) {
+    if (ctx && pile && pile->ctx == ctx && (pile->flags & MSW_PILEUP_QSUM) && !quals)
+        return fail(MSW_E_INVALID, "pileup add: a MSW_PILEUP_QSUM pileup needs quals (msw_pileup_add_qual*)");
+    return MSW_OK;
 }
 
 // the checks both add forms share; *go = false: nothing to do
@@ -3234,6 +3259,7 @@ int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* ro
     if (min_baseq > 93u) return fail(MSW_E_RANGE, "pileup add: min_baseq %u > 93", min_baseq);
     int rc;
     bool go;
+    if ((rc = check_pileup_qsum_add(ctx, pile, quals))) return rc;
     if ((rc = check_pileup_add(ctx, pile, rows, read_len, row_stride, n, aln, min_mapq, &go)) || !go) return rc;
     if ((rc = set_device(ctx))) return rc;
     msw::PileupParams p = pile->p;
@@ -3249,7 +3275,13 @@ int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* ro
     p.strand = strand;
     p.mapq = mapq;
     p.min_mapq = min_mapq;
-    if (quals && min_baseq) {  // else the plain add
+    if (pile->flags & MSW_PILEUP_QSUM) {
+        msw::PileupQsum q = pile->qs;
+        q.quals = quals;
+        q.qual_stride = qual_stride;
+        q.min_baseq = min_baseq;
+        HIP_TRY(msw::launch_pileup_add_qsum(p, q, call_stream(ctx, stream)));
+    } else if (quals && min_baseq) {  // else the plain add
         const msw::PileupQual q{quals, qual_stride, min_baseq, pile->d_lowq};
         HIP_TRY(msw::launch_pileup_add_qual(p, q, call_stream(ctx, stream)));
     } else {
@@ -3270,10 +3302,12 @@ int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, co
                         const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
                         uint32_t min_baseq, uint64_t chunk_reads) {
     if (min_baseq > 93u) return fail(MSW_E_RANGE, "pileup add: min_baseq %u > 93", min_baseq);
-    if (min_baseq == 0) quals = nullptr;  // the plain add
-    if (!quals) qual_stride = 0;
     int rc;
     bool go;
+    if ((rc = check_pileup_qsum_add(ctx, pile, quals))) return rc;
+    const bool qsum = ctx && pile && pile->ctx == ctx && (pile->flags & MSW_PILEUP_QSUM);
+    if (min_baseq == 0 && !qsum) quals = nullptr;  // the plain add
+    if (!quals) qual_stride = 0;
     if ((rc = check_pileup_add(ctx, pile, reads, read_len, read_stride, n, aln, min_mapq, &go)) || !go) return rc;
     const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
     // the offsets decide what is uploaded: they must be a prefix sum inside the capacity
@@ -3319,6 +3353,10 @@ int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, co
     p.min_mapq = min_mapq;
     p.orient = strand ? 1u : 0u;
     const msw::PileupQual q{d + o_q, qual_stride, min_baseq, pile->d_lowq};
+    msw::PileupQsum qq = pile->qs;
+    qq.quals = q.quals;
+    qq.qual_stride = qual_stride;
+    qq.min_baseq = min_baseq;
     for (uint64_t lo = 0; lo < n && e == hipSuccess; lo += chunk) {
         const uint64_t c = std::min(chunk, n - lo);
         auto up = [&](size_t at, const void* src, size_t bytes) {
@@ -3336,7 +3374,9 @@ int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, co
         if (quals) up(o_q, quals + lo * qs, c * qs);
         p.n = c;
         p.cigar_base = o0;
-        if (e == hipSuccess) e = quals ? msw::launch_pileup_add_qual(p, q, st) : msw::launch_pileup_add(p, st);
+        if (e == hipSuccess)
+            e = qsum ? msw::launch_pileup_add_qsum(p, qq, st)
+                     : quals ? msw::launch_pileup_add_qual(p, q, st) : msw::launch_pileup_add(p, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);  // the buffers are the next chunk's
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(st);
@@ -3351,7 +3391,8 @@ int msw_pileup_finish(msw_ctx* ctx, msw_pileup* pile, void* stream) {
     if (pile->finished) return MSW_OK;
     if ((rc = set_device(ctx))) return rc;
     hipStream_t st = call_stream(ctx, stream);
-    HIP_TRY(msw::launch_pileup_finish(pile->p, pile->d_scan_tmp, st));
+    if (pile->flags & MSW_PILEUP_QSUM) HIP_TRY(msw::launch_pileup_finish_qsum(pile->p, pile->qs, pile->d_scan_tmp, st));
+    else HIP_TRY(msw::launch_pileup_finish(pile->p, pile->d_scan_tmp, st));
     HIP_TRY(hipEventRecord(pile->fin, st));
     pile->finished = true;
     return MSW_OK;
@@ -3445,7 +3486,57 @@ int msw_pileup_lowq_columns(msw_ctx* ctx, msw_pileup* pile, uint64_t* out) {
     return MSW_OK;
 }
 
+// Quality sums (include/msw.h, "Quality sums and weighted genotypes").
+static int check_pileup_qsum(const msw_ctx* ctx, const msw_pileup* pile, const char* what) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!(pile->flags & MSW_PILEUP_QSUM)) return fail(MSW_E_INVALID, "%s: the pileup was created without MSW_PILEUP_QSUM", what);
+    return MSW_OK;
+}
+
+int msw_pileup_qsums_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** qsums, uint64_t* pos_stride,
+                            uint64_t* ch_stride) {
+    int rc;
+    if ((rc = check_pileup_qsum(ctx, pile, "pileup qsums"))) return rc;
+    if (!qsums || !pos_stride || !ch_stride) return fail(MSW_E_INVALID, "NULL output");
+    *qsums = pile->qs.qsum;
+    *pos_stride = 4;
+    *ch_stride = 1;
+    return MSW_OK;
+}
+
+int msw_pileup_qsums(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out) {
+    int rc;
+    if ((rc = check_pileup_qsum(ctx, pile, "pileup qsums"))) return rc;
+    if (!pile->finished) return fail(MSW_E_INVALID, "pileup qsums before msw_pileup_finish");
+    const uint64_t glen = pile->p.glen;
+    if (glen == 0) return MSW_OK;
+    if (!host_out) return fail(MSW_E_INVALID, "host_out is NULL");
+    if ((rc = set_device(ctx))) return rc;
+    HIP_TRY(hipEventSynchronize(pile->fin));
+    hipStream_t st = ctx->compute;
+    HIP_TRY(hipMemcpyAsync(host_out, pile->qs.qsum, glen * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MSW_OK;
+}
+
 // Variants (include/msw.h, "Variants"; the kernels: msw_call.hip).
+void msw_call_qparams_default(msw_call_qparams_t* q) {
+    if (!q) return;
+    *q = msw_call_qparams_t{100, 477};
+}
+
+static int check_call_qparams(const msw_call_qparams_t* qparams, msw::CallParams* p) {
+    msw_call_qparams_t q;
+    if (qparams) q = *qparams;
+    else msw_call_qparams_default(&q);
+    if (q.q_scale > 65535u || q.q_third > 65535u)
+        return fail(MSW_E_INVALID, "call qparams: q_scale or q_third above 65535");
+    p->q_scale = q.q_scale;
+    p->q_third = q.q_third;
+    return MSW_OK;
+}
+
 void msw_call_params_default(msw_call_params_t* q) {
     if (!q) return;
     *q = msw_call_params_t{4, 2, 200, 20, 4, 2477, 304, 3000, 3301};
@@ -3463,12 +3554,15 @@ static int check_call_params(const msw_call_params_t* params, msw_call_params_t*
 
 static_assert(sizeof(msw_variant_t) == 48, "msw_variant_t is 48 bytes, in memory and in the .var file");
 
-int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_dev,
-                           uint64_t cap, uint64_t* n_total_dev, void* stream) {
+// both device forms; weighted: the call of "Quality sums and weighted genotypes"
+static int pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, bool weighted,
+                              const msw_call_qparams_t* qparams, msw_variant_t* out_dev, uint64_t cap,
+                              uint64_t* n_total_dev, void* stream) {
     int rc;
     msw::CallParams p{};
-    if ((rc = check_pileup(ctx, pile))) return rc;
+    if ((rc = weighted ? check_pileup_qsum(ctx, pile, "pileup call") : check_pileup(ctx, pile))) return rc;
     if ((rc = check_call_params(params, &p.q))) return rc;
+    if (weighted && (rc = check_call_qparams(qparams, &p))) return rc;
     if (!pile->finished) return fail(MSW_E_INVALID, "pileup call before msw_pileup_finish");
     if (cap && !out_dev) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
     if (pile->p.glen > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "pileup call: genome above 2^31-1 bases");
@@ -3484,6 +3578,7 @@ int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params
     p.out = out_dev;
     p.cap = cap;
     p.n_total = reinterpret_cast<unsigned long long*>(n_total_dev);
+    p.qsum = weighted ? pile->qs.qsum : nullptr;
     HIP_TRY(hipMallocAsync((void**)&p.tile_off, msw::call_tmp_words(p.m) * sizeof(uint32_t), st));
     hipError_t e = msw::launch_call(p, st);
     const hipError_t ef = hipFreeAsync(p.tile_off, st);
@@ -3492,10 +3587,21 @@ int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params
     return MSW_OK;
 }
 
-int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_host,
-                    uint64_t cap, uint64_t* n_total) {
+int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_dev,
+                           uint64_t cap, uint64_t* n_total_dev, void* stream) {
+    return pileup_call_device(ctx, pile, params, false, nullptr, out_dev, cap, n_total_dev, stream);
+}
+
+int msw_pileup_call_qual_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params,
+                                const msw_call_qparams_t* qparams, msw_variant_t* out_dev, uint64_t cap,
+                                uint64_t* n_total_dev, void* stream) {
+    return pileup_call_device(ctx, pile, params, true, qparams, out_dev, cap, n_total_dev, stream);
+}
+
+static int pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, bool weighted,
+                       const msw_call_qparams_t* qparams, msw_variant_t* out_host, uint64_t cap, uint64_t* n_total) {
     int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
+    if ((rc = weighted ? check_pileup_qsum(ctx, pile, "pileup call") : check_pileup(ctx, pile))) return rc;
     if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
     if (cap && !out_host) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
     if ((rc = set_device(ctx))) return rc;
@@ -3510,7 +3616,8 @@ int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* par
     }
     hipStream_t st = ctx->compute;
     msw_variant_t* d_out = reinterpret_cast<msw_variant_t*>(d + 16);
-    rc = msw_pileup_call_device(ctx, pile, params, dcap ? d_out : nullptr, dcap, reinterpret_cast<uint64_t*>(d), st);
+    rc = pileup_call_device(ctx, pile, params, weighted, qparams, dcap ? d_out : nullptr, dcap,
+                            reinterpret_cast<uint64_t*>(d), st);
     if (rc == MSW_OK) {
         uint64_t total = 0;
         e = hipMemcpyAsync(&total, d, 8, hipMemcpyDeviceToHost, st);
@@ -3527,25 +3634,37 @@ int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* par
     return rc;
 }
 
-int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
-                    const msw_call_params_t* params, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
-                    uint64_t* n_total) {
+int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_host,
+                    uint64_t cap, uint64_t* n_total) {
+    return pileup_call(ctx, pile, params, false, nullptr, out_host, cap, n_total);
+}
+
+int msw_pileup_call_qual(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params,
+                         const msw_call_qparams_t* qparams, msw_variant_t* out_host, uint64_t cap, uint64_t* n_total) {
+    return pileup_call(ctx, pile, params, true, qparams, out_host, cap, n_total);
+}
+
+static int call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
+                       bool weighted, const uint32_t* qsums_host, const msw_call_params_t* params,
+                       const msw_call_qparams_t* qparams, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
+                       uint64_t* n_total) {
     int rc;
     msw::CallParams p{};
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
     if ((rc = check_call_params(params, &p.q))) return rc;
+    if (weighted && (rc = check_call_qparams(qparams, &p))) return rc;
     if (cap && !out_host) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
     if (chunk_pos > (1ull << 24)) return fail(MSW_E_RANGE, "call counts: chunk_pos above 2^24");
     *n_total = 0;
     if (glen == 0) return MSW_OK;
-    if (!genome_host || !counts_host) return fail(MSW_E_INVALID, "NULL array");
+    if (!genome_host || !counts_host || (weighted && !qsums_host)) return fail(MSW_E_INVALID, "NULL array");
     if ((rc = set_device(ctx))) return rc;
     const uint64_t chunk = std::min<uint64_t>(glen, chunk_pos ? chunk_pos : 1ull << 20);
     auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    // [rows of chunk + 1 positions | genome bytes | total u64 | tile offsets and scan words]
+    // [rows of chunk + 1 positions | genome bytes | total u64 | tile offsets and scan words | weighted: rows of four]
     const uint64_t o_gen = (chunk + 1) * 32, o_tot = o_gen + up16(chunk), o_tile = o_tot + 16,
-                   bytes = o_tile + up16(msw::call_tmp_words(chunk) * 4);
+                   o_qsum = o_tile + up16(msw::call_tmp_words(chunk) * 4), bytes = o_qsum + (weighted ? chunk * 16 : 0);
     uint8_t* d = nullptr;
     hipError_t e = hipMalloc((void**)&d, bytes);
     if (e != hipSuccess) {
@@ -3559,6 +3678,7 @@ int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, con
     p.ch_mul = 1;
     p.n_total = reinterpret_cast<unsigned long long*>(d + o_tot);
     p.tile_off = reinterpret_cast<uint32_t*>(d + o_tile);
+    p.qsum = weighted ? reinterpret_cast<const uint32_t*>(d + o_qsum) : nullptr;
     msw_variant_t* d_out = nullptr;  // grows to the largest chunk's records that still fit cap
     uint64_t d_out_cap = 0, total = 0, written = 0;
     bool nomem = false;
@@ -3571,6 +3691,8 @@ int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, con
         p.cap = 0;
         e = hipMemcpyAsync(d, counts_host + lo * 8, p.rows * 32, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d + o_gen, genome_host + lo, m, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && weighted)
+            e = hipMemcpyAsync(d + o_qsum, qsums_host + lo * 4, m * 16, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = msw::launch_call_count(p, st);
         if (e == hipSuccess) e = msw::launch_call_scan(p, st);
         uint64_t t = 0;
@@ -3608,6 +3730,21 @@ int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, con
     if (e != hipSuccess) return fail(MSW_E_DEVICE, "call counts: %s", hipGetErrorString(e));
     *n_total = total;
     return MSW_OK;
+}
+
+int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
+                    const msw_call_params_t* params, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
+                    uint64_t* n_total) {
+    return call_counts(ctx, genome_host, glen, counts_host, false, nullptr, params, nullptr, chunk_pos, out_host, cap,
+                       n_total);
+}
+
+int msw_call_counts_qual(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
+                         const uint32_t* qsums_host, const msw_call_params_t* params,
+                         const msw_call_qparams_t* qparams, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
+                         uint64_t* n_total) {
+    return call_counts(ctx, genome_host, glen, counts_host, true, qsums_host, params, qparams, chunk_pos, out_host, cap,
+                       n_total);
 }
 
 int msw_memcpy_d2h_async(msw_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {

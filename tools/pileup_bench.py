@@ -17,6 +17,15 @@ both strands, traced and packed on the device.  HIP events on the stream,
   finish      msw_pileup_finish of a pileup holding one add (a fresh pileup per
               launch: the fold runs once per pileup)
   summary     msw_pileup_summary, wall time of the synchronous call
+  add_qual    msw_pileup_add_qual_device (threshold 20) of the same records with
+              quality rows, "binned" (NovaSeq-style, 84 % one value) and
+              "illumina" (drifting, noisy) as synthetic.py writes them
+  add_qsum    the same on a MSW_PILEUP_QSUM pileup, at
+              thresholds 0 and 20, alternated with add_qual; qsum_atomics_per_read
+              is the number of d_q adds the quality rows ask for (changes between
+              neighbouring bases, the first and the last column), an upper bound
+              that takes every read for one M run
+  finish_qsum msw_pileup_finish of such a pileup (one more scan and fold)
 
   python3 tools/pileup_bench.py [--planes] [--reads 40000]"""
 import argparse
@@ -155,6 +164,53 @@ def main():
         if k + 1 < args.warmup + args.steps:
             pk.close()
     rec["finish_ms"] = round(sum(ms) / len(ms), 4)
+
+    # quality rows in the order of the reads as given, one per read, stride rs
+    def quality_rows(kind):
+        rng = np.random.default_rng(5)
+        rl = b.read_len.astype(np.int64)
+        if kind == "binned":
+            q = rng.choice(np.frombuffer(b"F:,#", np.uint8), (n, rs), p=[0.84, 0.11, 0.04, 0.01])
+        else:
+            q = (np.clip(40 - np.arange(rs)[None, :] // 12 + rng.integers(-6, 3, (n, rs)), 2, 41) + 33).astype(np.uint8)
+        inside = np.arange(rs)[None, :] < rl[:, None]
+        changes = ((q[:, 1:] != q[:, :-1]) & inside[:, 1:]).sum() + 2 * n
+        return up(q), round(float(changes) / n, 2)
+
+    def add_qual_to(pile, d_q, min_baseq):
+        pile.add_device(oriented.data_ptr(), d_rl.data_ptr(), ors, n, ref.data_ptr(), nm.data_ptr(), off.data_ptr(),
+                        ops.data_ptr(), cap, strand.data_ptr(), 0, 0, s, d_q.data_ptr(), rs, min_baseq)
+
+    for kind in ("binned", "illumina"):
+        d_q, per_read = quality_rows(kind)
+        rec["qsum_atomics_per_read_" + kind] = per_read
+        plain, flagged = ctx.pileup(genome), ctx.pileup(genome, qsum=True)
+        runs = {"add_qual_ms": [], "add_qsum_ms": [], "add_qsum_q0_ms": []}
+        for _ in range(3):                      # alternated: one process, the same clocks
+            runs["add_qual_ms"].append(timed(lambda: add_qual_to(plain, d_q, 20)))
+            runs["add_qsum_ms"].append(timed(lambda: add_qual_to(flagged, d_q, 20)))
+            runs["add_qsum_q0_ms"].append(timed(lambda: add_qual_to(flagged, d_q, 0)))
+        for k, v in runs.items():
+            rec[k + "_" + kind] = sorted(v)[1]
+            rec[k + "_" + kind + "_runs"] = v
+        plain.close()
+        flagged.close()
+    ms = []
+    for k in range(args.warmup + args.steps):
+        pq = ctx.pileup(genome, qsum=True)
+        add_qual_to(pq, d_q, 0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        pq.finish(s)
+        e1.record(st)
+        torch.cuda.synchronize()
+        if k >= args.warmup:
+            ms.append(e0.elapsed_time(e1))
+        if k + 1 < args.warmup + args.steps:
+            pq.close()
+    rec["finish_qsum_ms"] = round(sum(ms) / len(ms), 4)
+    rec["qsum_checksum"] = int(pq.qsums().astype(np.uint64).sum())
+    pq.close()
     walls = []
     for k in range(args.warmup + args.steps):
         t0 = time.perf_counter()
