@@ -597,6 +597,143 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
                   const msw_read_batch_t* batch, int both, const msw_seed_params_t* params, uint32_t sep,
                   msw_out_t* out, uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint64_t chunk_pairs);
 
+/* Pairs.
+ *
+ * Defined on integers, like "Candidates and mapping quality"
+ * (tests/pair_oracle.py restates it).  A read and its mate are placed
+ * together: the locus of each is chosen among its candidates so that the two
+ * lie as a sequenced fragment would, and a mate without a usable candidate is
+ * searched for where its partner says it should be.
+ *
+ * Layout.  A batch of n pairs is 2n read rows: row 2p is mate 1 and row 2p + 1
+ * mate 2 of pair p.  Every per-read call runs on the 2n rows unchanged.
+ *
+ * Candidates.  A mate has up to K candidates, K = 2 or 3.  Candidates 0 and 1
+ * are those of "Candidates and mapping quality", each scored on both strands;
+ * candidate 2 is the rescue candidate below.  A candidate carries its score s,
+ * strand t, win_pos, end_i, end_j and oriented row, as
+ * msw_align_reads_strands_device leaves them (s >= 0; an empty window scores
+ * 0).  It exists iff win_pos >= 0 and s > 0.  Each mate also has the
+ * pseudo-candidate "none": score 0, never proper.
+ *
+ * Unclipped span, from the scoring pass alone (L the read length; end_i is the
+ * 0-based row of the best cell in the oriented read and end_j its 0-based
+ * column in the window, as in msw_out_t):
+ *   right_u = win_pos + (end_j + 1) + (L - 1 - end_i)
+ *   left_u  = right_u - L = win_pos + end_j - end_i
+ * For a gap-free full-length alignment left_u is the genome coordinate of the
+ * oriented read's first base.  left_u may be negative.
+ *
+ * Proper pair.  Given one existing candidate per mate, f the strand-0 one and
+ * r the strand-1 one, the combination is proper iff the strands differ,
+ * left_u(f) <= left_u(r), right_u(f) <= right_u(r), and
+ * min_ins <= tlen <= max_ins with tlen = right_u(r) - left_u(f) and
+ * 1 <= min_ins <= max_ins <= 4095 (FR orientation only).
+ *
+ * Choice.  S(c1, c2) = s1[c1] + s2[c2] + (proper ? pair_bonus : 0),
+ * pair_bonus >= 0, over each mate's existing candidates and "none".  The
+ * chosen combination is the maximum of S; on ties the lexicographically
+ * smallest (c1, c2) wins, with 0 < 1 < 2 < none.  With pair_bonus = 0 and
+ * K = 2 each mate's result equals msw_mapq_select_device's, bit for bit.
+ *
+ * Per mate m: the winner's score, end cell, win_len, strand, win_pos and
+ * oriented row move into candidate 0's arrays as msw_mapq_select_device moves
+ * them.  cand[m] is 0, 1 or 2; when "none" was chosen cand[m] is 0, the score
+ * is written as 0 and candidate 0's other arrays stay.  sub_score[m] is the
+ * best score among the mate's other existing candidates, 0 without one.
+ *   mapq[m] = min(60, 120 * (S_best - S_alt_m) / (match * L_m)),
+ * floor division in 64-bit integers, S_alt_m the maximum of S over the
+ * combinations in which mate m does not use its chosen candidate ("none"
+ * included); 0 when the mate's chosen score is <= 0 or match * L_m == 0.  It is
+ * the same uncalibrated heuristic as the single-end one, now over pair scores.
+ *
+ * Per pair: flags u8, bit 0 = proper, bit 1 = mate 1 came from rescue, bit 2 =
+ * mate 2 came from rescue; tlen i32 = the chosen combination's tlen when both
+ * chosen candidates exist and their strands differ (clamped to +-(2^31 - 1)),
+ * otherwise 0.
+ *
+ * Rescue.  The choice runs over K = 2 first.  Mate m is to be rescued iff the
+ * chosen combination is not proper and its partner's chosen candidate a
+ * exists with s_a >= rescue_min_score.  Its window starts where a proper mate
+ * would lie:
+ *   t_a = 0: right_u(m) lies in [left_u(a) + min_ins, left_u(a) + max_ins], so
+ *            win_pos = left_u(a) + min_ins - L_m - slack;
+ *   t_a = 1: left_u(m) lies in [right_u(a) - max_ins, right_u(a) - min_ins], so
+ *            win_pos = right_u(a) - max_ins - slack;
+ * clamped to >= 0 (a start at or past the genome end is an empty window, so
+ * "none"); every other read gets -1.  The window length of a whole call is
+ * W_r = max_ins - min_ins + max_read_len + 2 * slack; W_r > 4096 is
+ * MSW_E_RANGE.  Candidate 2 is msw_align_reads_strands_device's result for the
+ * mate against that window: no orientation is forced, a wrong-strand winner is
+ * simply not proper.  The final choice runs over K = 3.
+ * rescue_min_score = 0 with slack = 0 means rescue is off.
+ *
+ * Insert sizes.  hist u32[4096], cleared by the caller and added to by each
+ * call: pair p adds 1 to hist[tlen] iff both chosen candidates exist, their
+ * strands differ, 0 < tlen < 4096 and both mates' mapq >= min_mapq.  (tlen is
+ * non-zero only under the first two conditions, so tlen and mapq decide.) */
+typedef struct {
+    uint32_t min_ins;           /* 1 <= min_ins <= max_ins <= 4095 */
+    uint32_t max_ins;
+    int32_t  pair_bonus;        /* >= 0, in score units */
+    int32_t  rescue_min_score;  /* >= 0 */
+    uint32_t slack;             /* <= 4096 */
+} msw_pair_params_t;
+/* min_ins 1, max_ins 1000, pair_bonus 17, rescue_min_score 60, slack 16. */
+void msw_pair_params_default(msw_pair_params_t* p);
+
+/* The device calls: every array is device memory, msw_cand_t as above with
+ * every member given, rows 2p / 2p + 1 the mates of pair p.  Enqueued on
+ * `stream` (NULL = the context's compute stream), no host synchronisation;
+ * n_pairs = 0 launches nothing.  A NULL array is MSW_E_INVALID; pair params
+ * outside the ranges above, match outside [0, 64] and n_pairs > 2^30 - 1 are
+ * MSW_E_RANGE.
+ *
+ * The K = 2 choice, then rescue_pos i64[2 n_pairs]: each mate's rescue window
+ * position, -1 where it is not to be rescued.  Reads cand[0..1]'s score, end_i,
+ * end_j, strand and win_pos; writes nothing else. */
+int msw_pair_plan_device(msw_ctx* ctx, const msw_cand_t* cand, const uint16_t* read_len, uint64_t n_pairs,
+                         const msw_pair_params_t* params, int64_t* rescue_pos, void* stream);
+
+/* The choice over cand[0..K), K = 2 or 3 (else MSW_E_INVALID), in place: the
+ * winners land in cand[0]'s arrays; where candidate 0 wins its arrays are not
+ * written, and a losing row is not read.  Rows as for msw_mapq_select_device
+ * (16-byte aligned slabs, oriented_stride a non-zero multiple of 16, else
+ * MSW_E_INVALID).  sub_score i32, mapq u8 and cand_out u8 are [2 n_pairs];
+ * pair_flags u8 and tlen i32 are [n_pairs]. */
+int msw_pair_select_device(msw_ctx* ctx, const msw_cand_t* cand, uint32_t K, uint32_t oriented_stride,
+                           const uint16_t* read_len, uint64_t n_pairs, int32_t match,
+                           const msw_pair_params_t* params, int32_t* sub_score, uint8_t* mapq, uint8_t* cand_out,
+                           uint8_t* pair_flags, int32_t* tlen, void* stream);
+
+/* hist[tlen[p]] += 1 by the rule above: tlen i32[n_pairs] and mapq
+ * u8[2 n_pairs] as msw_pair_select_device wrote them, hist device u32[4096].
+ * min_mapq > 255 is MSW_E_RANGE.  The result does not depend on the order of
+ * the adds. */
+int msw_insert_hist_device(msw_ctx* ctx, const int32_t* tlen, const uint8_t* mapq, uint64_t n_pairs,
+                           uint32_t min_mapq, uint32_t* hist, void* stream);
+
+/* Insert-size bounds of a host histogram u32[4096] of total N, in integers: q25, q50
+ * and q75 are the smallest bins whose cumulative count reaches ceil(N / 4),
+ * ceil(N / 2) and ceil(3 N / 4); *median = q50,
+ * *lo = max(1, q25 - 3 (q75 - q25)), *hi = min(4095, q75 + 3 (q75 - q25)).
+ * N = 0 is MSW_E_INVALID.  Host only. */
+int msw_insert_bounds(const uint32_t* hist, uint32_t* lo, uint32_t* hi, uint32_t* median);
+
+/* msw_map_reads with `both` for pairs: batch holds 2n rows (an odd row count
+ * is MSW_E_INVALID).  Host memory, synchronous, in chunks of `chunk_pairs`
+ * read pairs (0 = 32768).  Per chunk: the candidates and both scorings; unless
+ * rescue is off, the plan and the rescue scoring at window W_r; the select;
+ * the histogram when `hist` (host u32[4096], added to; min_mapq 0) is given;
+ * then the trace and the pack of the winners' rows at the winners' positions.
+ * out, strand, aln and mq are [2n] and filled as by msw_map_reads; pair_flags
+ * u8 and tlen i32 are [n].  Ranges as for msw_map_reads, plus W_r when rescue
+ * is on. */
+int msw_map_pairs(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_index* idx,
+                  const msw_read_batch_t* batch, const msw_seed_params_t* params, uint32_t sep,
+                  const msw_pair_params_t* pair_params, msw_out_t* out, uint8_t* strand, msw_aln_t* aln,
+                  const msw_mapq_t* mq, uint8_t* pair_flags, int32_t* tlen, uint32_t* hist, uint64_t chunk_pairs);
+
 /* Pileup: per genome base, what the reads aligned over it show.
  *
  * Everything is integers and bytes, so a plain restatement

@@ -41,6 +41,8 @@ EXPORTED = (
     "msw_call_params_default", "msw_pileup_call_device", "msw_pileup_call", "msw_call_counts",
     "msw_call_qparams_default", "msw_pileup_create_ex", "msw_pileup_qsums", "msw_pileup_qsums_device",
     "msw_pileup_call_qual_device", "msw_pileup_call_qual", "msw_call_counts_qual",
+    "msw_pair_params_default", "msw_pair_plan_device", "msw_pair_select_device", "msw_insert_hist_device",
+    "msw_insert_bounds", "msw_map_pairs",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -119,6 +121,11 @@ class CandT(ctypes.Structure):
 
 class MapqT(ctypes.Structure):
     _fields_ = [("mapq", ctypes.c_void_p), ("sub_score", ctypes.c_void_p), ("cand", ctypes.c_void_p)]
+
+
+class PairParamsT(ctypes.Structure):
+    _fields_ = [("min_ins", ctypes.c_uint32), ("max_ins", ctypes.c_uint32), ("pair_bonus", ctypes.c_int32),
+                ("rescue_min_score", ctypes.c_int32), ("slack", ctypes.c_uint32)]
 
 
 class PileupSummaryT(ctypes.Structure):
@@ -210,6 +217,17 @@ def _declare(L):
         "msw_map_reads": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.POINTER(ReadBatchT), I,
                               ctypes.POINTER(SeedParamsT), ctypes.c_uint32, ctypes.POINTER(OutT), P,
                               ctypes.POINTER(AlnT), ctypes.POINTER(MapqT), ctypes.c_uint64]),
+        "msw_pair_params_default": (None, [ctypes.POINTER(PairParamsT)]),
+        "msw_pair_plan_device": (I, [P, ctypes.POINTER(CandT), P, ctypes.c_uint64, ctypes.POINTER(PairParamsT), P, P]),
+        "msw_pair_select_device": (I, [P, ctypes.POINTER(CandT), ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64,
+                                       ctypes.c_int32, ctypes.POINTER(PairParamsT), P, P, P, P, P, P]),
+        "msw_insert_hist_device": (I, [P, P, P, ctypes.c_uint64, ctypes.c_uint32, P, P]),
+        "msw_insert_bounds": (I, [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                  ctypes.POINTER(ctypes.c_uint32)]),
+        "msw_map_pairs": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.POINTER(ReadBatchT),
+                              ctypes.POINTER(SeedParamsT), ctypes.c_uint32, ctypes.POINTER(PairParamsT),
+                              ctypes.POINTER(OutT), P, ctypes.POINTER(AlnT), ctypes.POINTER(MapqT), P, P, P,
+                              ctypes.c_uint64]),
         "msw_pileup_create": (I, [P, P, ctypes.POINTER(P)]),
         "msw_pileup_destroy": (None, [P]),
         "msw_pileup_add_device": (I, [P, P, P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(AlnT), P, P,

@@ -26,7 +26,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, MSW_PILEUP_QSUM, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PileupSummaryT,
+from ._lib import (MSW_E_INVALID, MSW_PILEUP_QSUM, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PairParamsT, PileupSummaryT,
                    ReadBatchT, ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
@@ -201,6 +201,41 @@ class QualParams:
             if not 0 <= int(getattr(self, k)) <= 0xFFFFFFFF:
                 raise MswError(MSW_E_INVALID, f"call qparams: {k} does not fit 32 bits")
         return CallQParamsT(int(self.q_scale), int(self.q_third))
+
+
+@dataclass(frozen=True)
+class PairParams:
+    """How read pairs are placed (msw_pair_params_t; the defaults are
+    msw_pair_params_default's): the insert-size bounds of a proper pair, the
+    score a proper combination gains, and the rescue of a mate in the window
+    its partner implies.  ``rescue_min_score = 0`` with ``slack = 0`` turns
+    rescue off."""
+    min_ins: int = 1
+    max_ins: int = 1000
+    pair_bonus: int = 17
+    rescue_min_score: int = 60
+    slack: int = 16
+
+    FIELDS = ("min_ins", "max_ins", "pair_bonus", "rescue_min_score", "slack")
+
+    def to_c(self) -> PairParamsT:
+        for k in self.FIELDS:
+            if not -0x80000000 <= int(getattr(self, k)) <= 0x7FFFFFFF:
+                raise MswError(MSW_E_INVALID, f"pair params: {k} does not fit 32 bits")
+        if self.min_ins < 0 or self.max_ins < 0 or self.slack < 0:
+            raise MswError(MSW_E_INVALID, "pair params: min_ins, max_ins and slack are unsigned")
+        return PairParamsT(*(int(getattr(self, k)) for k in self.FIELDS))
+
+
+def insert_bounds(hist):
+    """(lo, hi, median) of an insert-size histogram uint32[4096]
+    (msw_insert_bounds): the quartile rule of include/msw.h, "Pairs"."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.shape != (4096,):
+        raise MswError(MSW_E_INVALID, "hist must be uint32[4096]")
+    lo, hi, med = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().msw_insert_bounds(h.ctypes.data, ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(med)))
+    return int(lo.value), int(hi.value), int(med.value)
 
 
 class Variants(NamedTuple):
@@ -748,6 +783,106 @@ class Context:
                                            ctypes.c_void_p(read_len_ptr or None), n, match,
                                            ctypes.c_void_p(sub_score_ptr or None), ctypes.c_void_p(mapq_ptr or None),
                                            ctypes.c_void_p(cand_ptr or None), ctypes.c_void_p(stream or None)))
+
+    # -- pairs (include/msw.h, "Pairs") -------------------------------------------------
+    def map_pairs(self, genome: "Genome", index: "Index", reads: np.ndarray, read_len: np.ndarray,
+                  scoring: Scoring = LINEAR, pair_params: Optional[PairParams] = None, window: int = 0,
+                  band: int = 16, cap: int = 4096, step: int = 1, min_votes: int = 1, chunk_pairs: int = 0,
+                  sep: int = 0, hist: Optional[np.ndarray] = None):
+        """:meth:`map_reads` with ``mapq`` and both strands for read pairs
+        (msw_map_pairs): rows 2p and 2p + 1 of ``reads`` are the mates of pair
+        p.  Each mate's locus is chosen among its candidates together with
+        its partner's, a combination that lies as a proper pair gaining
+        ``pair_params.pair_bonus``, and a mate is searched for again in the
+        window its partner implies (rescue, ``cand`` 2).  Returns the ten
+        arrays of ``map_reads(mapq=True)`` for the 2n rows, then pair_flags
+        uint8[n] (bit 0 proper, bits 1 / 2: mate 1 / 2 came from rescue) and
+        tlen int32[n].  ``hist`` (uint32[4096], contiguous) is added to: the
+        insert sizes of the pairs on opposite strands, for
+        :func:`insert_bounds`.  ``chunk_pairs`` counts read pairs."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        B = reads.shape[0]
+        if read_len.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        if hist is not None and (hist.dtype != np.uint32 or hist.shape != (4096,) or not hist.flags.c_contiguous):
+            raise MswError(MSW_E_INVALID, "hist must be a contiguous uint32[4096]")
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0, None, None, B)
+        sc = _scoring_c(scoring)
+        sp = SeedParamsT(band, cap, step, min_votes, window)
+        pp = (pair_params or PairParams()).to_c()
+        strand = np.zeros(B, np.uint8)
+        mq, sub, cand = np.zeros(B, np.uint8), np.zeros(B, np.int32), np.zeros(B, np.uint8)
+        flags, tlen = np.zeros(B // 2, np.uint8), np.zeros(B // 2, np.int32)
+        ccap = 4 * B
+        if B == 0:  # nothing to call with: every array is empty
+            (score, ei, ej), _ = _outputs(0, True)
+            cigars = CigarList()
+            cigars.n_cigar = np.zeros(0, np.int32)
+            return score, ei, ej, strand, np.empty(0, np.int64), np.empty(0, np.int32), cigars, mq, sub, cand, flags, tlen
+        while True:
+            (score, ei, ej), out = _outputs(B, True)
+            ref_pos, nm = np.empty(B, np.int64), np.empty(B, np.int32)
+            off = np.zeros(B + 1, np.uint32)
+            cig = np.zeros(max(ccap, 1), np.uint32)
+            ovf = np.zeros(1, np.uint32)
+            aln = AlnT(_fresh_ptr(ref_pos), _fresh_ptr(nm), _fresh_ptr(off), _fresh_ptr(cig), ccap, _fresh_ptr(ovf))
+            mt = MapqT(_fresh_ptr(mq), _fresh_ptr(sub), _fresh_ptr(cand))
+            # the histogram is added to: only the pass whose ops fit may touch the caller's
+            h = np.zeros(4096, np.uint32) if hist is not None else None
+            check(lib().msw_map_pairs(self.handle, ctypes.byref(sc), genome.handle, index.handle, ctypes.byref(batch),
+                                      ctypes.byref(sp), sep, ctypes.byref(pp), ctypes.byref(out),
+                                      ctypes.c_void_p(_fresh_ptr(strand) or None), ctypes.byref(aln), ctypes.byref(mt),
+                                      ctypes.c_void_p(_fresh_ptr(flags) or None),
+                                      ctypes.c_void_p(_fresh_ptr(tlen) or None),
+                                      ctypes.c_void_p(_fresh_ptr(h) if h is not None else None), chunk_pairs))
+            total = int(off[B])
+            if total > ccap:
+                ccap = total  # once: the offsets do not depend on the capacity
+                continue
+            break
+        if h is not None:
+            hist += h
+        cigars = CigarList(cig[off[p]:off[p + 1]].copy() for p in range(B))
+        cigars.n_cigar = np.diff(off.astype(np.int64)).astype(np.int32)
+        return score, ei, ej, strand, ref_pos, nm, cigars, mq, sub, cand, flags, tlen
+
+    _CAND_KEYS = ("score", "end_i", "end_j", "win_len", "strand", "oriented", "win_pos")
+
+    def pair_plan_device(self, cands: Sequence[dict], read_len_ptr: int, n_pairs: int, params: PairParams,
+                         rescue_pos_ptr: int, stream: int = 0) -> None:
+        """Enqueue the rescue plan (msw_pair_plan_device): ``cands`` are the
+        two candidates' raw device pointers keyed as in
+        :meth:`mapq_select_device`, over 2 x ``n_pairs`` rows;
+        ``rescue_pos_ptr`` receives int64[2 n_pairs]."""
+        cs = (CandT * 2)(*[CandT(*[c.get(k) or None for k in self._CAND_KEYS]) for c in cands[:2]])
+        pp = params.to_c()
+        check(lib().msw_pair_plan_device(self.handle, cs, ctypes.c_void_p(read_len_ptr or None), n_pairs,
+                                         ctypes.byref(pp), ctypes.c_void_p(rescue_pos_ptr or None),
+                                         ctypes.c_void_p(stream or None)))
+
+    def pair_select_device(self, cands: Sequence[dict], read_len_ptr: int, n_pairs: int, match: int,
+                           params: PairParams, sub_score_ptr: int, mapq_ptr: int, cand_ptr: int, pair_flags_ptr: int,
+                           tlen_ptr: int, oriented_stride: int, stream: int = 0) -> None:
+        """Enqueue the choice among the candidate combinations of each pair
+        (msw_pair_select_device): ``cands`` holds two or three candidates; the
+        winners land in the first one's arrays."""
+        K = len(cands)
+        cs = (CandT * max(K, 1))(*[CandT(*[c.get(k) or None for k in self._CAND_KEYS]) for c in cands])
+        pp = params.to_c()
+        check(lib().msw_pair_select_device(self.handle, cs, K, oriented_stride, ctypes.c_void_p(read_len_ptr or None),
+                                           n_pairs, match, ctypes.byref(pp), ctypes.c_void_p(sub_score_ptr or None),
+                                           ctypes.c_void_p(mapq_ptr or None), ctypes.c_void_p(cand_ptr or None),
+                                           ctypes.c_void_p(pair_flags_ptr or None), ctypes.c_void_p(tlen_ptr or None),
+                                           ctypes.c_void_p(stream or None)))
+
+    def insert_hist_device(self, tlen_ptr: int, mapq_ptr: int, n_pairs: int, min_mapq: int, hist_ptr: int,
+                           stream: int = 0) -> None:
+        """Enqueue the insert-size histogram (msw_insert_hist_device):
+        device uint32[4096] at ``hist_ptr`` is added to."""
+        check(lib().msw_insert_hist_device(self.handle, ctypes.c_void_p(tlen_ptr or None),
+                                           ctypes.c_void_p(mapq_ptr or None), n_pairs, min_mapq,
+                                           ctypes.c_void_p(hist_ptr or None), ctypes.c_void_p(stream or None)))
 
     # -- HBM-resident batches ----------------------------------------------------------
     def align_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int,

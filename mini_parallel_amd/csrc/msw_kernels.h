@@ -495,6 +495,57 @@ struct MapqSelectParams {
 hipError_t launch_mapq_select(const MapqSelectParams& p, hipStream_t stream);
 int mapq_blocks_per_cu();
 
+// Pairs (msw_pair.hip; the contract is in include/msw.h, "Pairs").  Rows 2p and
+// 2p + 1 of every per-read array are the mates of pair p.
+struct PairCand {               // one candidate's scoring results over the 2n rows
+    int32_t* score;
+    int16_t* end_i;
+    int16_t* end_j;
+    uint16_t* win_len;          // select only
+    uint8_t* strand;
+    uint8_t* oriented;          // select only
+    int64_t* win_pos;
+};
+struct PairRule {
+    int32_t min_ins, max_ins, pair_bonus, rescue_min_score, slack;
+};
+// pair_plan_kernel: the K = 2 choice per pair, then rescue_pos[2n]: where each
+// mate's rescue window starts, -1 where the mate is not to be rescued.  Reads
+// the candidates only.
+struct PairPlanParams {
+    PairCand c[2];
+    const uint16_t* read_len;
+    uint64_t n_pairs;
+    PairRule rule;
+    int64_t* rescue_pos;
+};
+hipError_t launch_pair_plan(const PairPlanParams& p, hipStream_t stream);
+// pair_select_kernel: the choice over k = 2 or 3 candidates per mate; the
+// winner moves into c[0]'s arrays as mapq_select_kernel moves it (both slabs
+// 16-byte aligned, oriented_stride a non-zero multiple of 16, else
+// hipErrorInvalidValue and nothing launched).  sub_score / mapq / cand are per
+// row, pair_flags / tlen per pair.
+struct PairSelectParams {
+    PairCand c[3];
+    uint32_t k;
+    const uint16_t* read_len;
+    uint64_t oriented_stride;
+    uint64_t n_pairs;
+    int32_t match;
+    PairRule rule;
+    int32_t* sub_score;
+    uint8_t* mapq;
+    uint8_t* cand;
+    uint8_t* pair_flags;
+    int32_t* tlen;
+};
+hipError_t launch_pair_select(const PairSelectParams& p, hipStream_t stream);
+// insert_hist_kernel: hist[tlen[p]] += 1 for the pairs with 0 < tlen < 4096
+// whose two mapq are >= min_mapq; hist is u32[kInsertBins] and is added to.
+constexpr uint32_t kInsertBins = 4096;
+hipError_t launch_insert_hist(const int32_t* tlen, const uint8_t* mapq, uint64_t n_pairs, uint32_t min_mapq,
+                              uint32_t* hist, hipStream_t stream);
+
 // Both strands (msw_strand.hip; the contract is in include/msw.h).
 // out[p][0, read_len[p]) = the reverse complement of read row p, zeros up to
 // out_stride: every byte of every output row is written.  out 16-byte

@@ -3121,6 +3121,323 @@ int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
     return MSW_OK;
 }
 
+// Pairs (include/msw.h, "Pairs"; the kernels: msw_pair.hip).
+void msw_pair_params_default(msw_pair_params_t* p) {
+    if (!p) return;
+    *p = msw_pair_params_t{1u, 1000u, 17, 60, 16u};
+}
+
+static bool rescue_on(const msw_pair_params_t& q) { return q.rescue_min_score != 0 || q.slack != 0; }
+
+static int check_pair_params(const msw_pair_params_t* q, msw::PairRule* r) {
+    if (!q) return fail(MSW_E_INVALID, "pair params is NULL");
+    if (q->min_ins < 1 || q->min_ins > q->max_ins || q->max_ins > 4095)
+        return fail(MSW_E_RANGE, "pairs: insert bounds [%u, %u] outside 1 <= min <= max <= 4095", q->min_ins,
+                    q->max_ins);
+    if (q->pair_bonus < 0 || q->rescue_min_score < 0)
+        return fail(MSW_E_RANGE, "pairs: pair_bonus / rescue_min_score below 0");
+    if (q->slack > 4096) return fail(MSW_E_RANGE, "pairs: slack %u > 4096", q->slack);
+    *r = msw::PairRule{(int32_t)q->min_ins, (int32_t)q->max_ins, q->pair_bonus, q->rescue_min_score, (int32_t)q->slack};
+    return MSW_OK;
+}
+
+// W_r of the contract; 0 when rescue is off
+static int rescue_window(const msw_pair_params_t& q, uint32_t max_read_len, uint32_t* w) {
+    *w = 0;
+    if (!rescue_on(q)) return MSW_OK;
+    const uint64_t wr = (uint64_t)q.max_ins - q.min_ins + max_read_len + 2ull * q.slack;
+    if (wr > (uint64_t)msw::kMaxWinLen)
+        return fail(MSW_E_RANGE, "pairs: rescue window %llu > %d", (unsigned long long)wr, msw::kMaxWinLen);
+    *w = (uint32_t)wr;
+    return MSW_OK;
+}
+
+static msw::PairCand pair_cand(const msw_cand_t& c) {
+    return msw::PairCand{c.score, c.end_i, c.end_j, c.win_len, c.strand, c.oriented, c.win_pos};
+}
+
+int msw_pair_plan_device(msw_ctx* ctx, const msw_cand_t* cand, const uint16_t* read_len, uint64_t n_pairs,
+                         const msw_pair_params_t* params, int64_t* rescue_pos, void* stream) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    msw::PairPlanParams p;
+    int rc;
+    if ((rc = check_pair_params(params, &p.rule))) return rc;
+    if (n_pairs == 0) return MSW_OK;
+    if (!cand || !read_len || !rescue_pos) return fail(MSW_E_INVALID, "NULL array");
+    for (int k = 0; k < 2; ++k) {
+        if (!cand[k].score || !cand[k].end_i || !cand[k].end_j || !cand[k].strand || !cand[k].win_pos)
+            return fail(MSW_E_INVALID, "NULL array in candidate %d", k);
+        p.c[k] = pair_cand(cand[k]);
+    }
+    if (n_pairs > 0x3FFFFFFFull) return fail(MSW_E_RANGE, "pair plan: too many pairs in one call");
+    if ((rc = set_device(ctx))) return rc;
+    p.read_len = read_len;
+    p.n_pairs = n_pairs;
+    p.rescue_pos = rescue_pos;
+    HIP_TRY(msw::launch_pair_plan(p, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_pair_select_device(msw_ctx* ctx, const msw_cand_t* cand, uint32_t K, uint32_t oriented_stride,
+                           const uint16_t* read_len, uint64_t n_pairs, int32_t match,
+                           const msw_pair_params_t* params, int32_t* sub_score, uint8_t* mapq, uint8_t* cand_out,
+                           uint8_t* pair_flags, int32_t* tlen, void* stream) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    msw::PairSelectParams p;
+    memset(&p, 0, sizeof(p));
+    int rc;
+    if ((rc = check_pair_params(params, &p.rule))) return rc;
+    if (match < 0 || match > 64) return fail(MSW_E_RANGE, "pair select: match=%d outside [0, 64]", match);
+    if (K != 2 && K != 3) return fail(MSW_E_INVALID, "pair select: K=%u is neither 2 nor 3", K);
+    if (n_pairs == 0) return MSW_OK;
+    if (!cand || !read_len || !sub_score || !mapq || !cand_out || !pair_flags || !tlen)
+        return fail(MSW_E_INVALID, "NULL array");
+    for (uint32_t k = 0; k < K; ++k) {
+        const msw_cand_t& c = cand[k];
+        if (!c.score || !c.end_i || !c.end_j || !c.win_len || !c.strand || !c.oriented || !c.win_pos)
+            return fail(MSW_E_INVALID, "NULL array in candidate %u", k);
+        if (((uintptr_t)c.oriented & 15) != 0 || oriented_stride == 0 || oriented_stride % 16 != 0)
+            return fail(MSW_E_INVALID, "oriented must be 16-byte aligned and oriented_stride a non-zero multiple of 16");
+        p.c[k] = pair_cand(c);
+    }
+    if (n_pairs > 0x3FFFFFFFull) return fail(MSW_E_RANGE, "pair select: too many pairs in one call");
+    if ((rc = set_device(ctx))) return rc;
+    p.k = K;
+    p.read_len = read_len;
+    p.oriented_stride = oriented_stride;
+    p.n_pairs = n_pairs;
+    p.match = match;
+    p.sub_score = sub_score, p.mapq = mapq, p.cand = cand_out, p.pair_flags = pair_flags, p.tlen = tlen;
+    HIP_TRY(msw::launch_pair_select(p, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_insert_hist_device(msw_ctx* ctx, const int32_t* tlen, const uint8_t* mapq, uint64_t n_pairs,
+                           uint32_t min_mapq, uint32_t* hist, void* stream) {
+    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
+    if (min_mapq > 255) return fail(MSW_E_RANGE, "insert hist: min_mapq %u > 255", min_mapq);
+    if (n_pairs == 0) return MSW_OK;
+    if (!tlen || !mapq || !hist) return fail(MSW_E_INVALID, "NULL array");
+    if (n_pairs > 0x3FFFFFFFull) return fail(MSW_E_RANGE, "insert hist: too many pairs in one call");
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    HIP_TRY(msw::launch_insert_hist(tlen, mapq, n_pairs, min_mapq, hist, call_stream(ctx, stream)));
+    return MSW_OK;
+}
+
+int msw_insert_bounds(const uint32_t* hist, uint32_t* lo, uint32_t* hi, uint32_t* median) {
+    if (!hist || !lo || !hi || !median) return fail(MSW_E_INVALID, "NULL argument");
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < msw::kInsertBins; ++k) total += hist[k];
+    if (total == 0) return fail(MSW_E_INVALID, "insert bounds: the histogram is empty");
+    const uint64_t need[3] = {(total + 3) / 4, (total + 1) / 2, (3 * total + 3) / 4};
+    uint32_t q[3] = {0, 0, 0};
+    uint64_t cum = 0;
+    int at = 0;
+    for (uint32_t k = 0; k < msw::kInsertBins && at < 3; ++k) {
+        cum += hist[k];
+        while (at < 3 && cum >= need[at]) q[at++] = k;
+    }
+    const int64_t iqr = (int64_t)q[2] - q[0];
+    *lo = (uint32_t)std::max<int64_t>(1, (int64_t)q[0] - 3 * iqr);
+    *hi = (uint32_t)std::min<int64_t>(4095, (int64_t)q[2] + 3 * iqr);
+    *median = q[1];
+    return MSW_OK;
+}
+
+int msw_map_pairs(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_index* x,
+                  const msw_read_batch_t* b, const msw_seed_params_t* sp, uint32_t sep, const msw_pair_params_t* pp,
+                  msw_out_t* out, uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint8_t* pair_flags,
+                  int32_t* tlen, uint32_t* hist, uint64_t chunk_pairs) {
+    if (!ctx || !g || !x) return fail(MSW_E_INVALID, "ctx/genome/index is NULL");
+    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
+    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
+    if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
+    msw_scoring_t scc = *sc;
+    scc.want_coords = 1;
+    Scheme sch;
+    int rc;
+    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
+    if ((rc = validate_aln(aln))) return rc;
+    const uint64_t n = b->n_pairs;  // rows
+    if (n & 1) return fail(MSW_E_INVALID, "pairs: %llu rows is an odd number", (unsigned long long)n);
+    uint32_t max_m = 0;
+    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array in batch");
+    max_u16(b->read_len, n, max_m);
+    if ((rc = check_seed_params(sp, max_m))) return rc;
+    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
+    msw::PairRule rule;
+    uint32_t wr = 0;
+    if ((rc = check_pair_params(pp, &rule)) || (rc = rescue_window(*pp, max_m, &wr))) return rc;
+    const bool rescue = wr != 0;
+    *aln->n_overflow = 0;
+    aln->cigar_off[0] = 0;
+    if (n == 0) return MSW_OK;
+    if (!b->reads) return fail(MSW_E_INVALID, "NULL array in batch");
+    if (!strand) return fail(MSW_E_INVALID, "strand is NULL");
+    if (!out || !out->score || !out->end_i || !out->end_j)
+        return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
+    if (!mq || !mq->mapq || !mq->sub_score || !mq->cand) return fail(MSW_E_INVALID, "NULL array in mapq");
+    if (!pair_flags || !tlen) return fail(MSW_E_INVALID, "pair_flags / tlen is NULL");
+    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
+    const uint32_t window = sp->window;
+    const uint32_t max_n = window ? window : std::min<uint32_t>(2u * max_m, (uint32_t)msw::kMaxWinLen);
+    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
+    if ((rc = set_device(ctx))) return rc;
+    // The trace reads a window only up to the best cell's column, so its
+    // window argument is a bound and one call serves both window lengths: with
+    // rescue it is the larger of the two, without it what msw_map_reads passes.
+    const uint32_t trace_window = rescue ? std::max(max_n, wr) : window;
+    const uint32_t trace_n = rescue ? trace_window : max_n;
+    // msw_map_reads with `both`, on whole pairs, with the plan and the rescue
+    // scoring between the two candidate scorings and the select.
+    const uint64_t chunk = std::min<uint64_t>(n, 2 * (chunk_pairs ? chunk_pairs : 32768));
+    const size_t rs = b->read_stride, ors = round16(std::max<uint32_t>(max_m, 1)), cs = (size_t)max_m + trace_n;
+    size_t total_bytes = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = total_bytes;
+        total_bytes = (at + bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_reads = take(chunk * rs), o_rc = take(chunk * ors), o_rows = take(chunk * cs * 4),
+                 o_ref = take(chunk * 8), o_sub = take(chunk * 4), o_nc = take(chunk * 4), o_nm = take(chunk * 4),
+                 o_votes = take(chunk * 4), o_hits = take(chunk * 4), o_votes1 = take(chunk * 4),
+                 o_off = take((chunk + 2) * 4), o_rl = take(chunk * 2), o_si = take(chunk * 2), o_sj = take(chunk * 2),
+                 o_fl = take(chunk), o_fl1 = take(chunk), o_mapq = take(chunk), o_cand = take(chunk),
+                 o_pf = take(chunk / 2), o_tlen = take(chunk / 2 * 4), o_hist = take(msw::kInsertBins * 4);
+    struct CandAt {
+        size_t wp, s, ei, ej, wl, st, rows;
+    } ca[3];
+    for (int k = 0; k < (rescue ? 3 : 2); ++k)
+        ca[k] = CandAt{take(chunk * 8), take(chunk * 4), take(chunk * 2), take(chunk * 2),
+                       take(chunk * 2), take(chunk),     take(chunk * ors)};
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total_bytes);
+    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
+    uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
+    uint64_t ops_cap = chunk * 8;
+    e = hipMalloc((void**)&d_ops, ops_cap * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
+    }
+    msw_cand_t cand[3];
+    msw_out_t co[3];
+    for (int k = 0; k < (rescue ? 3 : 2); ++k) {
+        cand[k] = msw_cand_t{reinterpret_cast<int32_t*>(d + ca[k].s),   reinterpret_cast<int16_t*>(d + ca[k].ei),
+                             reinterpret_cast<int16_t*>(d + ca[k].ej),  reinterpret_cast<uint16_t*>(d + ca[k].wl),
+                             d + ca[k].st,                              d + ca[k].rows,
+                             reinterpret_cast<int64_t*>(d + ca[k].wp)};
+        co[k] = msw_out_t{cand[k].score, cand[k].end_i, cand[k].end_j};
+    }
+    uint8_t *d_reads = d + o_reads, *d_rc = d + o_rc, *d_fl = d + o_fl, *d_fl1 = d + o_fl1, *d_mapq = d + o_mapq,
+            *d_cand = d + o_cand, *d_pf = d + o_pf;
+    int64_t* d_ref = reinterpret_cast<int64_t*>(d + o_ref);
+    int32_t *d_sub = reinterpret_cast<int32_t*>(d + o_sub), *d_nc = reinterpret_cast<int32_t*>(d + o_nc),
+            *d_nm = reinterpret_cast<int32_t*>(d + o_nm), *d_tlen = reinterpret_cast<int32_t*>(d + o_tlen);
+    uint32_t *d_votes = reinterpret_cast<uint32_t*>(d + o_votes), *d_hits = reinterpret_cast<uint32_t*>(d + o_hits),
+             *d_votes1 = reinterpret_cast<uint32_t*>(d + o_votes1), *d_off = reinterpret_cast<uint32_t*>(d + o_off),
+             *d_hist = reinterpret_cast<uint32_t*>(d + o_hist);
+    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_rl);
+    int16_t *d_si = reinterpret_cast<int16_t*>(d + o_si), *d_sj = reinterpret_cast<int16_t*>(d + o_sj);
+    hipStream_t st = ctx->compute;
+    std::vector<uint32_t> off(chunk + 1);
+    uint64_t base = 0;  // ops of the chunks before this one
+    rc = MSW_OK;
+    if (hist) e = hipMemsetAsync(d_hist, 0, msw::kInsertBins * 4, st);
+    for (uint64_t lo = 0; lo < n && rc == MSW_OK && e == hipSuccess; lo += chunk) {
+        const uint64_t c = std::min(chunk, n - lo);
+        auto up = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+        };
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+        };
+        up(d_reads, b->reads + lo * rs, c * rs);
+        up(d_rl, b->read_len + lo, c * 2);
+        if (e != hipSuccess) break;
+        if ((rc = msw_revcomp_device(ctx, d_reads, d_rl, (uint32_t)rs, c, d_rc, (uint32_t)ors, st))) break;
+        const msw_seed_out_t so = {cand[0].win_pos, d_votes, d_hits, d_fl};
+        const msw_seed_alt_t sa = {cand[1].win_pos, d_votes1, d_fl1};
+        if ((rc = msw_seed_candidates_device(ctx, x, d_reads, d_rc, d_rl, (uint32_t)rs, (uint32_t)ors, c, max_m, sp,
+                                             sep, &so, &sa, st)))
+            break;
+        for (int k = 0; k < 2 && rc == MSW_OK; ++k)
+            rc = msw_align_reads_strands_device(ctx, &scc, g, d_reads, d_rl, (uint32_t)rs, cand[k].win_pos, c, window,
+                                                max_m, &co[k], cand[k].win_len, cand[k].strand, cand[k].oriented,
+                                                (uint32_t)ors, st);
+        if (rc) break;
+        if (rescue) {
+            // every row is scored at W_r; a row that is not to be rescued is an empty window
+            if ((rc = msw_pair_plan_device(ctx, cand, d_rl, c / 2, pp, cand[2].win_pos, st)) ||
+                (rc = msw_align_reads_strands_device(ctx, &scc, g, d_reads, d_rl, (uint32_t)rs, cand[2].win_pos, c, wr,
+                                                     max_m, &co[2], cand[2].win_len, cand[2].strand, cand[2].oriented,
+                                                     (uint32_t)ors, st)))
+                break;
+        }
+        if ((rc = msw_pair_select_device(ctx, cand, rescue ? 3u : 2u, (uint32_t)ors, d_rl, c / 2, scc.match, pp, d_sub,
+                                         d_mapq, d_cand, d_pf, d_tlen, st)))
+            break;
+        if (hist && (rc = msw_insert_hist_device(ctx, d_tlen, d_mapq, c / 2, 0u, d_hist, st))) break;
+        // from here on the reads are the winners' oriented rows, in candidate 0's arrays
+        const uint8_t* rows = cand[0].oriented;
+        const int64_t* d_wp = cand[0].win_pos;
+        msw_trace_t dtr = {d_si, d_sj, d_nc, reinterpret_cast<uint32_t*>(d + o_rows), (uint32_t)cs};
+        if ((rc = msw_trace_reads_device(ctx, &scc, g, rows, d_rl, (uint32_t)ors, d_wp, c, trace_window, max_m, &co[0],
+                                         &dtr, st)))
+            break;
+        uint64_t total = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            msw_aln_t da = {d_ref, d_nm, d_off, d_ops, ops_cap, d_off + c + 1};
+            if ((rc = msw_aln_pack_device(ctx, g, rows, d_rl, (uint32_t)ors, d_wp, c, &co[0], &dtr, &da, st))) break;
+            down(off.data(), d_off, (c + 1) * 4);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) break;
+            total = off[c];
+            if (total <= ops_cap) break;
+            (void)hipFree(d_ops);
+            d_ops = nullptr;
+            ops_cap = total;
+            if (hipMalloc((void**)&d_ops, ops_cap * 4) != hipSuccess) {
+                d_ops = nullptr;
+                rc = fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the packed ops", (unsigned long long)ops_cap * 4);
+                break;
+            }
+        }
+        if (rc || e != hipSuccess) break;
+        down(out->score + lo, cand[0].score, c * 4);
+        down(out->end_i + lo, cand[0].end_i, c * 2);
+        down(out->end_j + lo, cand[0].end_j, c * 2);
+        down(strand + lo, cand[0].strand, c);
+        down(mq->mapq + lo, d_mapq, c);
+        down(mq->sub_score + lo, d_sub, c * 4);
+        down(mq->cand + lo, d_cand, c);
+        down(pair_flags + lo / 2, d_pf, c / 2);
+        down(tlen + lo / 2, d_tlen, c / 2 * 4);
+        down(aln->ref_pos + lo, d_ref, c * 8);
+        down(aln->nm + lo, d_nm, c * 4);
+        const uint64_t room = aln->cigar_cap > base ? aln->cigar_cap - base : 0;
+        down(aln->cigar + base, d_ops, std::min(total, room) * 4);
+        for (uint64_t k = 0; k <= c; ++k) aln->cigar_off[lo + k] = (uint32_t)(base + off[k]);
+        base += total;
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (hist && rc == MSW_OK && e == hipSuccess) {
+        std::vector<uint32_t> h(msw::kInsertBins);
+        e = hipMemcpyAsync(h.data(), d_hist, msw::kInsertBins * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess)
+            for (uint32_t k = 0; k < msw::kInsertBins; ++k) hist[k] += h[k];
+    }
+    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (d_ops) (void)hipFree(d_ops);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "map pairs: %s", hipGetErrorString(e));
+    return MSW_OK;
+}
+
 // Pileup (include/msw.h, "Pileup"; the kernels: msw_pileup.hip).
 struct msw_pileup {
     const msw_ctx* ctx = nullptr;  // identity only
