@@ -165,9 +165,9 @@ int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
  *    pair: start (-1, -1) and 0 ops.  The first and last ops are M, adjacent
  *    ops differ, every length is >= 1.
  *
- * Range: traceback supports the packed kernels' range only, read <= 384 and
- * window <= 4096; a longer pair (or bound) in a traceback call returns
- * MSW_E_RANGE (scoring such pairs stays available through the calls above).
+ * Range: these traceback calls support the packed kernels' range only, read
+ * <= 384 and window <= 4096; a longer pair (or bound) returns MSW_E_RANGE.
+ * The *_long calls below trace pairs up to 32,767 x 32,767.
  *
  * Overflow: when a pair needs more than cigar_stride ops, n_cigar[p] still
  * holds the count it needs, its cigar row is unspecified (nothing is written
@@ -193,6 +193,29 @@ int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
  * out->end_i and out->end_j are required. */
 int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch, msw_out_t* out,
                           msw_trace_t* tr, uint64_t chunk_pairs);
+
+/* Traceback for long pairs: the two calls above with bounds up to 32,767 x
+ * 32,767 (the range of scoring), same arguments, same canonical alignment,
+ * same outputs and overflow rule.  While the bounds are inside the packed
+ * range (read <= 384, window <= 4096) and MSW_FORCE_LONG is unset they ARE the
+ * calls above; past it the whole call runs on a strip-checkpointed kernel
+ * (the way msw_align_batch_device routes scoring): strips of 384 rows, one
+ * score-only pass that keeps each strip's bottom row, then one strip at a
+ * time refilled with direction codes and walked, so no [rows][cols] direction
+ * array exists.  A pair needs up to rows + columns ops: size cigar_stride by
+ * the bounds you pass (an overflowing pair keeps its count, as above).
+ * Global scratch, stream-ordered on the call's stream and freed by it: per
+ * block (strips - 1) checkpoint rows of (window bound rounded up to 64) + 128
+ * i32 (x2 affine), a strip slab of 384 x ceil(window bound / 16 or 8) words
+ * and, past 4096 ops, the reverse op buffer; at the worst bounds (32,767 x
+ * 32,767, affine) 22.4 + 6.3 + 0.3 = 28.9 MB per block.  The grid is capped
+ * by what the CUs hold and by 256 MiB of scratch (9 blocks at the worst
+ * bounds), blocks taking pairs from a queue. */
+int msw_trace_long_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch,
+                                const msw_out_t* ends, msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len,
+                                void* stream);
+int msw_align_batch_trace_long(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch, msw_out_t* out,
+                               msw_trace_t* tr, uint64_t chunk_pairs);
 
 /* Length-bucketed plan for a device-resident batch of mixed lengths (BASELINE
  * config 5).  Built on the host from host copies of the length arrays (the
@@ -301,6 +324,14 @@ int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
                            const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
                            uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
                            void* stream);
+/* The same for long pairs (see msw_trace_long_batch_device): max_read_len up
+ * to 32,767; `window` = 0 stays 2 x read_len capped at 4096, an explicit
+ * window may go to 32,767.  `ends` comes from msw_align_reads_device with the
+ * same arguments (it scores such bounds on the long-pair kernel). */
+int msw_trace_reads_long_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                                const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                                uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
+                                void* stream);
 
 /* Alignment records: what a consumer of alignments needs beside the trace,
  * and the CIGARs packed into one stream instead of [n][cigar_stride] rows.
@@ -338,6 +369,14 @@ int msw_aln_pack_device(msw_ctx* ctx, const msw_genome* g, const uint8_t* reads,
  * `cigar` is then unspecified.  Reads <= 384, requested windows <= 4096. */
 int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* batch,
                           msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs);
+/* The same for long pairs: reads and requested windows up to 32,767, scored
+ * on whichever scoring kernel the bounds select, traced by
+ * msw_trace_long_batch_device and packed by msw_aln_pack_device (which has no
+ * length limit of its own: an op holds 28 bits of length).  Past the packed
+ * range a chunk is also capped so that its trace rows (read bound + window
+ * bound ops per read) stay within 1 GiB of device memory. */
+int msw_align_reads_trace_long(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                               const msw_read_batch_t* batch, msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs);
 
 /* Both strands.
  *

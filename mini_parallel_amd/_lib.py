@@ -43,6 +43,8 @@ EXPORTED = (
     "msw_pileup_call_qual_device", "msw_pileup_call_qual", "msw_call_counts_qual",
     "msw_pair_params_default", "msw_pair_plan_device", "msw_pair_select_device", "msw_insert_hist_device",
     "msw_insert_bounds", "msw_map_pairs",
+    "msw_trace_long_batch_device", "msw_align_batch_trace_long", "msw_trace_reads_long_device",
+    "msw_align_reads_trace_long",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -317,6 +319,12 @@ def _declare(L):
         "msw_gfastq_prefetch": (I, [P, ctypes.c_char_p]),
         "msw_bgzf_inflate": (I, [P, P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     }
+    # the long-pair traceback calls take the argument lists of the calls they extend
+    for name, base in (("msw_trace_long_batch_device", "msw_trace_batch_device"),
+                       ("msw_align_batch_trace_long", "msw_align_batch_trace"),
+                       ("msw_trace_reads_long_device", "msw_trace_reads_device"),
+                       ("msw_align_reads_trace_long", "msw_align_reads_trace")):
+        sigs[name] = sigs[base]
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
         fn.restype = res

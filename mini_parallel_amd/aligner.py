@@ -325,7 +325,7 @@ class Context:
     # -- full alignments: traceback ----------------------------------------------------
     def align_batch_trace(self, reads: np.ndarray, read_len: np.ndarray, wins: np.ndarray,
                           win_len: np.ndarray, scoring: Scoring = LINEAR,
-                          cigar_stride: Optional[int] = None, chunk_pairs: int = 0):
+                          cigar_stride: Optional[int] = None, chunk_pairs: int = 0, long_pairs: bool = False):
         """Score a padded SoA batch and trace every pair's canonical alignment
         (msw_align_batch_trace; include/msw.h states the rule).  Returns
         (score int32[B], end_i, end_j, start_i, start_j int16[B], ops): ops[p]
@@ -335,7 +335,10 @@ class Context:
         is repeated once with the largest count if a pair overflowed; with a
         given stride an overflowing pair's ops are None.  ``ops.n_cigar``
         holds every pair's op count either way.  Reads over 384 or windows
-        over 4096 bases raise :class:`MswError` (MSW_E_RANGE)."""
+        over 4096 bases raise :class:`MswError` (MSW_E_RANGE) unless
+        ``long_pairs`` is set: then the call is msw_align_batch_trace_long,
+        which traces pairs up to 32,767 x 32,767 on the strip-checkpointed
+        kernel and is the same call inside the packed range."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         wins = np.ascontiguousarray(wins, dtype=np.uint8)
         read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
@@ -347,6 +350,7 @@ class Context:
                        reads.shape[1] if reads.ndim == 2 else 0,
                        wins.shape[1] if wins.ndim == 2 else 0, B)
         sc = _scoring_c(scoring)
+        call = lib().msw_align_batch_trace_long if long_pairs else lib().msw_align_batch_trace
         stride = 32 if cigar_stride is None else int(cigar_stride)
         while True:
             (score, ei, ej), out = _outputs(B, True)
@@ -354,8 +358,8 @@ class Context:
             nc = np.zeros(B, np.int32)
             cig = np.zeros((B, stride), np.uint32)
             tr = TraceT(_fresh_ptr(si), _fresh_ptr(sj), _fresh_ptr(nc), _fresh_ptr(cig), stride)
-            check(lib().msw_align_batch_trace(self.handle, ctypes.byref(sc), ctypes.byref(batch),
-                                              ctypes.byref(out), ctypes.byref(tr), chunk_pairs))
+            check(call(self.handle, ctypes.byref(sc), ctypes.byref(batch), ctypes.byref(out), ctypes.byref(tr),
+                       chunk_pairs))
             need = int(nc.max()) if B else 0
             if cigar_stride is None and need > stride:
                 stride = need  # once: the counts do not depend on the stride
@@ -369,18 +373,20 @@ class Context:
                            read_stride: int, win_stride: int, n_pairs: int, score_ptr: int,
                            end_i_ptr: int, end_j_ptr: int, start_i_ptr: int, start_j_ptr: int,
                            n_cigar_ptr: int, cigar_ptr: int, cigar_stride: int, max_read_len: int,
-                           max_win_len: int, scoring: Scoring = LINEAR, stream: int = 0) -> None:
+                           max_win_len: int, scoring: Scoring = LINEAR, stream: int = 0,
+                           long_pairs: bool = False) -> None:
         """Enqueue one traceback pass over device-resident arrays (raw device
         pointers) on ``stream``: score / end_i / end_j are the outputs of
         :meth:`align_batch_device` with coordinates for the same batch and
-        scheme (msw_trace_batch_device)."""
+        scheme (msw_trace_batch_device; with ``long_pairs``
+        msw_trace_long_batch_device, bounds up to 32,767)."""
         batch = BatchT(reads_ptr, wins_ptr, read_len_ptr, win_len_ptr, read_stride, win_stride, n_pairs)
         ends = OutT(score_ptr, end_i_ptr, end_j_ptr)
         tr = TraceT(start_i_ptr, start_j_ptr, n_cigar_ptr, cigar_ptr, cigar_stride)
         sc = _scoring_c(scoring)
-        check(lib().msw_trace_batch_device(self.handle, ctypes.byref(sc), ctypes.byref(batch),
-                                           ctypes.byref(ends), ctypes.byref(tr), max_read_len, max_win_len,
-                                           ctypes.c_void_p(stream or None)))
+        call = lib().msw_trace_long_batch_device if long_pairs else lib().msw_trace_batch_device
+        check(call(self.handle, ctypes.byref(sc), ctypes.byref(batch), ctypes.byref(ends), ctypes.byref(tr),
+                   max_read_len, max_win_len, ctypes.c_void_p(stream or None)))
 
     # -- reads against an HBM-resident genome ------------------------------------------
     def load_genome(self, seq) -> "Genome":
@@ -419,7 +425,7 @@ class Context:
     # -- alignment records: reads against the genome, traced and packed ----------------
     def align_reads_trace(self, genome: "Genome", reads: np.ndarray, read_len: np.ndarray,
                           win_pos: np.ndarray, win_len: np.ndarray, scoring: Scoring = LINEAR,
-                          chunk_pairs: int = 0, cigar_cap: Optional[int] = None):
+                          chunk_pairs: int = 0, cigar_cap: Optional[int] = None, long_pairs: bool = False):
         """Score read p against genome[win_pos[p] : win_pos[p] + win_len[p]]
         like :meth:`align_reads` and trace it (msw_align_reads_trace).  Returns
         (score, end_i, end_j, ref_pos int64[B], nm int32[B], cigars):
@@ -428,7 +434,9 @@ class Context:
         array of BAM-encoded ops with soft clips (S = 4), so that it consumes
         the whole read; ``cigars.n_cigar`` holds the op counts.  ``cigar_cap``
         is the first guess at the total number of ops (default 4 per read);
-        when it is too small the call is repeated once with the exact size."""
+        when it is too small the call is repeated once with the exact size.
+        ``long_pairs`` lifts the range (reads <= 384, windows <= 4096) to
+        32,767 each (msw_align_reads_trace_long)."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
         win_pos = np.ascontiguousarray(win_pos, dtype=np.int64)
@@ -439,6 +447,7 @@ class Context:
         batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0,
                            _ptr(win_pos), _ptr(win_len), B)
         sc = _scoring_c(scoring)
+        call = lib().msw_align_reads_trace_long if long_pairs else lib().msw_align_reads_trace
         cap = 4 * B if cigar_cap is None else int(cigar_cap)
         while True:
             (score, ei, ej), out = _outputs(B, True)
@@ -447,8 +456,8 @@ class Context:
             cig = np.zeros(max(cap, 1), np.uint32)
             ovf = np.zeros(1, np.uint32)
             aln = AlnT(_fresh_ptr(ref_pos), _fresh_ptr(nm), _fresh_ptr(off), _fresh_ptr(cig), cap, _fresh_ptr(ovf))
-            check(lib().msw_align_reads_trace(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch),
-                                              ctypes.byref(out), ctypes.byref(aln), chunk_pairs))
+            check(call(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch), ctypes.byref(out),
+                       ctypes.byref(aln), chunk_pairs))
             total = int(off[B])
             if total > cap:
                 cap = total  # once: the offsets do not depend on the capacity
@@ -462,18 +471,19 @@ class Context:
                            win_pos_ptr: int, n: int, window: int, max_read_len: int, score_ptr: int,
                            end_i_ptr: int, end_j_ptr: int, start_i_ptr: int, start_j_ptr: int,
                            n_cigar_ptr: int, cigar_ptr: int, cigar_stride: int, scoring: Scoring = LINEAR,
-                           stream: int = 0) -> None:
+                           stream: int = 0, long_pairs: bool = False) -> None:
         """Enqueue one traceback pass over device-resident reads against
         windows read straight from the genome (msw_trace_reads_device): the
         arguments of msw_align_reads_device, whose outputs with coordinates
-        are score / end_i / end_j."""
+        are score / end_i / end_j.  With ``long_pairs``
+        msw_trace_reads_long_device: reads and explicit windows up to 32,767."""
         ends = OutT(score_ptr, end_i_ptr, end_j_ptr)
         tr = TraceT(start_i_ptr, start_j_ptr, n_cigar_ptr, cigar_ptr, cigar_stride)
         sc = _scoring_c(scoring)
-        check(lib().msw_trace_reads_device(self.handle, ctypes.byref(sc), genome.handle, ctypes.c_void_p(reads_ptr),
-                                           ctypes.c_void_p(read_len_ptr), read_stride, ctypes.c_void_p(win_pos_ptr),
-                                           n, window, max_read_len, ctypes.byref(ends), ctypes.byref(tr),
-                                           ctypes.c_void_p(stream or None)))
+        call = lib().msw_trace_reads_long_device if long_pairs else lib().msw_trace_reads_device
+        check(call(self.handle, ctypes.byref(sc), genome.handle, ctypes.c_void_p(reads_ptr),
+                   ctypes.c_void_p(read_len_ptr), read_stride, ctypes.c_void_p(win_pos_ptr), n, window, max_read_len,
+                   ctypes.byref(ends), ctypes.byref(tr), ctypes.c_void_p(stream or None)))
 
     def aln_pack_device(self, genome: "Genome", reads_ptr: int, read_len_ptr: int, read_stride: int,
                         win_pos_ptr: int, n: int, score_ptr: int, end_i_ptr: int, end_j_ptr: int,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "msw.h"  // msw_call_params_t, msw_variant_t (Variants)
+#include "msw_trace_sizes.h"
 
 namespace msw {
 
@@ -277,6 +278,25 @@ __host__ __device__ inline uint64_t trace_words(bool affine, uint32_t rows, uint
 size_t trace_lds_layout(TraceParams& p, bool affine);
 int trace_blocks_per_cu(bool affine, uint32_t max_read_len, size_t lds_bytes);
 hipError_t launch_sw_trace(const TraceParams& p, bool affine, uint32_t blocks, size_t lds_bytes, hipStream_t stream);
+
+// Traceback past the packed range (sw_trace_long_kernel, msw_trace_long.hip):
+// strips of 64 R rows; a score-only forward pass keeps every strip's bottom
+// row (the checkpoints), a backward pass refills one strip at a time with
+// direction codes and walks it.  `t` holds the call as for sw_trace_kernel
+// (slab / slab_words / lds_words are not read); the rest is the block's
+// scratch, laid out by trace_long_layout (msw_trace_sizes.h).
+struct TraceLongParams {
+    TraceParams t;
+    uint8_t* scratch;         // [blocks][block_bytes]: checkpoint rows | strip slab | reverse ops
+    uint64_t block_bytes;
+    uint64_t slab_off, ops_off;
+    uint32_t ckpt_cols;       // i32 per checkpoint row (affine: H row then F row)
+    uint32_t slab_w;          // direction words a slab row can hold
+    uint32_t ops_in_lds;
+};
+int trace_long_blocks_per_cu(bool affine, uint32_t max_read_len, size_t lds_bytes);
+hipError_t launch_sw_trace_long(const TraceLongParams& p, bool affine, uint32_t blocks, size_t lds_bytes,
+                                hipStream_t stream);
 
 // Alignment records (msw_aln.hip, msw_aln_pack_device): per read the genome
 // coordinate, the edit distance and the soft-clipped op count; an exclusive

@@ -1777,13 +1777,17 @@ int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     return launch_packed(ctx, sch, p, (uint32_t)b->n_pairs, max_read_len, max_win_len, st);
 }
 
-// Traceback supports the packed kernels' range only.
+// Traceback on sw_trace_kernel supports the packed kernels' range only; the
+// *_long calls take bounds up to kMaxLongLen (check_bounds).
 static int check_trace_bounds(uint32_t max_m, uint32_t max_n) {
     if (max_m > (uint32_t)msw::kMaxReadLen)
         return fail(MSW_E_RANGE, "traceback: read length %u > %d", max_m, msw::kMaxReadLen);
     if (max_n > (uint32_t)msw::kMaxWinLen)
         return fail(MSW_E_RANGE, "traceback: window length %u > %d", max_n, msw::kMaxWinLen);
     return MSW_OK;
+}
+static int check_trace_bounds(const Scheme& sch, uint32_t max_m, uint32_t max_n, bool long_pairs) {
+    return long_pairs ? check_bounds(sch, max_m, max_n) : check_trace_bounds(max_m, max_n);
 }
 
 static int validate_trace(const msw_trace_t* tr) {
@@ -1793,11 +1797,11 @@ static int validate_trace(const msw_trace_t* tr) {
     return MSW_OK;
 }
 
-// The launch both traceback entry points share: LDS layout, LDS / slab switch,
-// grid cap and work queue.  p holds the call's inputs and outputs (windows
-// from a slab or from the genome); the bounds and scoring are filled here.
-static int run_trace(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, msw::TraceParams p, uint64_t n_pairs,
-                     uint32_t max_read_len, uint32_t max_win_len, hipStream_t st) {
+// What both traceback kernels' launches share.  p holds the call's inputs and
+// outputs (windows from a slab or from the genome); this fills the bounds and
+// the scoring.
+static void trace_call_params(msw::TraceParams& p, const msw_scoring_t* sc, uint64_t n_pairs, uint32_t max_read_len,
+                              uint32_t max_win_len) {
     p.n_slots = (uint32_t)n_pairs;
     p.max_rows = max_read_len;
     p.max_cols = max_win_len;
@@ -1805,44 +1809,100 @@ static int run_trace(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, m
     p.mismatch = sc->mismatch;
     p.gap = sc->gap_extend;
     p.goe = sc->gap_open + sc->gap_extend;
-    const size_t shm = msw::trace_lds_layout(p, sch.affine);
-    // One block per pair while the direction words fit LDS.  A bound whose
-    // rectangle does not fit needs a global slab per block: the grid is then
-    // capped (what the CUs hold at once, and 256 MiB of slabs) and finished
-    // blocks take the next pair from a queue.  Slab and counter are allocated
-    // stream-ordered on `st`, like the long-pair launch's scratch.
-    const uint64_t need = msw::trace_words(sch.affine, max_read_len, max_win_len);
-    const bool slab = need > p.lds_words;
-    const uint64_t slab_bytes = slab ? need * sizeof(uint32_t) : 0;
-    uint64_t blocks = n_pairs;
-    if (slab) {
-        const int per_cu = msw::trace_blocks_per_cu(sch.affine, max_read_len, shm);
-        if (per_cu <= 0) return fail(MSW_E_DEVICE, "traceback kernel does not fit a CU");
-        const uint64_t resident = (uint64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (uint64_t)per_cu;
-        blocks = std::min(blocks, std::min(resident, std::max<uint64_t>(1, (256ull << 20) / slab_bytes)));
+}
+
+// The grid and its global scratch: one block per pair while a block needs no
+// scratch (block_bytes == 0); else the grid is capped (what the CUs hold at
+// once -- per_cu() is asked only then -- and 256 MiB of scratch) and finished
+// blocks take the next pair from a queue.  Scratch and counter are allocated
+// stream-ordered on `st`, like the long-pair launch's scratch; launch(mem,
+// next, blocks) enqueues the kernel.
+extern "C++" {
+template <class PerCu, class Launch>
+static int trace_grid_launch(msw_ctx* ctx, uint64_t n_pairs, uint64_t block_bytes, hipStream_t st, PerCu per_cu,
+                             Launch launch) {
+    uint64_t resident = 0;
+    if (block_bytes) {
+        const int k = per_cu();
+        if (k <= 0) return fail(MSW_E_DEVICE, "traceback kernel does not fit a CU");
+        resident = (uint64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (uint64_t)k;
     }
-    if (ctx->opt.trace_blocks) blocks = std::min<uint64_t>(blocks, ctx->opt.trace_blocks);  // tests: a fixed block count
+    // MSW_TRACE_BLOCKS: tests fix the block count
+    const uint64_t blocks = msw::trace_grid_cap(n_pairs, resident, block_bytes, ctx->opt.trace_blocks);
     const bool queue = blocks < n_pairs;
     uint8_t* mem = nullptr;
-    if (slab || queue) {
-        HIP_TRY(hipMallocAsync((void**)&mem, blocks * slab_bytes + 256, st));
-        if (slab) {
-            p.slab = reinterpret_cast<uint32_t*>(mem);
-            p.slab_words = need;
-        }
+    uint32_t* next = nullptr;
+    if (block_bytes || queue) {
+        HIP_TRY(hipMallocAsync((void**)&mem, blocks * block_bytes + 256, st));
         if (queue) {
-            p.next = reinterpret_cast<uint32_t*>(mem + blocks * slab_bytes);
-            const hipError_t em = hipMemsetAsync(p.next, 0, sizeof(uint32_t), st);
+            next = reinterpret_cast<uint32_t*>(mem + blocks * block_bytes);
+            const hipError_t em = hipMemsetAsync(next, 0, sizeof(uint32_t), st);
             if (em != hipSuccess) {
                 (void)hipFreeAsync(mem, st);
                 HIP_TRY(em);
             }
         }
     }
-    const hipError_t e = msw::launch_sw_trace(p, sch.affine, (uint32_t)blocks, shm, st);
+    const hipError_t e = launch(block_bytes ? mem : nullptr, next, (uint32_t)blocks);
     if (mem) HIP_TRY(hipFreeAsync(mem, st));
     HIP_TRY(e);
     return MSW_OK;
+}
+}  // extern "C++"
+
+// sw_trace_kernel: the direction words of the whole rectangle, in LDS while
+// the bound's rectangle fits, else in a global slab per block.
+static int run_trace(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, msw::TraceParams p, uint64_t n_pairs,
+                     uint32_t max_read_len, uint32_t max_win_len, hipStream_t st) {
+    trace_call_params(p, sc, n_pairs, max_read_len, max_win_len);
+    const size_t shm = msw::trace_lds_layout(p, sch.affine);
+    const uint64_t need = msw::trace_words(sch.affine, max_read_len, max_win_len);
+    const uint64_t slab_bytes = need > p.lds_words ? need * sizeof(uint32_t) : 0;
+    return trace_grid_launch(
+        ctx, n_pairs, slab_bytes, st, [&] { return msw::trace_blocks_per_cu(sch.affine, max_read_len, shm); },
+        [&](uint8_t* mem, uint32_t* next, uint32_t blocks) {
+            p.slab = reinterpret_cast<uint32_t*>(mem);
+            p.slab_words = mem ? need : 0;
+            p.next = next;
+            return msw::launch_sw_trace(p, sch.affine, blocks, shm, st);
+        });
+}
+
+// sw_trace_long_kernel: bounds past the packed range (or MSW_FORCE_LONG);
+// every block has its checkpoint rows, strip slab and op buffer in scratch.
+static int run_trace_long(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, msw::TraceParams p,
+                          uint64_t n_pairs, uint32_t max_read_len, uint32_t max_win_len, hipStream_t st) {
+    trace_call_params(p, sc, n_pairs, max_read_len, max_win_len);
+    const msw::TraceLongLayout l = msw::trace_long_layout(sch.affine, max_read_len, max_win_len, p.cigar_stride);
+    p.win_bytes = l.win_bytes;
+    p.ops_cap = l.ops_cap;
+    msw::TraceLongParams q;
+    memset(&q, 0, sizeof(q));
+    q.block_bytes = l.block_bytes;
+    q.slab_off = l.slab_off;
+    q.ops_off = l.ops_off;
+    q.ckpt_cols = l.ckpt_cols;
+    q.slab_w = l.slab_w;
+    q.ops_in_lds = l.ops_in_lds;
+    return trace_grid_launch(
+        ctx, n_pairs, l.block_bytes, st,
+        [&] { return msw::trace_long_blocks_per_cu(sch.affine, max_read_len, l.lds_bytes); },
+        [&](uint8_t* mem, uint32_t* next, uint32_t blocks) {
+            q.t = p;
+            q.t.next = next;
+            q.scratch = mem;
+            return msw::launch_sw_trace_long(q, sch.affine, blocks, l.lds_bytes, st);
+        });
+}
+
+// The kernel a traceback call runs on: the *_long calls leave the packed range
+// (or take MSW_FORCE_LONG) as msw_align_batch_device does for scoring.
+static int run_trace_any(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, const msw::TraceParams& p,
+                         uint64_t n_pairs, uint32_t max_read_len, uint32_t max_win_len, hipStream_t st,
+                         bool long_pairs) {
+    if (long_pairs && (ctx->opt.force_long || is_long(max_read_len, max_win_len)))
+        return run_trace_long(ctx, sch, sc, p, n_pairs, max_read_len, max_win_len, st);
+    return run_trace(ctx, sch, sc, p, n_pairs, max_read_len, max_win_len, st);
 }
 
 static void trace_outputs(msw::TraceParams& p, const msw_out_t* ends, const msw_trace_t* tr) {
@@ -1855,8 +1915,9 @@ static void trace_outputs(msw::TraceParams& p, const msw_out_t* ends, const msw_
     p.cigar_stride = tr->cigar_stride;
 }
 
-int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
-                           msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
+static int trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
+                              msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream,
+                              bool long_pairs) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     Scheme sch;
     int rc;
@@ -1864,7 +1925,7 @@ int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     sch.coords = true;  // want_coords is not read: the ends are an input here
     if ((rc = validate_batch(b, ends, sch)) || (rc = validate_trace(tr))) return rc;
     if (b->n_pairs == 0) return MSW_OK;
-    if ((rc = check_trace_bounds(max_read_len, max_win_len))) return rc;
+    if ((rc = check_trace_bounds(sch, max_read_len, max_win_len, long_pairs))) return rc;
     // one block per pair: a 1-D grid holds 2^31 - 1 blocks
     if (b->n_pairs > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
     if ((rc = check_strides(*b, max_read_len, max_win_len))) return rc;
@@ -1879,13 +1940,23 @@ int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     p.read_stride = b->read_stride;
     p.win_stride = b->win_stride;
     trace_outputs(p, ends, tr);
-    return run_trace(ctx, sch, sc, p, b->n_pairs, max_read_len, max_win_len, st);
+    return run_trace_any(ctx, sch, sc, p, b->n_pairs, max_read_len, max_win_len, st, long_pairs);
 }
 
-int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
-                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
-                           uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
-                           void* stream) {
+int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
+                           msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
+    return trace_batch_device(ctx, sc, b, ends, tr, max_read_len, max_win_len, stream, false);
+}
+
+int msw_trace_long_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
+                                msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
+    return trace_batch_device(ctx, sc, b, ends, tr, max_read_len, max_win_len, stream, true);
+}
+
+static int trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                              const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                              uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
+                              void* stream, bool long_pairs) {
     if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
     if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
     Scheme sch;
@@ -1897,7 +1968,7 @@ int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
     if (!ends || !ends->end_i || !ends->end_j) return fail(MSW_E_INVALID, "traceback needs end_i / end_j");
     // the window bound of msw_align_reads_device
     const uint32_t max_win = window ? window : std::min<uint32_t>(2u * max_read_len, (uint32_t)msw::kMaxWinLen);
-    if ((rc = check_trace_bounds(max_read_len, max_win))) return rc;
+    if ((rc = check_trace_bounds(sch, max_read_len, max_win, long_pairs))) return rc;
     if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n > 2^31-1 in one call");
     if (max_read_len > read_stride) return fail(MSW_E_INVALID, "max_read_len exceeds read_stride");
     if ((rc = set_device(ctx))) return rc;
@@ -1912,7 +1983,23 @@ int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
     p.win_pos = win_pos;
     p.window = window;
     trace_outputs(p, ends, tr);
-    return run_trace(ctx, sch, sc, p, n, max_read_len, max_win, st);
+    return run_trace_any(ctx, sch, sc, p, n, max_read_len, max_win, st, long_pairs);
+}
+
+int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                           uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
+                           void* stream) {
+    return trace_reads_device(ctx, sc, g, reads, read_len, read_stride, win_pos, n, window, max_read_len, ends, tr,
+                              stream, false);
+}
+
+int msw_trace_reads_long_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                                const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
+                                uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
+                                void* stream) {
+    return trace_reads_device(ctx, sc, g, reads, read_len, read_stride, win_pos, n, window, max_read_len, ends, tr,
+                              stream, true);
 }
 
 static int validate_aln(const msw_aln_t* a) {
@@ -1966,8 +2053,8 @@ int msw_aln_pack_device(msw_ctx* ctx, const msw_genome* g, const uint8_t* reads,
     return MSW_OK;
 }
 
-int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
-                          msw_trace_t* tr, uint64_t chunk_pairs) {
+static int align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
+                             msw_trace_t* tr, uint64_t chunk_pairs, bool long_pairs) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     if (!sc) return fail(MSW_E_INVALID, "scoring is NULL");
     msw_scoring_t scc = *sc;
@@ -1981,7 +2068,7 @@ int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch
     uint32_t max_m = 0, max_n = 0;
     max_u16(b->read_len, n, max_m);
     max_u16(b->win_len, n, max_n);
-    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+    if ((rc = check_trace_bounds(sch, max_m, max_n, long_pairs))) return rc;
     if (max_m > b->read_stride || max_n > b->win_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
     if ((rc = set_device(ctx))) return rc;
     // Simple and synchronous: per chunk upload, score with coordinates, trace,
@@ -2022,7 +2109,7 @@ int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch
                            (uint32_t)cs};
         if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) break;
         // same stream: the trace reads the ends the scoring launch wrote
-        if ((rc = msw_trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st))) break;
+        if ((rc = trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st, long_pairs))) break;
         down(out->score + lo, dout.score, c * 4);
         down(out->end_i + lo, d_ei, c * 2);
         down(out->end_j + lo, d_ej, c * 2);
@@ -2037,6 +2124,16 @@ int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch
     if (rc) return rc;
     if (e != hipSuccess) return fail(MSW_E_DEVICE, "traceback: %s", hipGetErrorString(e));
     return MSW_OK;
+}
+
+int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
+                          msw_trace_t* tr, uint64_t chunk_pairs) {
+    return align_batch_trace(ctx, sc, b, out, tr, chunk_pairs, false);
+}
+
+int msw_align_batch_trace_long(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
+                               msw_trace_t* tr, uint64_t chunk_pairs) {
+    return align_batch_trace(ctx, sc, b, out, tr, chunk_pairs, true);
 }
 
 }  // extern "C"
@@ -2457,7 +2554,8 @@ int msw_align_reads_strands_device(msw_ctx* ctx, const msw_scoring_t* sc, const 
 // trace and the pack read the oriented rows, and aln may be NULL for scores
 // alone, with coordinates as sc says).
 static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
-                         msw_out_t* out, msw_aln_t* aln, uint8_t* strand, bool both, uint64_t chunk_pairs) {
+                         msw_out_t* out, msw_aln_t* aln, uint8_t* strand, bool both, uint64_t chunk_pairs,
+                         bool long_pairs = false) {
     if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
     if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
     if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
@@ -2487,7 +2585,7 @@ static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome
     max_u16(b->read_len, n, max_m);
     max_u16(b->win_len, n, max_n);
     if (aln) {
-        if ((rc = check_trace_bounds(max_m, max_n))) return rc;
+        if ((rc = check_trace_bounds(sch, max_m, max_n, long_pairs))) return rc;
     } else if ((rc = check_bounds(sch, max_m, max_n))) {
         return rc;
     }
@@ -2497,9 +2595,12 @@ static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome
     // cut, score with coordinates, trace, pack, download.  The trace stride is
     // exact (no alignment has more ops than rows + columns), so no read
     // overflows; the packed ops of a chunk are pulled once its total is known.
-    const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
     const size_t rs = b->read_stride, ws = std::max<size_t>(16, (max_n + 15u) & ~15u),
                  cs = aln ? (size_t)max_m + max_n : 0;
+    uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
+    // past the packed range the exact stride reaches 65,534 ops: a chunk's trace rows stay within 1 GiB
+    if (long_pairs && is_long(max_m, max_n))
+        chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, (1ull << 30) / (cs * 4)));
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // [reads | wins | rows u32 | pos i64 | ref i64 | score nc nm i32 | off u32 [c+1] + ovf | 7 x 2 B arrays]
     const size_t o_wins = up256(chunk * rs), o_rows = up256(o_wins + chunk * ws), o_pos = up256(o_rows + chunk * cs * 4);
@@ -2581,7 +2682,7 @@ static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome
         } else if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) {
             break;
         }
-        if ((rc = msw_trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st))) break;
+        if ((rc = trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st, long_pairs))) break;
         uint64_t total = 0;
         for (int pass = 0; pass < 2; ++pass) {
             msw_aln_t da = {d_ref, reinterpret_cast<int32_t*>(d + o_nm), d_off, d_ops, ops_cap, d_off + c + 1};
@@ -2622,6 +2723,11 @@ static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome
 int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
                           msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
     return reads_records(ctx, sc, g, b, out, aln, nullptr, false, chunk_pairs);
+}
+
+int msw_align_reads_trace_long(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                               const msw_read_batch_t* b, msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
+    return reads_records(ctx, sc, g, b, out, aln, nullptr, false, chunk_pairs, true);
 }
 
 int msw_align_reads_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
@@ -4182,6 +4288,7 @@ int msw_ctx_prepare(msw_ctx* ctx, const msw_scoring_t* sc) {
     tp.max_cols = 300;
     tp.cigar_stride = 64;
     ok &= msw::trace_blocks_per_cu(sch.affine, tp.max_rows, msw::trace_lds_layout(tp, sch.affine)) > 0;  // traceback
+    ok &= msw::trace_long_blocks_per_cu(sch.affine, 385, msw::trace_long_layout(sch.affine, 385, 600, 64).lds_bytes) > 0;
     (void)hipGetLastError();
     return ok ? MSW_OK : fail(MSW_E_DEVICE, "kernel module load failed");
 }
