@@ -10,30 +10,26 @@
 //                        -> msw_align_batch: pinned double-buffered staging, H2D
 //                           on a copy stream overlapped with the kernels
 //   system_info.rs:236-243  80 % memory cap -> hipMemGetInfo
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <mutex>
+// Traceback and records, mapping, and pileup and calls are in msw_rt_trace.cpp,
+// msw_rt_map.cpp and msw_rt_pileup.cpp (msw_runtime_internal.h).
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <atomic>
-#include <deque>
-#include <functional>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/msw.h"
-#include "msw_kernels.h"
+#include "msw_runtime_internal.h"
+
+using namespace msw_detail;
 
 namespace {
 
 thread_local std::string g_last_error;
 
+}  // namespace
+
+namespace msw_detail {
 int fail(int code, const char* fmt, ...) {
     char buf[1024];
     va_list ap;
@@ -44,9 +40,6 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-}  // namespace
-
-namespace msw_detail {
 int set_error(int code, const char* fmt, ...) {
     char buf[1024];
     va_list ap;
@@ -60,36 +53,7 @@ int set_error(int code, const char* fmt, ...) {
 
 namespace {
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(MSW_E_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                        __FILE__, __LINE__);                                                   \
-    } while (0)
-
 inline uint32_t dup16(uint32_t v) { return (v & 0xFFFFu) | ((v & 0xFFFFu) << 16); }
-
-// The library's run-time switches, read ONCE when a context is created
-// (msw_ctx_create -> read_options) and kept in the context: no call or launch
-// path reads the environment.  Every one forces a code path the tests cover
-// (INTEGRATION.md section 4), or turns a diagnostic trace on.
-struct Options {
-    bool no_f16 = false;          // MSW_NO_F16: the integer path for every launch
-    bool force_long = false;      // MSW_FORCE_LONG=1: every pair on the long-pair kernel
-    uint64_t long_blocks = 0;     // MSW_LONG_BLOCKS: a fixed long-pair block count (work-queue grids)
-    uint64_t trace_blocks = 0;    // MSW_TRACE_BLOCKS: a fixed traceback block count (work-queue grids)
-    bool layout_set = false;      // MSW_LAYOUT given (per-bucket launches then)
-    bool force_pairs = false, force_split = false, force_mixed = false;  // its value
-    bool group_set = false;       // MSW_GROUP_LANES given
-    uint32_t group_lanes = 0;     // its value (8..16)
-    bool no_multi = false;        // MSW_NO_MULTI: one launch per bucket
-    bool host_trace = false;      // MSW_HOST_TRACE: per-call host phase times on stderr
-    std::string wave_trace;       // MSW_WAVE_TRACE=file: per-block placement records
-    uint64_t chunk = 65536;       // GPU_CHUNK_SIZE_READS: default pairs per staged chunk (aligner.rs:9-15)
-    uint64_t gz_group_bytes = 1024ull << 20;  // MSW_GZ_GROUP_MB: output bytes per msw_bgzf_inflate launch
-    bool pileup_planes = false;   // MSW_PILEUP_PLANES=1: a pileup's device counts as eight planes, not rows of eight
-};
 
 Options read_options() {
     Options o;
@@ -126,20 +90,11 @@ Options read_options() {
     return o;
 }
 
-const Options kDefaultOptions{};
+}  // namespace
 
-// Validated kernel constants for one scoring scheme.
-struct Scheme {
-    const Options* opt = &kDefaultOptions;  // the context's switches
-    bool affine, coords;
-    uint32_t match2, delta2, gap2, open_ext2, bias2, code_shift;
-    int32_t match;
-    uint32_t bias;  // affine value bias K (0 for linear)
-    // f16 fast path: match and mismatch are f16 values with a zero low byte
-    // (the v_perm tables hold high bytes only); per-launch bound in f16_fits.
-    bool f16_scheme;
-    uint32_t f16_hi, f16_ngap2, f16_noe2;
-};
+namespace msw_detail {
+
+const Options kDefaultOptions{};
 
 int make_scheme(const msw_scoring_t* sc, const Options& opt, Scheme* s) {
     if (!sc) return fail(MSW_E_INVALID, "scoring is NULL");
@@ -180,12 +135,6 @@ int make_scheme(const msw_scoring_t* sc, const Options& opt, Scheme* s) {
     return MSW_OK;
 }
 
-// The f16 path holds every cell value (<= match * min(m, n)) below 2048.
-bool f16_fits(const Scheme& s, uint32_t max_m, uint32_t max_n) {
-    if (s.opt->no_f16) return false;  // tests: force the integer path
-    return s.f16_scheme && (uint64_t)s.match * (std::min(max_m, max_n) + 2u) < 2048u;
-}
-
 // Length limits: pairs up to kMaxReadLen x kMaxWinLen run on the packed
 // 16-bit kernels (every cell value, <= match * (384 + 1) + bias <= 64 * 385 +
 // 1280 = 25920 < 0x7C00, is a finite non-negative f16 bit pattern for
@@ -201,10 +150,17 @@ int check_bounds(const Scheme& s, uint32_t max_m, uint32_t max_n) {
     return MSW_OK;
 }
 
-// A pair (or a bound) beyond the packed kernels' limits.
-inline bool is_long(uint32_t m, uint32_t n) {
-    return m > (uint32_t)msw::kMaxReadLen || n > (uint32_t)msw::kMaxWinLen;
+}  // namespace msw_detail
+
+namespace {
+
+// The f16 path holds every cell value (<= match * min(m, n)) below 2048.
+bool f16_fits(const Scheme& s, uint32_t max_m, uint32_t max_n) {
+    if (s.opt->no_f16) return false;  // tests: force the integer path
+    return s.f16_scheme && (uint64_t)s.match * (std::min(max_m, max_n) + 2u) < 2048u;
 }
+
+
 // MSW_FORCE_LONG=1 (Options::force_long) sends every pair to the long-pair
 // kernel (tests and tools/long_bench.py run it on the packed kernels' shapes).
 
@@ -268,42 +224,6 @@ msw::SwParams base_params(const Scheme& s) {
     return p;
 }
 
-// Device + pinned buffers for one in-flight chunk.  The per-pair metadata of a
-// chunk (window positions, read and window lengths, slot order) is one block,
-// [pos i64 | rlen u16 | wlen u16 | order u32] x n, uploaded by ONE copy of the
-// part the chunk uses (pairs mode skips the positions, a chunk in input order
-// the order); the results [score i32 | end_i i16 | end_j i16] come back by one
-// copy, or are written by the kernels straight into the pinned block (a
-// one-chunk call: no copy and no event between the kernel and the host).
-struct Slot {
-    size_t cap_pairs = 0, cap_read = 0, cap_win = 0;
-    uint8_t *d_reads = nullptr, *d_wins = nullptr, *d_meta = nullptr, *d_res = nullptr;
-    uint8_t *h_reads = nullptr, *h_wins = nullptr, *h_meta = nullptr, *h_res = nullptr;
-    // device addresses of the pinned staging blocks (one-chunk calls pull from them)
-    const uint8_t *g_reads = nullptr, *g_wins = nullptr, *g_meta = nullptr;
-    // views into d_meta / h_meta and d_res / h_res
-    int64_t *d_pos = nullptr, *h_pos = nullptr;
-    uint32_t *d_order = nullptr, *h_order = nullptr;
-    uint16_t *d_rlen = nullptr, *d_wlen = nullptr, *h_rlen = nullptr, *h_wlen = nullptr;
-    int32_t *d_score = nullptr, *h_score = nullptr;
-    int16_t *d_ei = nullptr, *d_ej = nullptr, *h_ei = nullptr, *h_ej = nullptr;
-    // where this chunk's kernels store results: the device block or the host one
-    int32_t* k_score = nullptr;
-    int16_t *k_ei = nullptr, *k_ej = nullptr;
-    hipEvent_t uploaded = nullptr, computed = nullptr, done = nullptr;
-    // timing events around the chunk's scoring launches; a chunk whose kernels
-    // write the host block directly ends on k_end (done is not recorded)
-    hipEvent_t k_start = nullptr, k_end = nullptr;
-    bool busy = false;
-    bool by_slot = false;  // results in slot order: the drain scatters them through h_order
-    bool direct_out = false;  // the kernels wrote h_res themselves; k_end marks completion
-    uint64_t ticket = 0;  // msw_align_*_async call that owns the chunk in flight
-    uint64_t seq = 0;     // submission order of the chunk (drains go in this order)
-    // Pending readback bookkeeping.
-    uint64_t first = 0, count = 0;
-    msw_out_t out{};
-};
-
 constexpr size_t kMetaBytesPerPair = 8 + 2 + 2 + 4;
 constexpr size_t kResBytesPerPair = 4 + 2 + 2;
 
@@ -334,113 +254,11 @@ void free_slot(Slot& s) {
 
 }  // namespace
 
-struct msw_ctx {
-    int device = 0;
-    int cu_count = 256;
-    Options opt;  // the environment's switches, read at creation
-    // compute: created with the context; the others too, unless the context
-    // is lean (MSW_CTX_LEAN: made by the first call that uses them,
-    // aux_streams): a stream costs 3-30 ms to create (the first few each make
-    // a hardware queue) and as much to destroy, and the --full-wgs GPU-reader
-    // workers never use them (profiles/r06/c3f/)
-    hipStream_t compute = nullptr, copy = nullptr, d2h = nullptr;
-    // multi-chunk calls alternate their chunks' kernels over compute and
-    // compute2, so chunk k+1's waves start under chunk k's tail (one stream
-    // would idle the CUs the tail leaves)
-    hipStream_t compute2 = nullptr;
-    hipStream_t side = nullptr;  // long-pair launches beside packed ones (fork_side)
-    // Staging slots, used round robin by successive chunks (and calls): with
-    // three, the host stages chunk k+1 while k runs and k-1 drains, so the
-    // uploads of k+1 finish under kernel k.
-    static constexpr int kSlots = 3;
-    Slot slots[kSlots];
-    uint64_t next_ticket = 1, done_ticket = 0;
-    uint64_t slot_seq = 0;  // chunks submitted (slot = slot_seq % kSlots)
-    msw_stats_t stats{};    // msw_ctx_stats: host-batch calls since creation / the last reset
-    // Origin of the kernel-time interval union (recorded at creation, moved
-    // forward every ~second of GPU time so float ms offsets stay fine-grained:
-    // epoch_next is recorded, and once it has completed becomes the epoch)
-    hipEvent_t epoch = nullptr, epoch_next = nullptr;
-    double busy_until = 0.0;     // ms after epoch at which the counted scoring intervals end
-    // pinned_cached: the most recently used (address, bytes) ranges asked
-    // about, most recent first (move to front on a hit).  16: a --full-wgs
-    // worker's two result sets x five copies per batch, plus a call's reads /
-    // windows, stay cached (the 8-entry FIFO missed every one).
-    struct PinnedRange {
-        const void* p = nullptr;
-        size_t bytes = 0;
-        bool pinned = false;
-        const uint8_t* dev = nullptr;  // its device address (pinned ranges)
-    };
-    static constexpr unsigned kPinnedRanges = 16;
-    PinnedRange pinned_ranges[kPinnedRanges];
-    unsigned pinned_used = 0;
-    uint64_t pinned_epoch = 0;           // g_host_free_epoch when the cache was last valid
-    uint64_t pinned_hits = 0, pinned_misses = 0;  // MSW_HOST_TRACE
-    // compat buffers
-    uint8_t *c_s1 = nullptr, *c_s2 = nullptr;
-    int32_t* c_res = nullptr;
-    size_t c_cap = 0;
-    hipEvent_t c_k0 = nullptr, c_k1 = nullptr;  // timing of the compat launch (msw_ctx_stats)
-    // msw_align_reads_device scratch: the cut windows and their clipped lengths
-    // msw_align_reads_device's window slab and lengths, one set per stream
-    // it is called on (calls on two streams run concurrently)
-    struct ReadsScratch {
-        hipStream_t st = nullptr;
-        uint8_t* wins = nullptr;
-        uint16_t* wlen = nullptr;
-        size_t wins_cap = 0, wlen_cap = 0;
-        // both strands: the reverse pass's results [score i32 | end_i i16 | end_j i16]
-        uint8_t* rev = nullptr;
-        size_t rev_cap = 0;
-    };
-    std::vector<ReadsScratch> rscratch;
-    // streams made by msw_stream_create (synchronised by msw_synchronize,
-    // destroyed with the context if the caller has not)
-    std::vector<hipStream_t> user_streams;
-    // timing events of msw_align_reads_device launches not yet harvested
-    struct DevTiming {
-        hipEvent_t k0, k1;
-        uint64_t pairs;
-    };
-    std::deque<DevTiming> dev_timings;
-    std::vector<hipEvent_t> free_events;
-    // free_events and fences: msw_fence_wait may run on several threads at
-    // once (--full-wgs settles its last two batches on two)
-    std::mutex ev_mu;
-    // the plan of the last single-bucket launch of a host chunk or of a
-    // planned call (issue_schedule; MSW_HOST_TRACE prints it)
-    msw::Layout last_layout = msw::Layout::kPairs;
-    uint32_t last_group_lanes = 0, last_kr = 0;
-    std::unordered_map<uint64_t, hipEvent_t> fences;  // msw_fence_record, not yet waited on
-    uint64_t next_fence = 1;
-};
-
-struct msw_genome {
-    const msw_ctx* ctx = nullptr;  // identity only
-    int device = 0;
-    uint8_t* d_seq = nullptr;      // len + kGenomePad bytes (cut kernel over-reads <= 20)
-    uint64_t len = 0;
-};
-
-struct msw_index {
-    const msw_ctx* ctx = nullptr;  // identity only
-    int device = 0;
-    uint32_t k = 0, max_occ = 0;
-    uint64_t buckets = 0, n_pos = 0, n_masked = 0;
-    uint32_t* d_off = nullptr;     // [buckets + 1]
-    uint32_t* d_pos = nullptr;     // [max(n_pos, 1)]
-    double build_ms[5] = {0, 0, 0, 0, 0};
-};
-
 // Internal accessors for the other units of the library (msw_gfastq.cpp).
 namespace msw_detail {
 int ctx_device(const msw_ctx* c) { return c->device; }
 hipStream_t ctx_compute_stream(const msw_ctx* c) { return c->compute; }
 uint64_t ctx_gz_group_bytes(const msw_ctx* c) { return c->opt.gz_group_bytes; }
-}  // namespace msw_detail
-
-namespace {
 
 int set_device(msw_ctx* ctx) {
     int cur = -1;
@@ -449,10 +267,9 @@ int set_device(msw_ctx* ctx) {
     return MSW_OK;
 }
 
-// The stream of a device-API call: the caller's, or the context's compute stream.
-inline hipStream_t call_stream(const msw_ctx* ctx, void* stream) {
-    return stream ? (hipStream_t)stream : ctx->compute;
-}
+}  // namespace msw_detail
+
+namespace {
 
 // The streams a context creates on first use (compute is made with it).
 int aux_streams(msw_ctx* ctx) {
@@ -1096,22 +913,6 @@ int drain_through(msw_ctx* ctx, uint64_t ticket) {
     }
 }
 
-int validate_batch(const msw_batch_t* b, const msw_out_t* out, const Scheme& sch) {
-    if (!b || !out) return fail(MSW_E_INVALID, "batch/out is NULL");
-    if (b->n_pairs == 0) return MSW_OK;
-    if (!b->reads || !b->wins || !b->read_len || !b->win_len || !out->score)
-        return fail(MSW_E_INVALID, "NULL array in batch/out");
-    if (sch.coords && (!out->end_i || !out->end_j))
-        return fail(MSW_E_INVALID, "want_coords set but end_i/end_j is NULL");
-    if (b->n_pairs > 0xFFFFFFFFull) return fail(MSW_E_RANGE, "n_pairs > 2^32-1");
-    return MSW_OK;
-}
-
-// The length bounds a device-memory call states must fit the batch's rows.
-int check_strides(const msw_batch_t& b, uint32_t max_m, uint32_t max_n) {
-    if (max_m > b.read_stride || max_n > b.win_stride) return fail(MSW_E_INVALID, "max length exceeds stride");
-    return MSW_OK;
-}
 
 // Host-memory batch of either form: pairs (reads + windows) or reads against
 // a genome-resident window source (wins == nullptr, genome + win_pos set).
@@ -1145,8 +946,6 @@ bool is_pinned(const void* p, size_t bytes, const uint8_t** dev) {
     }
     return true;
 }
-
-inline uint32_t round16(uint32_t v) { return (v + 15u) & ~15u; }
 
 // Window length actually scored in genome mode: clipped at the genome end,
 // empty for positions outside it.
@@ -1220,12 +1019,37 @@ void clip_windows(const int64_t* __restrict pos, const uint16_t* __restrict want
     for (uint64_t i = 0; i < n; ++i) out[i] = genome_window(pos[i], want[i], glen);
 }
 
+}  // namespace
+
+namespace msw_detail {
+
 MSW_HOST_SIMD
 void max_u16(const uint16_t* __restrict a, uint64_t n, uint32_t& m) {
     uint32_t v = 0;
     for (uint64_t i = 0; i < n; ++i) v = std::max<uint32_t>(v, a[i]);
     m = v;
 }
+
+int validate_batch(const msw_batch_t* b, const msw_out_t* out, const Scheme& sch) {
+    if (!b || !out) return fail(MSW_E_INVALID, "batch/out is NULL");
+    if (b->n_pairs == 0) return MSW_OK;
+    if (!b->reads || !b->wins || !b->read_len || !b->win_len || !out->score)
+        return fail(MSW_E_INVALID, "NULL array in batch/out");
+    if (sch.coords && (!out->end_i || !out->end_j))
+        return fail(MSW_E_INVALID, "want_coords set but end_i/end_j is NULL");
+    if (b->n_pairs > 0xFFFFFFFFull) return fail(MSW_E_RANGE, "n_pairs > 2^32-1");
+    return MSW_OK;
+}
+
+// The length bounds a device-memory call states must fit the batch's rows.
+int check_strides(const msw_batch_t& b, uint32_t max_m, uint32_t max_n) {
+    if (max_m > b.read_stride || max_n > b.win_stride) return fail(MSW_E_INVALID, "max length exceeds stride");
+    return MSW_OK;
+}
+
+}  // namespace msw_detail
+
+namespace {
 
 ChunkScan stage_meta(Slot& s, const HostBatch& b, uint64_t first, uint64_t cnt) {
     memcpy(s.h_rlen, b.read_len + first, cnt * sizeof(uint16_t));
@@ -1777,365 +1601,6 @@ int msw_align_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batc
     return launch_packed(ctx, sch, p, (uint32_t)b->n_pairs, max_read_len, max_win_len, st);
 }
 
-// Traceback on sw_trace_kernel supports the packed kernels' range only; the
-// *_long calls take bounds up to kMaxLongLen (check_bounds).
-static int check_trace_bounds(uint32_t max_m, uint32_t max_n) {
-    if (max_m > (uint32_t)msw::kMaxReadLen)
-        return fail(MSW_E_RANGE, "traceback: read length %u > %d", max_m, msw::kMaxReadLen);
-    if (max_n > (uint32_t)msw::kMaxWinLen)
-        return fail(MSW_E_RANGE, "traceback: window length %u > %d", max_n, msw::kMaxWinLen);
-    return MSW_OK;
-}
-static int check_trace_bounds(const Scheme& sch, uint32_t max_m, uint32_t max_n, bool long_pairs) {
-    return long_pairs ? check_bounds(sch, max_m, max_n) : check_trace_bounds(max_m, max_n);
-}
-
-static int validate_trace(const msw_trace_t* tr) {
-    if (!tr) return fail(MSW_E_INVALID, "trace is NULL");
-    if (!tr->start_i || !tr->start_j || !tr->n_cigar) return fail(MSW_E_INVALID, "NULL array in trace");
-    if (tr->cigar_stride && !tr->cigar) return fail(MSW_E_INVALID, "cigar is NULL with cigar_stride > 0");
-    return MSW_OK;
-}
-
-// What both traceback kernels' launches share.  p holds the call's inputs and
-// outputs (windows from a slab or from the genome); this fills the bounds and
-// the scoring.
-static void trace_call_params(msw::TraceParams& p, const msw_scoring_t* sc, uint64_t n_pairs, uint32_t max_read_len,
-                              uint32_t max_win_len) {
-    p.n_slots = (uint32_t)n_pairs;
-    p.max_rows = max_read_len;
-    p.max_cols = max_win_len;
-    p.match = sc->match;
-    p.mismatch = sc->mismatch;
-    p.gap = sc->gap_extend;
-    p.goe = sc->gap_open + sc->gap_extend;
-}
-
-// The grid and its global scratch: one block per pair while a block needs no
-// scratch (block_bytes == 0); else the grid is capped (what the CUs hold at
-// once -- per_cu() is asked only then -- and 256 MiB of scratch) and finished
-// blocks take the next pair from a queue.  Scratch and counter are allocated
-// stream-ordered on `st`, like the long-pair launch's scratch; launch(mem,
-// next, blocks) enqueues the kernel.
-extern "C++" {
-template <class PerCu, class Launch>
-static int trace_grid_launch(msw_ctx* ctx, uint64_t n_pairs, uint64_t block_bytes, hipStream_t st, PerCu per_cu,
-                             Launch launch) {
-    uint64_t resident = 0;
-    if (block_bytes) {
-        const int k = per_cu();
-        if (k <= 0) return fail(MSW_E_DEVICE, "traceback kernel does not fit a CU");
-        resident = (uint64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * (uint64_t)k;
-    }
-    // MSW_TRACE_BLOCKS: tests fix the block count
-    const uint64_t blocks = msw::trace_grid_cap(n_pairs, resident, block_bytes, ctx->opt.trace_blocks);
-    const bool queue = blocks < n_pairs;
-    uint8_t* mem = nullptr;
-    uint32_t* next = nullptr;
-    if (block_bytes || queue) {
-        HIP_TRY(hipMallocAsync((void**)&mem, blocks * block_bytes + 256, st));
-        if (queue) {
-            next = reinterpret_cast<uint32_t*>(mem + blocks * block_bytes);
-            const hipError_t em = hipMemsetAsync(next, 0, sizeof(uint32_t), st);
-            if (em != hipSuccess) {
-                (void)hipFreeAsync(mem, st);
-                HIP_TRY(em);
-            }
-        }
-    }
-    const hipError_t e = launch(block_bytes ? mem : nullptr, next, (uint32_t)blocks);
-    if (mem) HIP_TRY(hipFreeAsync(mem, st));
-    HIP_TRY(e);
-    return MSW_OK;
-}
-}  // extern "C++"
-
-// sw_trace_kernel: the direction words of the whole rectangle, in LDS while
-// the bound's rectangle fits, else in a global slab per block.
-static int run_trace(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, msw::TraceParams p, uint64_t n_pairs,
-                     uint32_t max_read_len, uint32_t max_win_len, hipStream_t st) {
-    trace_call_params(p, sc, n_pairs, max_read_len, max_win_len);
-    const size_t shm = msw::trace_lds_layout(p, sch.affine);
-    const uint64_t need = msw::trace_words(sch.affine, max_read_len, max_win_len);
-    const uint64_t slab_bytes = need > p.lds_words ? need * sizeof(uint32_t) : 0;
-    return trace_grid_launch(
-        ctx, n_pairs, slab_bytes, st, [&] { return msw::trace_blocks_per_cu(sch.affine, max_read_len, shm); },
-        [&](uint8_t* mem, uint32_t* next, uint32_t blocks) {
-            p.slab = reinterpret_cast<uint32_t*>(mem);
-            p.slab_words = mem ? need : 0;
-            p.next = next;
-            return msw::launch_sw_trace(p, sch.affine, blocks, shm, st);
-        });
-}
-
-// sw_trace_long_kernel: bounds past the packed range (or MSW_FORCE_LONG);
-// every block has its checkpoint rows, strip slab and op buffer in scratch.
-static int run_trace_long(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, msw::TraceParams p,
-                          uint64_t n_pairs, uint32_t max_read_len, uint32_t max_win_len, hipStream_t st) {
-    trace_call_params(p, sc, n_pairs, max_read_len, max_win_len);
-    const msw::TraceLongLayout l = msw::trace_long_layout(sch.affine, max_read_len, max_win_len, p.cigar_stride);
-    p.win_bytes = l.win_bytes;
-    p.ops_cap = l.ops_cap;
-    msw::TraceLongParams q;
-    memset(&q, 0, sizeof(q));
-    q.block_bytes = l.block_bytes;
-    q.slab_off = l.slab_off;
-    q.ops_off = l.ops_off;
-    q.ckpt_cols = l.ckpt_cols;
-    q.slab_w = l.slab_w;
-    q.ops_in_lds = l.ops_in_lds;
-    return trace_grid_launch(
-        ctx, n_pairs, l.block_bytes, st,
-        [&] { return msw::trace_long_blocks_per_cu(sch.affine, max_read_len, l.lds_bytes); },
-        [&](uint8_t* mem, uint32_t* next, uint32_t blocks) {
-            q.t = p;
-            q.t.next = next;
-            q.scratch = mem;
-            return msw::launch_sw_trace_long(q, sch.affine, blocks, l.lds_bytes, st);
-        });
-}
-
-// The kernel a traceback call runs on: the *_long calls leave the packed range
-// (or take MSW_FORCE_LONG) as msw_align_batch_device does for scoring.
-static int run_trace_any(msw_ctx* ctx, const Scheme& sch, const msw_scoring_t* sc, const msw::TraceParams& p,
-                         uint64_t n_pairs, uint32_t max_read_len, uint32_t max_win_len, hipStream_t st,
-                         bool long_pairs) {
-    if (long_pairs && (ctx->opt.force_long || is_long(max_read_len, max_win_len)))
-        return run_trace_long(ctx, sch, sc, p, n_pairs, max_read_len, max_win_len, st);
-    return run_trace(ctx, sch, sc, p, n_pairs, max_read_len, max_win_len, st);
-}
-
-static void trace_outputs(msw::TraceParams& p, const msw_out_t* ends, const msw_trace_t* tr) {
-    p.end_i = ends->end_i;
-    p.end_j = ends->end_j;
-    p.start_i = tr->start_i;
-    p.start_j = tr->start_j;
-    p.n_cigar = tr->n_cigar;
-    p.cigar = tr->cigar;
-    p.cigar_stride = tr->cigar_stride;
-}
-
-static int trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
-                              msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream,
-                              bool long_pairs) {
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    Scheme sch;
-    int rc;
-    if ((rc = make_scheme(sc, ctx->opt, &sch))) return rc;
-    sch.coords = true;  // want_coords is not read: the ends are an input here
-    if ((rc = validate_batch(b, ends, sch)) || (rc = validate_trace(tr))) return rc;
-    if (b->n_pairs == 0) return MSW_OK;
-    if ((rc = check_trace_bounds(sch, max_read_len, max_win_len, long_pairs))) return rc;
-    // one block per pair: a 1-D grid holds 2^31 - 1 blocks
-    if (b->n_pairs > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
-    if ((rc = check_strides(*b, max_read_len, max_win_len))) return rc;
-    if ((rc = set_device(ctx))) return rc;
-    hipStream_t st = call_stream(ctx, stream);
-    msw::TraceParams p;
-    memset(&p, 0, sizeof(p));
-    p.reads = b->reads;
-    p.wins = b->wins;
-    p.read_len = b->read_len;
-    p.win_len = b->win_len;
-    p.read_stride = b->read_stride;
-    p.win_stride = b->win_stride;
-    trace_outputs(p, ends, tr);
-    return run_trace_any(ctx, sch, sc, p, b->n_pairs, max_read_len, max_win_len, st, long_pairs);
-}
-
-int msw_trace_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
-                           msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
-    return trace_batch_device(ctx, sc, b, ends, tr, max_read_len, max_win_len, stream, false);
-}
-
-int msw_trace_long_batch_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const msw_out_t* ends,
-                                msw_trace_t* tr, uint32_t max_read_len, uint32_t max_win_len, void* stream) {
-    return trace_batch_device(ctx, sc, b, ends, tr, max_read_len, max_win_len, stream, true);
-}
-
-static int trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
-                              const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
-                              uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
-                              void* stream, bool long_pairs) {
-    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    Scheme sch;
-    int rc;
-    if ((rc = make_scheme(sc, ctx->opt, &sch))) return rc;
-    if ((rc = validate_trace(tr))) return rc;
-    if (n == 0) return MSW_OK;
-    if (!reads || !read_len || !win_pos) return fail(MSW_E_INVALID, "NULL array");
-    if (!ends || !ends->end_i || !ends->end_j) return fail(MSW_E_INVALID, "traceback needs end_i / end_j");
-    // the window bound of msw_align_reads_device
-    const uint32_t max_win = window ? window : std::min<uint32_t>(2u * max_read_len, (uint32_t)msw::kMaxWinLen);
-    if ((rc = check_trace_bounds(sch, max_read_len, max_win, long_pairs))) return rc;
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n > 2^31-1 in one call");
-    if (max_read_len > read_stride) return fail(MSW_E_INVALID, "max_read_len exceeds read_stride");
-    if ((rc = set_device(ctx))) return rc;
-    hipStream_t st = call_stream(ctx, stream);
-    msw::TraceParams p;
-    memset(&p, 0, sizeof(p));
-    p.reads = reads;
-    p.read_len = read_len;
-    p.read_stride = read_stride;
-    p.genome = g->d_seq;
-    p.glen = g->len;
-    p.win_pos = win_pos;
-    p.window = window;
-    trace_outputs(p, ends, tr);
-    return run_trace_any(ctx, sch, sc, p, n, max_read_len, max_win, st, long_pairs);
-}
-
-int msw_trace_reads_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
-                           const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
-                           uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
-                           void* stream) {
-    return trace_reads_device(ctx, sc, g, reads, read_len, read_stride, win_pos, n, window, max_read_len, ends, tr,
-                              stream, false);
-}
-
-int msw_trace_reads_long_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
-                                const uint16_t* read_len, uint32_t read_stride, const int64_t* win_pos, uint64_t n,
-                                uint32_t window, uint32_t max_read_len, const msw_out_t* ends, msw_trace_t* tr,
-                                void* stream) {
-    return trace_reads_device(ctx, sc, g, reads, read_len, read_stride, win_pos, n, window, max_read_len, ends, tr,
-                              stream, true);
-}
-
-static int validate_aln(const msw_aln_t* a) {
-    if (!a) return fail(MSW_E_INVALID, "aln is NULL");
-    if (!a->ref_pos || !a->nm || !a->cigar_off || !a->n_overflow) return fail(MSW_E_INVALID, "NULL array in aln");
-    if (a->cigar_cap && !a->cigar) return fail(MSW_E_INVALID, "cigar is NULL with cigar_cap > 0");
-    return MSW_OK;
-}
-
-int msw_aln_pack_device(msw_ctx* ctx, const msw_genome* g, const uint8_t* reads, const uint16_t* read_len,
-                        uint32_t read_stride, const int64_t* win_pos, uint64_t n, const msw_out_t* ends,
-                        const msw_trace_t* tr, msw_aln_t* aln, void* stream) {
-    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    int rc;
-    if ((rc = validate_aln(aln))) return rc;
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "aln pack: n > 2^31-1 in one call");
-    if (n) {
-        if ((rc = validate_trace(tr))) return rc;
-        if (!reads || !read_len || !win_pos) return fail(MSW_E_INVALID, "NULL array");
-        if (!ends || !ends->score || !ends->end_i || !ends->end_j)
-            return fail(MSW_E_INVALID, "aln pack needs score / end_i / end_j");
-    }
-    if ((rc = set_device(ctx))) return rc;
-    hipStream_t st = call_stream(ctx, stream);
-    msw::AlnParams p;
-    memset(&p, 0, sizeof(p));
-    p.genome = g->d_seq;
-    p.glen = g->len;
-    p.reads = reads;
-    p.read_len = read_len;
-    p.read_stride = read_stride;
-    p.win_pos = win_pos;
-    p.n = n;
-    if (n) {
-        p.score = ends->score;
-        p.end_i = ends->end_i;
-        p.start_i = tr->start_i;
-        p.start_j = tr->start_j;
-        p.n_cigar = tr->n_cigar;
-        p.rows = tr->cigar;
-        p.cigar_stride = tr->cigar_stride;
-    }
-    p.ref_pos = aln->ref_pos;
-    p.nm = aln->nm;
-    p.cigar_off = aln->cigar_off;
-    p.cigar = aln->cigar;
-    p.cigar_cap = aln->cigar_cap;
-    p.n_overflow = aln->n_overflow;
-    HIP_TRY(msw::launch_aln_pack(p, st));
-    return MSW_OK;
-}
-
-static int align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
-                             msw_trace_t* tr, uint64_t chunk_pairs, bool long_pairs) {
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    if (!sc) return fail(MSW_E_INVALID, "scoring is NULL");
-    msw_scoring_t scc = *sc;
-    scc.want_coords = 1;
-    Scheme sch;
-    int rc;
-    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
-    if ((rc = validate_batch(b, out, sch)) || (rc = validate_trace(tr))) return rc;
-    const uint64_t n = b->n_pairs;
-    if (n == 0) return MSW_OK;
-    uint32_t max_m = 0, max_n = 0;
-    max_u16(b->read_len, n, max_m);
-    max_u16(b->win_len, n, max_n);
-    if ((rc = check_trace_bounds(sch, max_m, max_n, long_pairs))) return rc;
-    if (max_m > b->read_stride || max_n > b->win_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    // Simple and synchronous: per chunk upload, score with coordinates, trace,
-    // download (not part of the three-slot staging pipeline).
-    const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
-    const size_t rs = b->read_stride, ws = b->win_stride, cs = tr->cigar_stride;
-    // [reads | wins | cigar u32 | score i32 | n_cigar i32 | rlen wlen end_i end_j start_i start_j, 2 B each]
-    const size_t o_wins = (chunk * rs + 255) & ~(size_t)255, o_cig = (o_wins + chunk * ws + 255) & ~(size_t)255;
-    const size_t o_score = o_cig + chunk * cs * 4, o_nc = o_score + chunk * 4, o_h = o_nc + chunk * 4;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, o_h + chunk * 12 + 256);
-    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", o_h + chunk * 12, hipGetErrorString(e));
-    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
-    uint16_t* d_wl = d_rl + chunk;
-    int16_t *d_ei = reinterpret_cast<int16_t*>(d_wl + chunk), *d_ej = d_ei + chunk, *d_si = d_ej + chunk,
-            *d_sj = d_si + chunk;
-    hipStream_t st = ctx->compute;
-    rc = MSW_OK;
-    for (uint64_t lo = 0; lo < n && rc == MSW_OK; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        uint32_t cm = 0, cn = 0;
-        max_u16(b->read_len + lo, c, cm);
-        max_u16(b->win_len + lo, c, cn);
-        auto up = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-        };
-        auto down = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-        };
-        up(d, b->reads + lo * rs, c * rs);
-        up(d + o_wins, b->wins + lo * ws, c * ws);
-        up(d_rl, b->read_len + lo, c * 2);
-        up(d_wl, b->win_len + lo, c * 2);
-        if (e != hipSuccess) break;
-        msw_batch_t db = {d, d + o_wins, d_rl, d_wl, (uint32_t)rs, (uint32_t)ws, c};
-        msw_out_t dout = {reinterpret_cast<int32_t*>(d + o_score), d_ei, d_ej};
-        msw_trace_t dtr = {d_si, d_sj, reinterpret_cast<int32_t*>(d + o_nc), reinterpret_cast<uint32_t*>(d + o_cig),
-                           (uint32_t)cs};
-        if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) break;
-        // same stream: the trace reads the ends the scoring launch wrote
-        if ((rc = trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st, long_pairs))) break;
-        down(out->score + lo, dout.score, c * 4);
-        down(out->end_i + lo, d_ei, c * 2);
-        down(out->end_j + lo, d_ej, c * 2);
-        down(tr->start_i + lo, d_si, c * 2);
-        down(tr->start_j + lo, d_sj, c * 2);
-        down(tr->n_cigar + lo, dtr.n_cigar, c * 4);
-        if (cs) down(tr->cigar + lo * cs, dtr.cigar, c * cs * 4);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "traceback: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-int msw_align_batch_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
-                          msw_trace_t* tr, uint64_t chunk_pairs) {
-    return align_batch_trace(ctx, sc, b, out, tr, chunk_pairs, false);
-}
-
-int msw_align_batch_trace_long(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
-                               msw_trace_t* tr, uint64_t chunk_pairs) {
-    return align_batch_trace(ctx, sc, b, out, tr, chunk_pairs, true);
-}
-
 }  // extern "C"
 
 struct msw_plan {
@@ -2453,13 +1918,16 @@ static int check_oriented(const void* strand, const void* oriented, uint32_t ori
     return MSW_OK;
 }
 
+}  // extern "C"
+
 // Both orientations of the device batch b (windows cut) on one stream:
 // reverse complements into `oriented`, forward scoring into `out`, reverse
 // scoring into the stream's own scratch, then the choice per read.  `score`
-// is one scoring pass (both go through msw_align_batch_device).
-using ScorePass = std::function<int(const msw_batch_t*, msw_out_t*)>;
-static int score_both_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out, uint8_t* strand,
-                              uint8_t* oriented, uint32_t oriented_stride, hipStream_t st, const ScorePass& score) {
+// is one scoring pass (both go through msw_align_batch_device).  Shared with
+// the records driver of msw_rt_trace.cpp.
+int msw_detail::score_both_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, msw_out_t* out,
+                                   uint8_t* strand, uint8_t* oriented, uint32_t oriented_stride, hipStream_t st,
+                                   const ScorePass& score) {
     const uint64_t n = b->n_pairs;
     int rc;
     HIP_TRY(msw::launch_revcomp_rows(b->reads, b->read_len, b->read_stride, n, oriented, oriented_stride, st));
@@ -2499,6 +1967,8 @@ static int score_both_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_b
     HIP_TRY(e);
     return MSW_OK;
 }
+
+extern "C" {
 
 int msw_revcomp_device(msw_ctx* ctx, const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride, uint64_t n,
                        uint8_t* out, uint32_t out_stride, void* stream) {
@@ -2547,1627 +2017,6 @@ int msw_align_reads_strands_device(msw_ctx* ctx, const msw_scoring_t* sc, const 
                               [&](const msw_batch_t* pb, msw_out_t* po) {
                                   return score_reads_batch(ctx, sc, pb, po, max_read_len, max_win, stream, st);
                               });
-}
-
-// The body of msw_align_reads_trace (strand == NULL: aln required) and of
-// msw_align_reads_strands (strand != NULL: both orientations are scored, the
-// trace and the pack read the oriented rows, and aln may be NULL for scores
-// alone, with coordinates as sc says).
-static int reads_records(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
-                         msw_out_t* out, msw_aln_t* aln, uint8_t* strand, bool both, uint64_t chunk_pairs,
-                         bool long_pairs = false) {
-    if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
-    msw_scoring_t scc = *sc;
-    if (aln) scc.want_coords = 1;
-    const bool coords = scc.want_coords != 0;
-    Scheme sch;
-    int rc;
-    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
-    if ((aln || !both) && (rc = validate_aln(aln))) return rc;
-    const uint64_t n = b->n_pairs;
-    if (aln) {
-        *aln->n_overflow = 0;
-        aln->cigar_off[0] = 0;
-    }
-    if (n == 0) return MSW_OK;
-    if (!b->reads || !b->read_len || !b->win_pos || !b->win_len) return fail(MSW_E_INVALID, "NULL array in batch");
-    if (both && !strand) return fail(MSW_E_INVALID, "strand is NULL");
-    if (aln) {
-        if (!out || !out->score || !out->end_i || !out->end_j)
-            return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
-    } else if (!out || !out->score || (coords && (!out->end_i || !out->end_j))) {
-        return fail(MSW_E_INVALID, "NULL array in out");
-    }
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
-    uint32_t max_m = 0, max_n = 0;
-    max_u16(b->read_len, n, max_m);
-    max_u16(b->win_len, n, max_n);
-    if (aln) {
-        if ((rc = check_trace_bounds(sch, max_m, max_n, long_pairs))) return rc;
-    } else if ((rc = check_bounds(sch, max_m, max_n))) {
-        return rc;
-    }
-    if (max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    // Simple and synchronous, like msw_align_batch_trace: per chunk upload,
-    // cut, score with coordinates, trace, pack, download.  The trace stride is
-    // exact (no alignment has more ops than rows + columns), so no read
-    // overflows; the packed ops of a chunk are pulled once its total is known.
-    const size_t rs = b->read_stride, ws = std::max<size_t>(16, (max_n + 15u) & ~15u),
-                 cs = aln ? (size_t)max_m + max_n : 0;
-    uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
-    // past the packed range the exact stride reaches 65,534 ops: a chunk's trace rows stay within 1 GiB
-    if (long_pairs && is_long(max_m, max_n))
-        chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, (1ull << 30) / (cs * 4)));
-    auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // [reads | wins | rows u32 | pos i64 | ref i64 | score nc nm i32 | off u32 [c+1] + ovf | 7 x 2 B arrays]
-    const size_t o_wins = up256(chunk * rs), o_rows = up256(o_wins + chunk * ws), o_pos = up256(o_rows + chunk * cs * 4);
-    const size_t o_ref = o_pos + chunk * 8, o_score = o_ref + chunk * 8, o_nc = o_score + chunk * 4,
-                 o_nm = o_nc + chunk * 4, o_off = o_nm + chunk * 4, o_h = o_off + (chunk + 2) * 4;
-    const size_t total_bytes = o_h + chunk * 14 + 256;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total_bytes);
-    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
-    uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
-    uint64_t ops_cap = aln ? chunk * 8 : 1;
-    e = hipMalloc((void**)&d_ops, ops_cap * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
-    }
-    // both strands: the chunk's oriented rows [chunk][ors] and its strand bytes
-    const size_t ors = std::max<size_t>(16, (max_m + 15u) & ~15u);
-    uint8_t *d_or = nullptr, *d_strand = nullptr;
-    if (both) {
-        e = hipMalloc((void**)&d_or, chunk * ors + chunk + 16);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            (void)hipFree(d_ops);
-            return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", chunk * ors + chunk, hipGetErrorString(e));
-        }
-        d_strand = d_or + chunk * ors;
-    }
-    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
-    uint16_t *d_want = d_rl + chunk, *d_wl = d_want + chunk;
-    int16_t *d_ei = reinterpret_cast<int16_t*>(d_wl + chunk), *d_ej = d_ei + chunk, *d_si = d_ej + chunk,
-            *d_sj = d_si + chunk;
-    int64_t *d_pos = reinterpret_cast<int64_t*>(d + o_pos), *d_ref = reinterpret_cast<int64_t*>(d + o_ref);
-    uint32_t* d_off = reinterpret_cast<uint32_t*>(d + o_off);
-    hipStream_t st = ctx->compute;
-    std::vector<uint32_t> off(chunk + 1);
-    uint64_t base = 0;  // ops of the chunks before this one
-    rc = MSW_OK;
-    for (uint64_t lo = 0; lo < n && rc == MSW_OK && e == hipSuccess; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        uint32_t cm = 0, cn = 0;
-        max_u16(b->read_len + lo, c, cm);
-        max_u16(b->win_len + lo, c, cn);
-        auto up = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-        };
-        auto down = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-        };
-        up(d, b->reads + lo * rs, c * rs);
-        up(d_rl, b->read_len + lo, c * 2);
-        up(d_want, b->win_len + lo, c * 2);
-        up(d_pos, b->win_pos + lo, c * 8);
-        if (e != hipSuccess) break;
-        if ((rc = msw_genome_cut_device(ctx, g, d_pos, d_want, c, d + o_wins, (uint32_t)ws, d_wl, st))) break;
-        msw_batch_t db = {d, d + o_wins, d_rl, d_wl, (uint32_t)rs, (uint32_t)ws, c};
-        msw_out_t dout = {reinterpret_cast<int32_t*>(d + o_score), d_ei, d_ej};
-        msw_trace_t dtr = {d_si, d_sj, reinterpret_cast<int32_t*>(d + o_nc), reinterpret_cast<uint32_t*>(d + o_rows),
-                           (uint32_t)cs};
-        if (both) {
-            rc = score_both_strands(ctx, &scc, &db, &dout, d_strand, d_or, (uint32_t)ors, st,
-                                    [&](const msw_batch_t* pb, msw_out_t* po) {
-                                        return msw_align_batch_device(ctx, &scc, pb, po, cm, cn, st);
-                                    });
-            if (rc) break;
-            down(strand + lo, d_strand, c);
-            // from here on the reads are the oriented rows
-            db.reads = d_or;
-            db.read_stride = (uint32_t)ors;
-            if (!aln) {
-                down(out->score + lo, dout.score, c * 4);
-                if (coords) {
-                    down(out->end_i + lo, d_ei, c * 2);
-                    down(out->end_j + lo, d_ej, c * 2);
-                }
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                continue;
-            }
-        } else if ((rc = msw_align_batch_device(ctx, &scc, &db, &dout, cm, cn, st))) {
-            break;
-        }
-        if ((rc = trace_batch_device(ctx, &scc, &db, &dout, &dtr, cm, cn, st, long_pairs))) break;
-        uint64_t total = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            msw_aln_t da = {d_ref, reinterpret_cast<int32_t*>(d + o_nm), d_off, d_ops, ops_cap, d_off + c + 1};
-            if ((rc = msw_aln_pack_device(ctx, g, db.reads, d_rl, db.read_stride, d_pos, c, &dout, &dtr, &da, st)))
-                break;
-            down(off.data(), d_off, (c + 1) * 4);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) break;
-            total = off[c];
-            if (total <= ops_cap) break;
-            (void)hipFree(d_ops);
-            d_ops = nullptr;
-            ops_cap = total;
-            e = hipMalloc((void**)&d_ops, ops_cap * 4);
-        }
-        if (rc || e != hipSuccess) break;
-        down(out->score + lo, dout.score, c * 4);
-        down(out->end_i + lo, d_ei, c * 2);
-        down(out->end_j + lo, d_ej, c * 2);
-        down(aln->ref_pos + lo, d_ref, c * 8);
-        down(aln->nm + lo, d + o_nm, c * 4);
-        const uint64_t room = aln->cigar_cap > base ? aln->cigar_cap - base : 0;
-        down(aln->cigar + base, d_ops, std::min(total, room) * 4);
-        // one prefix sum over the whole batch: this chunk's offsets start at `base`
-        for (uint64_t k = 0; k <= c; ++k) aln->cigar_off[lo + k] = (uint32_t)(base + off[k]);
-        base += total;
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (d_ops) (void)hipFree(d_ops);
-    if (d_or) (void)hipFree(d_or);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "alignment records: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-int msw_align_reads_trace(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
-                          msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
-    return reads_records(ctx, sc, g, b, out, aln, nullptr, false, chunk_pairs);
-}
-
-int msw_align_reads_trace_long(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
-                               const msw_read_batch_t* b, msw_out_t* out, msw_aln_t* aln, uint64_t chunk_pairs) {
-    return reads_records(ctx, sc, g, b, out, aln, nullptr, false, chunk_pairs, true);
-}
-
-int msw_align_reads_strands(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
-                            msw_out_t* out, uint8_t* strand, msw_aln_t* aln, uint64_t chunk_pairs) {
-    return reads_records(ctx, sc, g, b, out, aln, strand, true, chunk_pairs);
-}
-
-// Placing reads (include/msw.h, "Placing reads"; the kernels: msw_seed.hip).
-int msw_index_create(msw_ctx* ctx, const msw_genome* g, uint32_t k, uint32_t max_occ, msw_index** out) {
-    if (!ctx || !out) return fail(MSW_E_INVALID, "ctx/out is NULL");
-    *out = nullptr;
-    if (!g) return fail(MSW_E_INVALID, "genome is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    if (k < 4 || k > 14) return fail(MSW_E_RANGE, "index: k %u outside [4, 14]", k);
-    if (max_occ < 1 || max_occ > msw::kSeedMaxOcc)
-        return fail(MSW_E_RANGE, "index: max_occ %u outside [1, %u]", max_occ, msw::kSeedMaxOcc);
-    if (g->len > msw::kSeedMaxGenome)
-        return fail(MSW_E_RANGE, "index: genome of %llu bases > %llu", (unsigned long long)g->len,
-                    (unsigned long long)msw::kSeedMaxGenome);
-    int rc = set_device(ctx);
-    if (rc) return rc;
-    msw_index* x = new msw_index();
-    x->ctx = ctx;
-    x->device = ctx->device;
-    x->k = k;
-    x->max_occ = max_occ;
-    x->buckets = 1ull << (2 * k);
-    // plain hipMalloc for the temporaries: a one-off, synchronous build
-    uint32_t *tmp = nullptr, *cursor = nullptr, *d_masked = nullptr;
-    hipEvent_t ev[7] = {};
-    hipStream_t st = ctx->compute;
-    const uint64_t tmp_words = msw::index_scan_tmp_words(x->buckets);
-    uint32_t h_masked = 0, total = 0;
-    int err = MSW_OK;
-    hipError_t e = hipMalloc((void**)&x->d_off, (x->buckets + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&tmp, (tmp_words + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_masked, sizeof(uint32_t));
-    if (e != hipSuccess) err = fail(MSW_E_NOMEM, "index: hipMalloc for 4^%u buckets: %s", k, hipGetErrorString(e));
-    for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-    if (e == hipSuccess)
-        e = msw::launch_index_count(g->d_seq, g->len, k, max_occ, x->d_off, d_masked, tmp, ev, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, x->d_off + x->buckets, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_masked, d_masked, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) {
-        x->n_pos = total;
-        x->n_masked = h_masked;
-        e = hipMalloc((void**)&x->d_pos, std::max<uint64_t>(total, 1) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&cursor, x->buckets * sizeof(uint32_t));
-        if (e != hipSuccess)
-            err = fail(MSW_E_NOMEM, "index: hipMalloc for %u positions: %s", total, hipGetErrorString(e));
-    }
-    if (e == hipSuccess) e = msw::launch_index_fill(g->d_seq, g->len, k, x->d_off, cursor, x->d_pos, ev + 4, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) {
-        // ev: [count | mask | scan |] then [fill | sort |]
-        const int a[5] = {0, 1, 2, 4, 5};
-        for (int i = 0; i < 5; ++i) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[a[i]], ev[a[i] + 1]) == hipSuccess) x->build_ms[i] = ms;
-        }
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    for (hipEvent_t v : ev)
-        if (v) (void)hipEventDestroy(v);
-    (void)hipFree(tmp);
-    (void)hipFree(cursor);
-    (void)hipFree(d_masked);
-    if (e != hipSuccess) {
-        msw_index_destroy(x);
-        return err ? err : fail(MSW_E_DEVICE, "index build: %s", hipGetErrorString(e));
-    }
-    *out = x;
-    return MSW_OK;
-}
-
-void msw_index_destroy(msw_index* x) {
-    if (!x) return;
-    (void)hipSetDevice(x->device);
-    if (x->d_off) (void)hipFree(x->d_off);
-    if (x->d_pos) (void)hipFree(x->d_pos);
-    delete x;
-}
-
-int msw_index_info(const msw_index* x, msw_index_info_t* out) {
-    if (!x || !out) return fail(MSW_E_INVALID, "index/out is NULL");
-    out->k = x->k;
-    out->max_occ = x->max_occ;
-    out->n_buckets = x->buckets;
-    out->n_pos = x->n_pos;
-    out->n_masked = x->n_masked;
-    out->off = x->d_off;
-    out->pos = x->d_pos;
-    for (int i = 0; i < 5; ++i) out->build_ms[i] = x->build_ms[i];
-    return MSW_OK;
-}
-
-static int check_seed_params(const msw_seed_params_t* sp, uint32_t max_read_len) {
-    if (!sp) return fail(MSW_E_INVALID, "seed params is NULL");
-    if (sp->band < 1) return fail(MSW_E_RANGE, "seed: band must be >= 1");
-    if (sp->cap < 1 || sp->cap > msw::kSeedMaxCap)
-        return fail(MSW_E_RANGE, "seed: cap %u outside [1, %u]", sp->cap, msw::kSeedMaxCap);
-    if (sp->step < 1) return fail(MSW_E_RANGE, "seed: step must be >= 1");
-    if (sp->min_votes < 1) return fail(MSW_E_RANGE, "seed: min_votes must be >= 1");
-    if (sp->window > (uint32_t)msw::kMaxLongLen)
-        return fail(MSW_E_RANGE, "seed: window %u > %d", sp->window, msw::kMaxLongLen);
-    if (max_read_len > (uint32_t)msw::kMaxLongLen)
-        return fail(MSW_E_RANGE, "seed: max_read_len %u > %d", max_read_len, msw::kMaxLongLen);
-    return MSW_OK;
-}
-
-// The checks of the device seeding calls and the kernel's parameters; *go is
-// false where the call has nothing to launch (n == 0).
-static int seed_device_params(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
-                              const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
-                              uint32_t max_read_len, const msw_seed_params_t* sp, const msw_seed_out_t* out,
-                              msw::SeedParams* pp, bool* go) {
-    msw::SeedParams& p = *pp;
-    *go = false;
-    if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
-    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
-    int rc;
-    if ((rc = check_seed_params(sp, max_read_len))) return rc;
-    if (n == 0) return MSW_OK;
-    if (!reads || !read_len || !out || !out->win_pos || !out->votes || !out->hits || !out->flags)
-        return fail(MSW_E_INVALID, "NULL array");
-    if (read_stride == 0 || max_read_len > read_stride) return fail(MSW_E_INVALID, "max_read_len exceeds read_stride");
-    if (rc_reads && (rc_stride == 0 || max_read_len > rc_stride))
-        return fail(MSW_E_INVALID, "max_read_len exceeds rc_stride");
-    if ((rc = set_device(ctx))) return rc;
-    p.off = x->d_off;
-    p.pos = x->d_pos;
-    p.reads = reads;
-    p.rc_reads = rc_reads;
-    p.read_len = read_len;
-    p.read_stride = read_stride;
-    p.rc_stride = rc_stride;
-    p.n = n;
-    p.k = x->k;
-    p.band = sp->band;
-    p.cap = sp->cap;
-    p.step = sp->step;
-    p.min_votes = sp->min_votes;
-    p.window = sp->window;
-    p.win_pos = out->win_pos;
-    p.votes = out->votes;
-    p.hits = out->hits;
-    p.flags = out->flags;
-    *go = true;
-    return MSW_OK;
-}
-
-int msw_seed_reads_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
-                          const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
-                          uint32_t max_read_len, const msw_seed_params_t* sp, const msw_seed_out_t* out, void* stream) {
-    msw::SeedParams p;
-    bool go;
-    int rc = seed_device_params(ctx, x, reads, rc_reads, read_len, read_stride, rc_stride, n, max_read_len, sp, out, &p,
-                                &go);
-    if (rc || !go) return rc;
-    HIP_TRY(msw::launch_seed_reads(p, call_stream(ctx, stream)));
-    return MSW_OK;
-}
-
-int msw_seed_reads(msw_ctx* ctx, const msw_index* x, const msw_read_batch_t* b, int both,
-                   const msw_seed_params_t* sp, const msw_seed_out_t* out, uint64_t chunk_reads) {
-    if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
-    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
-    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
-    const uint64_t n = b->n_pairs;
-    uint32_t max_m = 0;
-    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array");
-    max_u16(b->read_len, n, max_m);
-    int rc;
-    if ((rc = check_seed_params(sp, max_m))) return rc;
-    if (n == 0) return MSW_OK;
-    if (!b->reads || !out || !out->win_pos || !out->votes || !out->hits || !out->flags)
-        return fail(MSW_E_INVALID, "NULL array");
-    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    // Simple and synchronous, like msw_align_batch_trace: per chunk upload,
-    // reverse complement, seed, download.
-    const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
-    const size_t rs = b->read_stride, os = round16((uint32_t)std::max<uint32_t>(max_m, 1));
-    // [reads | rc rows | win_pos i64 | votes u32 | hits u32 | read_len u16 | flags u8]
-    const size_t o_rc = (chunk * rs + 255) & ~(size_t)255, o_wp = (o_rc + (both ? chunk * os : 0) + 255) & ~(size_t)255;
-    const size_t o_votes = o_wp + chunk * 8, o_hits = o_votes + chunk * 4, o_rl = o_hits + chunk * 4,
-                 o_fl = o_rl + chunk * 2;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, o_fl + chunk + 256);
-    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", o_fl + chunk, hipGetErrorString(e));
-    hipStream_t st = ctx->compute;
-    rc = MSW_OK;
-    for (uint64_t lo = 0; lo < n && rc == MSW_OK; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_rl);
-        msw_seed_out_t dout = {reinterpret_cast<int64_t*>(d + o_wp), reinterpret_cast<uint32_t*>(d + o_votes),
-                               reinterpret_cast<uint32_t*>(d + o_hits), d + o_fl};
-        e = hipMemcpyAsync(d, b->reads + lo * rs, c * rs, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rl, b->read_len + lo, c * 2, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) break;
-        if (both && (rc = msw_revcomp_device(ctx, d, d_rl, (uint32_t)rs, c, d + o_rc, (uint32_t)os, st))) break;
-        if ((rc = msw_seed_reads_device(ctx, x, d, both ? d + o_rc : nullptr, d_rl, (uint32_t)rs, (uint32_t)os, c, max_m,
-                                        sp, &dout, st)))
-            break;
-        e = hipMemcpyAsync(out->win_pos + lo, dout.win_pos, c * 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(out->votes + lo, dout.votes, c * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(out->hits + lo, dout.hits, c * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(out->flags + lo, dout.flags, c, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) break;
-    }
-    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "seeding: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-// Candidates and mapping quality (include/msw.h; the kernels: msw_seed.hip,
-// msw_mapq.hip).
-int msw_seed_candidates_device(msw_ctx* ctx, const msw_index* x, const uint8_t* reads, const uint8_t* rc_reads,
-                               const uint16_t* read_len, uint32_t read_stride, uint32_t rc_stride, uint64_t n,
-                               uint32_t max_read_len, const msw_seed_params_t* sp, uint32_t sep,
-                               const msw_seed_out_t* out, const msw_seed_alt_t* alt, void* stream) {
-    msw::SeedCandParams q;
-    bool go;
-    int rc = seed_device_params(ctx, x, reads, rc_reads, read_len, read_stride, rc_stride, n, max_read_len, sp, out,
-                                &q.s, &go);
-    if (rc) return rc;
-    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
-    if (!go) return MSW_OK;
-    if (!alt || !alt->win_pos || !alt->votes || !alt->flags) return fail(MSW_E_INVALID, "NULL array in alt");
-    q.sep = sep;
-    q.win_pos1 = alt->win_pos;
-    q.votes1 = alt->votes;
-    q.flags1 = alt->flags;
-    HIP_TRY(msw::launch_seed_candidates(q, call_stream(ctx, stream)));
-    return MSW_OK;
-}
-
-int msw_seed_candidates(msw_ctx* ctx, const msw_index* x, const msw_read_batch_t* b, int both,
-                        const msw_seed_params_t* sp, uint32_t sep, const msw_seed_out_t* out,
-                        const msw_seed_alt_t* alt, uint64_t chunk_reads) {
-    if (!ctx || !x) return fail(MSW_E_INVALID, "ctx/index is NULL");
-    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
-    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
-    const uint64_t n = b->n_pairs;
-    uint32_t max_m = 0;
-    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array");
-    max_u16(b->read_len, n, max_m);
-    int rc;
-    if ((rc = check_seed_params(sp, max_m))) return rc;
-    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
-    if (n == 0) return MSW_OK;
-    if (!b->reads || !out || !out->win_pos || !out->votes || !out->hits || !out->flags || !alt || !alt->win_pos ||
-        !alt->votes || !alt->flags)
-        return fail(MSW_E_INVALID, "NULL array");
-    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
-    const size_t rs = b->read_stride, os = round16((uint32_t)std::max<uint32_t>(max_m, 1));
-    // [reads | rc rows | win_pos, win_pos1 i64 | votes, hits, votes1 u32 | read_len u16 | flags, flags1 u8]
-    const size_t o_rc = (chunk * rs + 255) & ~(size_t)255, o_wp = (o_rc + (both ? chunk * os : 0) + 255) & ~(size_t)255;
-    const size_t o_wp1 = o_wp + chunk * 8, o_votes = o_wp1 + chunk * 8, o_hits = o_votes + chunk * 4,
-                 o_votes1 = o_hits + chunk * 4, o_rl = o_votes1 + chunk * 4, o_fl = o_rl + chunk * 2,
-                 o_fl1 = o_fl + chunk;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, o_fl1 + chunk + 256);
-    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", o_fl1 + chunk, hipGetErrorString(e));
-    hipStream_t st = ctx->compute;
-    rc = MSW_OK;
-    for (uint64_t lo = 0; lo < n && rc == MSW_OK; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_rl);
-        msw_seed_out_t dout = {reinterpret_cast<int64_t*>(d + o_wp), reinterpret_cast<uint32_t*>(d + o_votes),
-                               reinterpret_cast<uint32_t*>(d + o_hits), d + o_fl};
-        msw_seed_alt_t dalt = {reinterpret_cast<int64_t*>(d + o_wp1), reinterpret_cast<uint32_t*>(d + o_votes1),
-                               d + o_fl1};
-        e = hipMemcpyAsync(d, b->reads + lo * rs, c * rs, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rl, b->read_len + lo, c * 2, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) break;
-        if (both && (rc = msw_revcomp_device(ctx, d, d_rl, (uint32_t)rs, c, d + o_rc, (uint32_t)os, st))) break;
-        if ((rc = msw_seed_candidates_device(ctx, x, d, both ? d + o_rc : nullptr, d_rl, (uint32_t)rs, (uint32_t)os, c,
-                                             max_m, sp, sep, &dout, &dalt, st)))
-            break;
-        auto down = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-        };
-        down(out->win_pos + lo, dout.win_pos, c * 8);
-        down(out->votes + lo, dout.votes, c * 4);
-        down(out->hits + lo, dout.hits, c * 4);
-        down(out->flags + lo, dout.flags, c);
-        down(alt->win_pos + lo, dalt.win_pos, c * 8);
-        down(alt->votes + lo, dalt.votes, c * 4);
-        down(alt->flags + lo, dalt.flags, c);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) break;
-    }
-    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "candidates: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-int msw_mapq_select_device(msw_ctx* ctx, const msw_cand_t* pr, const msw_cand_t* al, uint32_t oriented_stride,
-                           const uint16_t* read_len, uint64_t n, int32_t match, int32_t* sub_score, uint8_t* mapq,
-                           uint8_t* cand, void* stream) {
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    if (match < 0 || match > 64) return fail(MSW_E_RANGE, "mapq select: match=%d outside [0, 64]", match);
-    if (n == 0) return MSW_OK;
-    if (!pr || !al || !pr->score || !al->score || !pr->win_pos || !al->win_pos || !read_len || !sub_score || !mapq ||
-        !cand)
-        return fail(MSW_E_INVALID, "NULL array");
-    const bool coords = pr->end_i || pr->end_j || al->end_i || al->end_j;
-    if (coords && (!pr->end_i || !pr->end_j || !al->end_i || !al->end_j))
-        return fail(MSW_E_INVALID, "end_i / end_j must be given for both candidates or for neither");
-    const bool rows = pr->strand || pr->oriented || al->strand || al->oriented;
-    if (rows && (!pr->strand || !pr->oriented || !al->strand || !al->oriented))
-        return fail(MSW_E_INVALID, "strand / oriented must be given for both candidates or for neither");
-    if ((pr->win_len != nullptr) != (al->win_len != nullptr))
-        return fail(MSW_E_INVALID, "win_len must be given for both candidates or for neither");
-    if (rows && (((uintptr_t)pr->oriented & 15) != 0 || ((uintptr_t)al->oriented & 15) != 0 || oriented_stride == 0 ||
-                 oriented_stride % 16 != 0))
-        return fail(MSW_E_INVALID, "oriented must be 16-byte aligned and oriented_stride a non-zero multiple of 16");
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "mapq select: too many reads in one call");
-    int rc = set_device(ctx);
-    if (rc) return rc;
-    msw::MapqSelectParams p;
-    p.score = pr->score, p.end_i = pr->end_i, p.end_j = pr->end_j, p.win_len = pr->win_len, p.strand = pr->strand;
-    p.oriented = pr->oriented, p.win_pos = pr->win_pos;
-    p.score_a = al->score, p.end_i_a = al->end_i, p.end_j_a = al->end_j, p.win_len_a = al->win_len;
-    p.strand_a = al->strand, p.oriented_a = al->oriented, p.win_pos_a = al->win_pos;
-    p.read_len = read_len;
-    p.oriented_stride = oriented_stride;
-    p.n = n;
-    p.match = match;
-    p.sub_score = sub_score, p.mapq = mapq, p.cand = cand;
-    HIP_TRY(msw::launch_mapq_select(p, call_stream(ctx, stream)));
-    return MSW_OK;
-}
-
-int msw_map_reads(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_index* x,
-                  const msw_read_batch_t* b, int both, const msw_seed_params_t* sp, uint32_t sep, msw_out_t* out,
-                  uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint64_t chunk_pairs) {
-    if (!ctx || !g || !x) return fail(MSW_E_INVALID, "ctx/genome/index is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
-    if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
-    msw_scoring_t scc = *sc;
-    scc.want_coords = 1;
-    Scheme sch;
-    int rc;
-    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
-    if ((rc = validate_aln(aln))) return rc;
-    const uint64_t n = b->n_pairs;
-    uint32_t max_m = 0;
-    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array in batch");
-    max_u16(b->read_len, n, max_m);
-    if ((rc = check_seed_params(sp, max_m))) return rc;
-    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
-    *aln->n_overflow = 0;
-    aln->cigar_off[0] = 0;
-    if (n == 0) return MSW_OK;
-    if (!b->reads) return fail(MSW_E_INVALID, "NULL array in batch");
-    if (both && !strand) return fail(MSW_E_INVALID, "strand is NULL");
-    if (!out || !out->score || !out->end_i || !out->end_j)
-        return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
-    if (!mq || !mq->mapq || !mq->sub_score || !mq->cand) return fail(MSW_E_INVALID, "NULL array in mapq");
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
-    const uint32_t window = sp->window;
-    const uint32_t max_n = window ? window : std::min<uint32_t>(2u * max_m, (uint32_t)msw::kMaxWinLen);
-    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
-    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    // Simple and synchronous, like msw_align_reads_trace.  Per chunk, all on
-    // the compute stream: upload, (reverse complement,) candidates, the two
-    // scoring calls, the selection, then trace and pack on the winner.
-    const uint64_t chunk = std::min<uint64_t>(n, chunk_pairs ? chunk_pairs : 65536);
-    const size_t rs = b->read_stride, ors = round16(std::max<uint32_t>(max_m, 1)), cs = (size_t)max_m + max_n;
-    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // [reads | rc rows | oriented 0 | oriented 1 | trace rows u32 | 3 x i64 | 8 x 4 B | off u32[c + 2] |
-    //  9 x 2 B | 6 x 1 B]
-    const size_t o_rc = up256(chunk * rs), o_or0 = up256(o_rc + (both ? chunk * ors : 0)),
-                 o_or1 = up256(o_or0 + (both ? chunk * ors : 0)), o_rows = up256(o_or1 + (both ? chunk * ors : 0)),
-                 o_q = up256(o_rows + chunk * cs * 4), o_w = o_q + chunk * 24, o_off = o_w + chunk * 32,
-                 o_h = o_off + (chunk + 2) * 4, o_b = up256(o_h + chunk * 18);
-    const size_t total_bytes = o_b + chunk * 6 + 256;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total_bytes);
-    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
-    uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
-    uint64_t ops_cap = chunk * 8;
-    e = hipMalloc((void**)&d_ops, ops_cap * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
-    }
-    int64_t *d_wp0 = reinterpret_cast<int64_t*>(d + o_q), *d_wp1 = d_wp0 + chunk, *d_ref = d_wp1 + chunk;
-    int32_t* w32 = reinterpret_cast<int32_t*>(d + o_w);
-    int32_t *d_s0 = w32, *d_s1 = w32 + chunk, *d_sub = w32 + 2 * chunk, *d_nc = w32 + 3 * chunk, *d_nm = w32 + 4 * chunk;
-    uint32_t *d_votes = reinterpret_cast<uint32_t*>(w32 + 5 * chunk), *d_hits = d_votes + chunk,
-             *d_votes1 = d_hits + chunk;
-    uint32_t* d_off = reinterpret_cast<uint32_t*>(d + o_off);
-    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_h);
-    uint16_t *d_wl0 = d_rl + chunk, *d_wl1 = d_wl0 + chunk;
-    int16_t *d_ei0 = reinterpret_cast<int16_t*>(d_wl1 + chunk), *d_ej0 = d_ei0 + chunk, *d_ei1 = d_ej0 + chunk,
-            *d_ej1 = d_ei1 + chunk, *d_si = d_ej1 + chunk, *d_sj = d_si + chunk;
-    uint8_t *d_fl = d + o_b, *d_fl1 = d_fl + chunk, *d_st0 = d_fl1 + chunk, *d_st1 = d_st0 + chunk,
-            *d_mapq = d_st1 + chunk, *d_cand = d_mapq + chunk;
-    uint8_t *d_rc = d + o_rc, *d_or0 = d + o_or0, *d_or1 = d + o_or1;
-    hipStream_t st = ctx->compute;
-    std::vector<uint32_t> off(chunk + 1);
-    uint64_t base = 0;  // ops of the chunks before this one
-    rc = MSW_OK;
-    for (uint64_t lo = 0; lo < n && rc == MSW_OK && e == hipSuccess; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        auto up = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-        };
-        auto down = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-        };
-        up(d, b->reads + lo * rs, c * rs);
-        up(d_rl, b->read_len + lo, c * 2);
-        if (e != hipSuccess) break;
-        if (both && (rc = msw_revcomp_device(ctx, d, d_rl, (uint32_t)rs, c, d_rc, (uint32_t)ors, st))) break;
-        const msw_seed_out_t so = {d_wp0, d_votes, d_hits, d_fl};
-        const msw_seed_alt_t sa = {d_wp1, d_votes1, d_fl1};
-        if ((rc = msw_seed_candidates_device(ctx, x, d, both ? d_rc : nullptr, d_rl, (uint32_t)rs, (uint32_t)ors, c,
-                                             max_m, sp, sep, &so, &sa, st)))
-            break;
-        msw_out_t o0 = {d_s0, d_ei0, d_ej0}, o1 = {d_s1, d_ei1, d_ej1};
-        if (both) {
-            if ((rc = msw_align_reads_strands_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp0, c, window, max_m, &o0,
-                                                     d_wl0, d_st0, d_or0, (uint32_t)ors, st)) ||
-                (rc = msw_align_reads_strands_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp1, c, window, max_m, &o1,
-                                                     d_wl1, d_st1, d_or1, (uint32_t)ors, st)))
-                break;
-        } else if ((rc = msw_align_reads_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp0, c, window, max_m, &o0,
-                                                d_wl0, st)) ||
-                   (rc = msw_align_reads_device(ctx, &scc, g, d, d_rl, (uint32_t)rs, d_wp1, c, window, max_m, &o1,
-                                                d_wl1, st))) {
-            break;
-        }
-        const msw_cand_t c0 = {d_s0, d_ei0, d_ej0, d_wl0, both ? d_st0 : nullptr, both ? d_or0 : nullptr, d_wp0};
-        const msw_cand_t c1 = {d_s1, d_ei1, d_ej1, d_wl1, both ? d_st1 : nullptr, both ? d_or1 : nullptr, d_wp1};
-        if ((rc = msw_mapq_select_device(ctx, &c0, &c1, (uint32_t)ors, d_rl, c, scc.match, d_sub, d_mapq, d_cand, st)))
-            break;
-        // from here on the reads are the winner's oriented rows
-        const uint8_t* rows = both ? d_or0 : d;
-        const uint32_t rstride = both ? (uint32_t)ors : (uint32_t)rs;
-        msw_trace_t dtr = {d_si, d_sj, d_nc, reinterpret_cast<uint32_t*>(d + o_rows), (uint32_t)cs};
-        if ((rc = msw_trace_reads_device(ctx, &scc, g, rows, d_rl, rstride, d_wp0, c, window, max_m, &o0, &dtr, st)))
-            break;
-        uint64_t total = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            msw_aln_t da = {d_ref, d_nm, d_off, d_ops, ops_cap, d_off + c + 1};
-            if ((rc = msw_aln_pack_device(ctx, g, rows, d_rl, rstride, d_wp0, c, &o0, &dtr, &da, st))) break;
-            down(off.data(), d_off, (c + 1) * 4);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) break;
-            total = off[c];
-            if (total <= ops_cap) break;
-            (void)hipFree(d_ops);
-            d_ops = nullptr;
-            ops_cap = total;
-            if (hipMalloc((void**)&d_ops, ops_cap * 4) != hipSuccess) {
-                d_ops = nullptr;
-                rc = fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the packed ops", (unsigned long long)ops_cap * 4);
-                break;
-            }
-        }
-        if (rc || e != hipSuccess) break;
-        down(out->score + lo, d_s0, c * 4);
-        down(out->end_i + lo, d_ei0, c * 2);
-        down(out->end_j + lo, d_ej0, c * 2);
-        if (both) down(strand + lo, d_st0, c);
-        down(mq->mapq + lo, d_mapq, c);
-        down(mq->sub_score + lo, d_sub, c * 4);
-        down(mq->cand + lo, d_cand, c);
-        down(aln->ref_pos + lo, d_ref, c * 8);
-        down(aln->nm + lo, d_nm, c * 4);
-        const uint64_t room = aln->cigar_cap > base ? aln->cigar_cap - base : 0;
-        down(aln->cigar + base, d_ops, std::min(total, room) * 4);
-        for (uint64_t k = 0; k <= c; ++k) aln->cigar_off[lo + k] = (uint32_t)(base + off[k]);
-        base += total;
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (d_ops) (void)hipFree(d_ops);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "map reads: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-// Pairs (include/msw.h, "Pairs"; the kernels: msw_pair.hip).
-void msw_pair_params_default(msw_pair_params_t* p) {
-    if (!p) return;
-    *p = msw_pair_params_t{1u, 1000u, 17, 60, 16u};
-}
-
-static bool rescue_on(const msw_pair_params_t& q) { return q.rescue_min_score != 0 || q.slack != 0; }
-
-static int check_pair_params(const msw_pair_params_t* q, msw::PairRule* r) {
-    if (!q) return fail(MSW_E_INVALID, "pair params is NULL");
-    if (q->min_ins < 1 || q->min_ins > q->max_ins || q->max_ins > 4095)
-        return fail(MSW_E_RANGE, "pairs: insert bounds [%u, %u] outside 1 <= min <= max <= 4095", q->min_ins,
-                    q->max_ins);
-    if (q->pair_bonus < 0 || q->rescue_min_score < 0)
-        return fail(MSW_E_RANGE, "pairs: pair_bonus / rescue_min_score below 0");
-    if (q->slack > 4096) return fail(MSW_E_RANGE, "pairs: slack %u > 4096", q->slack);
-    *r = msw::PairRule{(int32_t)q->min_ins, (int32_t)q->max_ins, q->pair_bonus, q->rescue_min_score, (int32_t)q->slack};
-    return MSW_OK;
-}
-
-// W_r of the contract; 0 when rescue is off
-static int rescue_window(const msw_pair_params_t& q, uint32_t max_read_len, uint32_t* w) {
-    *w = 0;
-    if (!rescue_on(q)) return MSW_OK;
-    const uint64_t wr = (uint64_t)q.max_ins - q.min_ins + max_read_len + 2ull * q.slack;
-    if (wr > (uint64_t)msw::kMaxWinLen)
-        return fail(MSW_E_RANGE, "pairs: rescue window %llu > %d", (unsigned long long)wr, msw::kMaxWinLen);
-    *w = (uint32_t)wr;
-    return MSW_OK;
-}
-
-static msw::PairCand pair_cand(const msw_cand_t& c) {
-    return msw::PairCand{c.score, c.end_i, c.end_j, c.win_len, c.strand, c.oriented, c.win_pos};
-}
-
-int msw_pair_plan_device(msw_ctx* ctx, const msw_cand_t* cand, const uint16_t* read_len, uint64_t n_pairs,
-                         const msw_pair_params_t* params, int64_t* rescue_pos, void* stream) {
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    msw::PairPlanParams p;
-    int rc;
-    if ((rc = check_pair_params(params, &p.rule))) return rc;
-    if (n_pairs == 0) return MSW_OK;
-    if (!cand || !read_len || !rescue_pos) return fail(MSW_E_INVALID, "NULL array");
-    for (int k = 0; k < 2; ++k) {
-        if (!cand[k].score || !cand[k].end_i || !cand[k].end_j || !cand[k].strand || !cand[k].win_pos)
-            return fail(MSW_E_INVALID, "NULL array in candidate %d", k);
-        p.c[k] = pair_cand(cand[k]);
-    }
-    if (n_pairs > 0x3FFFFFFFull) return fail(MSW_E_RANGE, "pair plan: too many pairs in one call");
-    if ((rc = set_device(ctx))) return rc;
-    p.read_len = read_len;
-    p.n_pairs = n_pairs;
-    p.rescue_pos = rescue_pos;
-    HIP_TRY(msw::launch_pair_plan(p, call_stream(ctx, stream)));
-    return MSW_OK;
-}
-
-int msw_pair_select_device(msw_ctx* ctx, const msw_cand_t* cand, uint32_t K, uint32_t oriented_stride,
-                           const uint16_t* read_len, uint64_t n_pairs, int32_t match,
-                           const msw_pair_params_t* params, int32_t* sub_score, uint8_t* mapq, uint8_t* cand_out,
-                           uint8_t* pair_flags, int32_t* tlen, void* stream) {
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    msw::PairSelectParams p;
-    memset(&p, 0, sizeof(p));
-    int rc;
-    if ((rc = check_pair_params(params, &p.rule))) return rc;
-    if (match < 0 || match > 64) return fail(MSW_E_RANGE, "pair select: match=%d outside [0, 64]", match);
-    if (K != 2 && K != 3) return fail(MSW_E_INVALID, "pair select: K=%u is neither 2 nor 3", K);
-    if (n_pairs == 0) return MSW_OK;
-    if (!cand || !read_len || !sub_score || !mapq || !cand_out || !pair_flags || !tlen)
-        return fail(MSW_E_INVALID, "NULL array");
-    for (uint32_t k = 0; k < K; ++k) {
-        const msw_cand_t& c = cand[k];
-        if (!c.score || !c.end_i || !c.end_j || !c.win_len || !c.strand || !c.oriented || !c.win_pos)
-            return fail(MSW_E_INVALID, "NULL array in candidate %u", k);
-        if (((uintptr_t)c.oriented & 15) != 0 || oriented_stride == 0 || oriented_stride % 16 != 0)
-            return fail(MSW_E_INVALID, "oriented must be 16-byte aligned and oriented_stride a non-zero multiple of 16");
-        p.c[k] = pair_cand(c);
-    }
-    if (n_pairs > 0x3FFFFFFFull) return fail(MSW_E_RANGE, "pair select: too many pairs in one call");
-    if ((rc = set_device(ctx))) return rc;
-    p.k = K;
-    p.read_len = read_len;
-    p.oriented_stride = oriented_stride;
-    p.n_pairs = n_pairs;
-    p.match = match;
-    p.sub_score = sub_score, p.mapq = mapq, p.cand = cand_out, p.pair_flags = pair_flags, p.tlen = tlen;
-    HIP_TRY(msw::launch_pair_select(p, call_stream(ctx, stream)));
-    return MSW_OK;
-}
-
-int msw_insert_hist_device(msw_ctx* ctx, const int32_t* tlen, const uint8_t* mapq, uint64_t n_pairs,
-                           uint32_t min_mapq, uint32_t* hist, void* stream) {
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    if (min_mapq > 255) return fail(MSW_E_RANGE, "insert hist: min_mapq %u > 255", min_mapq);
-    if (n_pairs == 0) return MSW_OK;
-    if (!tlen || !mapq || !hist) return fail(MSW_E_INVALID, "NULL array");
-    if (n_pairs > 0x3FFFFFFFull) return fail(MSW_E_RANGE, "insert hist: too many pairs in one call");
-    int rc = set_device(ctx);
-    if (rc) return rc;
-    HIP_TRY(msw::launch_insert_hist(tlen, mapq, n_pairs, min_mapq, hist, call_stream(ctx, stream)));
-    return MSW_OK;
-}
-
-int msw_insert_bounds(const uint32_t* hist, uint32_t* lo, uint32_t* hi, uint32_t* median) {
-    if (!hist || !lo || !hi || !median) return fail(MSW_E_INVALID, "NULL argument");
-    uint64_t total = 0;
-    for (uint32_t k = 0; k < msw::kInsertBins; ++k) total += hist[k];
-    if (total == 0) return fail(MSW_E_INVALID, "insert bounds: the histogram is empty");
-    const uint64_t need[3] = {(total + 3) / 4, (total + 1) / 2, (3 * total + 3) / 4};
-    uint32_t q[3] = {0, 0, 0};
-    uint64_t cum = 0;
-    int at = 0;
-    for (uint32_t k = 0; k < msw::kInsertBins && at < 3; ++k) {
-        cum += hist[k];
-        while (at < 3 && cum >= need[at]) q[at++] = k;
-    }
-    const int64_t iqr = (int64_t)q[2] - q[0];
-    *lo = (uint32_t)std::max<int64_t>(1, (int64_t)q[0] - 3 * iqr);
-    *hi = (uint32_t)std::min<int64_t>(4095, (int64_t)q[2] + 3 * iqr);
-    *median = q[1];
-    return MSW_OK;
-}
-
-int msw_map_pairs(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_index* x,
-                  const msw_read_batch_t* b, const msw_seed_params_t* sp, uint32_t sep, const msw_pair_params_t* pp,
-                  msw_out_t* out, uint8_t* strand, msw_aln_t* aln, const msw_mapq_t* mq, uint8_t* pair_flags,
-                  int32_t* tlen, uint32_t* hist, uint64_t chunk_pairs) {
-    if (!ctx || !g || !x) return fail(MSW_E_INVALID, "ctx/genome/index is NULL");
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    if (x->ctx != ctx) return fail(MSW_E_INVALID, "index belongs to another context");
-    if (!sc || !b) return fail(MSW_E_INVALID, "scoring/batch is NULL");
-    msw_scoring_t scc = *sc;
-    scc.want_coords = 1;
-    Scheme sch;
-    int rc;
-    if ((rc = make_scheme(&scc, ctx->opt, &sch))) return rc;
-    if ((rc = validate_aln(aln))) return rc;
-    const uint64_t n = b->n_pairs;  // rows
-    if (n & 1) return fail(MSW_E_INVALID, "pairs: %llu rows is an odd number", (unsigned long long)n);
-    uint32_t max_m = 0;
-    if (n && !b->read_len) return fail(MSW_E_INVALID, "NULL array in batch");
-    max_u16(b->read_len, n, max_m);
-    if ((rc = check_seed_params(sp, max_m))) return rc;
-    if (sep != 0 && sep < sp->band) return fail(MSW_E_RANGE, "candidates: sep %u is below band %u", sep, sp->band);
-    msw::PairRule rule;
-    uint32_t wr = 0;
-    if ((rc = check_pair_params(pp, &rule)) || (rc = rescue_window(*pp, max_m, &wr))) return rc;
-    const bool rescue = wr != 0;
-    *aln->n_overflow = 0;
-    aln->cigar_off[0] = 0;
-    if (n == 0) return MSW_OK;
-    if (!b->reads) return fail(MSW_E_INVALID, "NULL array in batch");
-    if (!strand) return fail(MSW_E_INVALID, "strand is NULL");
-    if (!out || !out->score || !out->end_i || !out->end_j)
-        return fail(MSW_E_INVALID, "traceback needs score / end_i / end_j");
-    if (!mq || !mq->mapq || !mq->sub_score || !mq->cand) return fail(MSW_E_INVALID, "NULL array in mapq");
-    if (!pair_flags || !tlen) return fail(MSW_E_INVALID, "pair_flags / tlen is NULL");
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "traceback: n_pairs > 2^31-1 in one call");
-    const uint32_t window = sp->window;
-    const uint32_t max_n = window ? window : std::min<uint32_t>(2u * max_m, (uint32_t)msw::kMaxWinLen);
-    if ((rc = check_trace_bounds(max_m, max_n))) return rc;
-    if (b->read_stride == 0 || max_m > b->read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    // The trace reads a window only up to the best cell's column, so its
-    // window argument is a bound and one call serves both window lengths: with
-    // rescue it is the larger of the two, without it what msw_map_reads passes.
-    const uint32_t trace_window = rescue ? std::max(max_n, wr) : window;
-    const uint32_t trace_n = rescue ? trace_window : max_n;
-    // msw_map_reads with `both`, on whole pairs, with the plan and the rescue
-    // scoring between the two candidate scorings and the select.
-    const uint64_t chunk = std::min<uint64_t>(n, 2 * (chunk_pairs ? chunk_pairs : 32768));
-    const size_t rs = b->read_stride, ors = round16(std::max<uint32_t>(max_m, 1)), cs = (size_t)max_m + trace_n;
-    size_t total_bytes = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = total_bytes;
-        total_bytes = (at + bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_reads = take(chunk * rs), o_rc = take(chunk * ors), o_rows = take(chunk * cs * 4),
-                 o_ref = take(chunk * 8), o_sub = take(chunk * 4), o_nc = take(chunk * 4), o_nm = take(chunk * 4),
-                 o_votes = take(chunk * 4), o_hits = take(chunk * 4), o_votes1 = take(chunk * 4),
-                 o_off = take((chunk + 2) * 4), o_rl = take(chunk * 2), o_si = take(chunk * 2), o_sj = take(chunk * 2),
-                 o_fl = take(chunk), o_fl1 = take(chunk), o_mapq = take(chunk), o_cand = take(chunk),
-                 o_pf = take(chunk / 2), o_tlen = take(chunk / 2 * 4), o_hist = take(msw::kInsertBins * 4);
-    struct CandAt {
-        size_t wp, s, ei, ej, wl, st, rows;
-    } ca[3];
-    for (int k = 0; k < (rescue ? 3 : 2); ++k)
-        ca[k] = CandAt{take(chunk * 8), take(chunk * 4), take(chunk * 2), take(chunk * 2),
-                       take(chunk * 2), take(chunk),     take(chunk * ors)};
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total_bytes);
-    if (e != hipSuccess) return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total_bytes, hipGetErrorString(e));
-    uint32_t* d_ops = nullptr;  // the chunk's packed ops; grown to a chunk's total when it does not fit
-    uint64_t ops_cap = chunk * 8;
-    e = hipMalloc((void**)&d_ops, ops_cap * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)ops_cap * 4, hipGetErrorString(e));
-    }
-    msw_cand_t cand[3];
-    msw_out_t co[3];
-    for (int k = 0; k < (rescue ? 3 : 2); ++k) {
-        cand[k] = msw_cand_t{reinterpret_cast<int32_t*>(d + ca[k].s),   reinterpret_cast<int16_t*>(d + ca[k].ei),
-                             reinterpret_cast<int16_t*>(d + ca[k].ej),  reinterpret_cast<uint16_t*>(d + ca[k].wl),
-                             d + ca[k].st,                              d + ca[k].rows,
-                             reinterpret_cast<int64_t*>(d + ca[k].wp)};
-        co[k] = msw_out_t{cand[k].score, cand[k].end_i, cand[k].end_j};
-    }
-    uint8_t *d_reads = d + o_reads, *d_rc = d + o_rc, *d_fl = d + o_fl, *d_fl1 = d + o_fl1, *d_mapq = d + o_mapq,
-            *d_cand = d + o_cand, *d_pf = d + o_pf;
-    int64_t* d_ref = reinterpret_cast<int64_t*>(d + o_ref);
-    int32_t *d_sub = reinterpret_cast<int32_t*>(d + o_sub), *d_nc = reinterpret_cast<int32_t*>(d + o_nc),
-            *d_nm = reinterpret_cast<int32_t*>(d + o_nm), *d_tlen = reinterpret_cast<int32_t*>(d + o_tlen);
-    uint32_t *d_votes = reinterpret_cast<uint32_t*>(d + o_votes), *d_hits = reinterpret_cast<uint32_t*>(d + o_hits),
-             *d_votes1 = reinterpret_cast<uint32_t*>(d + o_votes1), *d_off = reinterpret_cast<uint32_t*>(d + o_off),
-             *d_hist = reinterpret_cast<uint32_t*>(d + o_hist);
-    uint16_t* d_rl = reinterpret_cast<uint16_t*>(d + o_rl);
-    int16_t *d_si = reinterpret_cast<int16_t*>(d + o_si), *d_sj = reinterpret_cast<int16_t*>(d + o_sj);
-    hipStream_t st = ctx->compute;
-    std::vector<uint32_t> off(chunk + 1);
-    uint64_t base = 0;  // ops of the chunks before this one
-    rc = MSW_OK;
-    if (hist) e = hipMemsetAsync(d_hist, 0, msw::kInsertBins * 4, st);
-    for (uint64_t lo = 0; lo < n && rc == MSW_OK && e == hipSuccess; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        auto up = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-        };
-        auto down = [&](void* dst, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-        };
-        up(d_reads, b->reads + lo * rs, c * rs);
-        up(d_rl, b->read_len + lo, c * 2);
-        if (e != hipSuccess) break;
-        if ((rc = msw_revcomp_device(ctx, d_reads, d_rl, (uint32_t)rs, c, d_rc, (uint32_t)ors, st))) break;
-        const msw_seed_out_t so = {cand[0].win_pos, d_votes, d_hits, d_fl};
-        const msw_seed_alt_t sa = {cand[1].win_pos, d_votes1, d_fl1};
-        if ((rc = msw_seed_candidates_device(ctx, x, d_reads, d_rc, d_rl, (uint32_t)rs, (uint32_t)ors, c, max_m, sp,
-                                             sep, &so, &sa, st)))
-            break;
-        for (int k = 0; k < 2 && rc == MSW_OK; ++k)
-            rc = msw_align_reads_strands_device(ctx, &scc, g, d_reads, d_rl, (uint32_t)rs, cand[k].win_pos, c, window,
-                                                max_m, &co[k], cand[k].win_len, cand[k].strand, cand[k].oriented,
-                                                (uint32_t)ors, st);
-        if (rc) break;
-        if (rescue) {
-            // every row is scored at W_r; a row that is not to be rescued is an empty window
-            if ((rc = msw_pair_plan_device(ctx, cand, d_rl, c / 2, pp, cand[2].win_pos, st)) ||
-                (rc = msw_align_reads_strands_device(ctx, &scc, g, d_reads, d_rl, (uint32_t)rs, cand[2].win_pos, c, wr,
-                                                     max_m, &co[2], cand[2].win_len, cand[2].strand, cand[2].oriented,
-                                                     (uint32_t)ors, st)))
-                break;
-        }
-        if ((rc = msw_pair_select_device(ctx, cand, rescue ? 3u : 2u, (uint32_t)ors, d_rl, c / 2, scc.match, pp, d_sub,
-                                         d_mapq, d_cand, d_pf, d_tlen, st)))
-            break;
-        if (hist && (rc = msw_insert_hist_device(ctx, d_tlen, d_mapq, c / 2, 0u, d_hist, st))) break;
-        // from here on the reads are the winners' oriented rows, in candidate 0's arrays
-        const uint8_t* rows = cand[0].oriented;
-        const int64_t* d_wp = cand[0].win_pos;
-        msw_trace_t dtr = {d_si, d_sj, d_nc, reinterpret_cast<uint32_t*>(d + o_rows), (uint32_t)cs};
-        if ((rc = msw_trace_reads_device(ctx, &scc, g, rows, d_rl, (uint32_t)ors, d_wp, c, trace_window, max_m, &co[0],
-                                         &dtr, st)))
-            break;
-        uint64_t total = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            msw_aln_t da = {d_ref, d_nm, d_off, d_ops, ops_cap, d_off + c + 1};
-            if ((rc = msw_aln_pack_device(ctx, g, rows, d_rl, (uint32_t)ors, d_wp, c, &co[0], &dtr, &da, st))) break;
-            down(off.data(), d_off, (c + 1) * 4);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) break;
-            total = off[c];
-            if (total <= ops_cap) break;
-            (void)hipFree(d_ops);
-            d_ops = nullptr;
-            ops_cap = total;
-            if (hipMalloc((void**)&d_ops, ops_cap * 4) != hipSuccess) {
-                d_ops = nullptr;
-                rc = fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the packed ops", (unsigned long long)ops_cap * 4);
-                break;
-            }
-        }
-        if (rc || e != hipSuccess) break;
-        down(out->score + lo, cand[0].score, c * 4);
-        down(out->end_i + lo, cand[0].end_i, c * 2);
-        down(out->end_j + lo, cand[0].end_j, c * 2);
-        down(strand + lo, cand[0].strand, c);
-        down(mq->mapq + lo, d_mapq, c);
-        down(mq->sub_score + lo, d_sub, c * 4);
-        down(mq->cand + lo, d_cand, c);
-        down(pair_flags + lo / 2, d_pf, c / 2);
-        down(tlen + lo / 2, d_tlen, c / 2 * 4);
-        down(aln->ref_pos + lo, d_ref, c * 8);
-        down(aln->nm + lo, d_nm, c * 4);
-        const uint64_t room = aln->cigar_cap > base ? aln->cigar_cap - base : 0;
-        down(aln->cigar + base, d_ops, std::min(total, room) * 4);
-        for (uint64_t k = 0; k <= c; ++k) aln->cigar_off[lo + k] = (uint32_t)(base + off[k]);
-        base += total;
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (hist && rc == MSW_OK && e == hipSuccess) {
-        std::vector<uint32_t> h(msw::kInsertBins);
-        e = hipMemcpyAsync(h.data(), d_hist, msw::kInsertBins * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess)
-            for (uint32_t k = 0; k < msw::kInsertBins; ++k) hist[k] += h[k];
-    }
-    if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (d_ops) (void)hipFree(d_ops);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "map pairs: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-// Pileup (include/msw.h, "Pileup"; the kernels: msw_pileup.hip).
-struct msw_pileup {
-    const msw_ctx* ctx = nullptr;  // identity only
-    int device = 0;
-    // one allocation: counts [glen][8] | the read counters' slots + stats u64[4] + the low-quality column counter's
-    // slots | d_all [glen + 1] | d_rev [glen + 1] | mism [glen] | the scan's block sums
-    // and with MSW_PILEUP_QSUM: | qsum [glen][4] | d_q [glen + 1] | qmis [glen]
-    uint8_t* d_state = nullptr;
-    msw::PileupParams p{};         // the state's part; an add fills in its batch
-    uint32_t flags = 0;
-    msw::PileupQsum qs{};          // the state's part (d_q, qmis, qsum, lowq), with MSW_PILEUP_QSUM
-    unsigned long long* d_stats = nullptr;
-    unsigned long long* d_lowq = nullptr;  // PileupQual::lowq
-    uint32_t* d_scan_tmp = nullptr;
-    bool finished = false;
-    hipEvent_t fin = nullptr;      // recorded behind the fold
-};
-
-static int check_pileup(const msw_ctx* ctx, const msw_pileup* pile) {
-    if (!ctx || !pile) return fail(MSW_E_INVALID, "ctx/pileup is NULL");
-    if (pile->ctx != ctx) return fail(MSW_E_INVALID, "pileup belongs to another context");
-    return MSW_OK;
-}
-
-int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
-    return msw_pileup_create_ex(ctx, g, 0, out);
-}
-
-int msw_pileup_create_ex(msw_ctx* ctx, const msw_genome* g, uint32_t flags, msw_pileup** out) {
-    if (!ctx || !g || !out) return fail(MSW_E_INVALID, "ctx/genome/out is NULL");
-    *out = nullptr;
-    if (flags & ~MSW_PILEUP_QSUM) return fail(MSW_E_INVALID, "pileup create: unknown flag in 0x%x", flags);
-    const bool qsum = (flags & MSW_PILEUP_QSUM) != 0;
-    if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
-    int rc = set_device(ctx);
-    if (rc) return rc;
-    const uint64_t glen = g->len;
-    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    const uint64_t read_words = (uint64_t)msw::kPileupReadSlots * 2 * msw::kPileupReadSlotWords;
-    const uint64_t lowq_words = (uint64_t)msw::kPileupReadSlots * msw::kPileupReadSlotWords;
-    const uint64_t o_reads = (glen * 32 + 127) & ~(uint64_t)127, o_all = o_reads + (read_words + 16 + lowq_words) * 8,
-                   o_rev = o_all + up16((glen + 1) * 4),
-                   o_mism = o_rev + up16((glen + 1) * 4), o_tmp = o_mism + up16(glen * 4),
-                   o_qsum = o_tmp + up16(msw::pileup_scan_tmp_words(glen) * 4) + 16,
-                   o_dq = o_qsum + (qsum ? glen * 16 : 0), o_qmis = o_dq + (qsum ? up16((glen + 1) * 4) : 0),
-                   total = o_qmis + (qsum ? up16(glen * 4) + 16 : 0);
-    msw_pileup* pile = new msw_pileup();
-    pile->ctx = ctx;
-    pile->flags = flags;
-    pile->device = ctx->device;
-    hipError_t e = hipMalloc((void**)&pile->d_state, total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete pile;
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the pileup of %llu bases: %s", (unsigned long long)total,
-                    (unsigned long long)glen, hipGetErrorString(e));
-    }
-    msw::PileupParams& p = pile->p;
-    p.genome = g->d_seq;
-    p.glen = glen;
-    p.counts = reinterpret_cast<uint32_t*>(pile->d_state);
-    const bool planes = ctx->opt.pileup_planes;
-    p.pos_mul = planes ? 1 : 8;
-    p.ch_mul = planes ? glen : 1;
-    p.reads = reinterpret_cast<unsigned long long*>(pile->d_state + o_reads);
-    pile->d_stats = p.reads + read_words;
-    pile->d_lowq = pile->d_stats + 16;
-    p.d_all = reinterpret_cast<uint32_t*>(pile->d_state + o_all);
-    p.d_rev = reinterpret_cast<uint32_t*>(pile->d_state + o_rev);
-    p.mism = reinterpret_cast<uint32_t*>(pile->d_state + o_mism);
-    pile->d_scan_tmp = reinterpret_cast<uint32_t*>(pile->d_state + o_tmp);
-    if (qsum) {
-        pile->qs.lowq = pile->d_lowq;
-        pile->qs.qsum = reinterpret_cast<uint32_t*>(pile->d_state + o_qsum);
-        pile->qs.d_q = reinterpret_cast<uint32_t*>(pile->d_state + o_dq);
-        pile->qs.qmis = reinterpret_cast<uint32_t*>(pile->d_state + o_qmis);
-    }
-    // the kernels' code object, loaded here rather than inside the first add (HIP loads a module on first use)
-    (void)msw::pileup_blocks_per_cu();
-    e = hipEventCreateWithFlags(&pile->fin, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemsetAsync(pile->d_state, 0, total, ctx->compute);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->compute);
-    if (e != hipSuccess) {
-        msw_pileup_destroy(pile);
-        return fail(MSW_E_DEVICE, "pileup state: %s", hipGetErrorString(e));
-    }
-    *out = pile;
-    return MSW_OK;
-}
-
-void msw_pileup_destroy(msw_pileup* pile) {
-    if (!pile) return;
-    (void)hipSetDevice(pile->device);
-    if (pile->fin) (void)hipEventDestroy(pile->fin);
-    if (pile->d_state) (void)hipFree(pile->d_state);
-    delete pile;
-}
-
-// a MSW_PILEUP_QSUM pileup takes no add without qualities
-static int check_pileup_qsum_add(const msw_ctx* ctx, const msw_pileup* pile, const uint8_t* quals) {
-    if (ctx && pile && pile->ctx == ctx && (pile->flags & MSW_PILEUP_QSUM) && !quals)
-        return fail(MSW_E_INVALID, "pileup add: a MSW_PILEUP_QSUM pileup needs quals (msw_pileup_add_qual*)");
-    return MSW_OK;
-}
-
-// the checks both add forms share; *go = false: nothing to do
-static int check_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
-                            uint32_t row_stride, uint64_t n, const msw_aln_t* aln, uint32_t min_mapq, bool* go) {
-    *go = false;
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (!aln) return fail(MSW_E_INVALID, "aln is NULL");
-    if (pile->finished) return fail(MSW_E_INVALID, "pileup is finished: it takes no more reads");
-    if (n > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "pileup add: n > 2^31-1 in one call");
-    if (min_mapq > 255u) return fail(MSW_E_RANGE, "pileup add: min_mapq %u > 255", min_mapq);
-    if (n == 0) return MSW_OK;
-    if (!rows || !read_len) return fail(MSW_E_INVALID, "NULL array");
-    if (row_stride == 0) return fail(MSW_E_INVALID, "row_stride is 0");
-    if (!aln->ref_pos || !aln->nm || !aln->cigar_off) return fail(MSW_E_INVALID, "NULL array in aln");
-    if (aln->cigar_cap && !aln->cigar) return fail(MSW_E_INVALID, "cigar is NULL with cigar_cap > 0");
-    *go = true;
-    return MSW_OK;
-}
-
-int msw_pileup_add_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
-                          uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
-                          const uint8_t* mapq, uint32_t min_mapq, void* stream) {
-    return msw_pileup_add_qual_device(ctx, pile, rows, read_len, row_stride, n, aln, strand, mapq, min_mapq, nullptr, 0,
-                                      0, stream);
-}
-
-int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* rows, const uint16_t* read_len,
-                               uint32_t row_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
-                               const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
-                               uint32_t min_baseq, void* stream) {
-    if (min_baseq > 93u) return fail(MSW_E_RANGE, "pileup add: min_baseq %u > 93", min_baseq);
-    int rc;
-    bool go;
-    if ((rc = check_pileup_qsum_add(ctx, pile, quals))) return rc;
-    if ((rc = check_pileup_add(ctx, pile, rows, read_len, row_stride, n, aln, min_mapq, &go)) || !go) return rc;
-    if ((rc = set_device(ctx))) return rc;
-    msw::PileupParams p = pile->p;
-    p.rows = rows;
-    p.read_len = read_len;
-    p.row_stride = row_stride;
-    p.n = n;
-    p.ref_pos = aln->ref_pos;
-    p.nm = aln->nm;
-    p.cigar_off = aln->cigar_off;
-    p.cigar = aln->cigar;
-    p.cigar_cap = aln->cigar_cap;
-    p.strand = strand;
-    p.mapq = mapq;
-    p.min_mapq = min_mapq;
-    if (pile->flags & MSW_PILEUP_QSUM) {
-        msw::PileupQsum q = pile->qs;
-        q.quals = quals;
-        q.qual_stride = qual_stride;
-        q.min_baseq = min_baseq;
-        HIP_TRY(msw::launch_pileup_add_qsum(p, q, call_stream(ctx, stream)));
-    } else if (quals && min_baseq) {  // else the plain add
-        const msw::PileupQual q{quals, qual_stride, min_baseq, pile->d_lowq};
-        HIP_TRY(msw::launch_pileup_add_qual(p, q, call_stream(ctx, stream)));
-    } else {
-        HIP_TRY(msw::launch_pileup_add(p, call_stream(ctx, stream)));
-    }
-    return MSW_OK;
-}
-
-int msw_pileup_add(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
-                   uint64_t n, const msw_aln_t* aln, const uint8_t* strand, const uint8_t* mapq, uint32_t min_mapq,
-                   uint64_t chunk_reads) {
-    return msw_pileup_add_qual(ctx, pile, reads, read_len, read_stride, n, aln, strand, mapq, min_mapq, nullptr, 0, 0,
-                               chunk_reads);
-}
-
-int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, const uint16_t* read_len,
-                        uint32_t read_stride, uint64_t n, const msw_aln_t* aln, const uint8_t* strand,
-                        const uint8_t* mapq, uint32_t min_mapq, const uint8_t* quals, uint32_t qual_stride,
-                        uint32_t min_baseq, uint64_t chunk_reads) {
-    if (min_baseq > 93u) return fail(MSW_E_RANGE, "pileup add: min_baseq %u > 93", min_baseq);
-    int rc;
-    bool go;
-    if ((rc = check_pileup_qsum_add(ctx, pile, quals))) return rc;
-    const bool qsum = ctx && pile && pile->ctx == ctx && (pile->flags & MSW_PILEUP_QSUM);
-    if (min_baseq == 0 && !qsum) quals = nullptr;  // the plain add
-    if (!quals) qual_stride = 0;
-    if ((rc = check_pileup_add(ctx, pile, reads, read_len, read_stride, n, aln, min_mapq, &go)) || !go) return rc;
-    const uint64_t chunk = std::min<uint64_t>(n, chunk_reads ? chunk_reads : 65536);
-    // the offsets decide what is uploaded: they must be a prefix sum inside the capacity
-    uint64_t max_ops = 0;
-    for (uint64_t lo = 0; lo < n; lo += chunk) {
-        const uint64_t hi = std::min(n, lo + chunk);
-        for (uint64_t k = lo; k < hi; ++k)
-            if (aln->cigar_off[k + 1] < aln->cigar_off[k])
-                return fail(MSW_E_INVALID, "pileup add: cigar_off decreases at read %llu", (unsigned long long)k);
-        max_ops = std::max<uint64_t>(max_ops, aln->cigar_off[hi] - aln->cigar_off[lo]);
-    }
-    if (aln->cigar_off[n] > aln->cigar_cap)
-        return fail(MSW_E_INVALID, "pileup add: the reads hold %u ops, cigar_cap is %llu", aln->cigar_off[n],
-                    (unsigned long long)aln->cigar_cap);
-    for (uint64_t k = 0; k < n; ++k)
-        if (read_len[k] > read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
-    if ((rc = set_device(ctx))) return rc;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    // [ref i64 | nm i32 | off u32 [c + 1] | ops | rlen u16 | strand | mapq | rows | quals]
-    const size_t rs = read_stride, qs = qual_stride;
-    const size_t o_nm = chunk * 8, o_off = o_nm + chunk * 4, o_ops = up16(o_off + (chunk + 1) * 4),
-                 o_rl = up16(o_ops + max_ops * 4), o_st = up16(o_rl + chunk * 2), o_mq = up16(o_st + chunk),
-                 o_rows = up16(o_mq + chunk), o_q = up16(o_rows + chunk * rs),
-                 total = o_q + chunk * qs + 16;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MSW_E_NOMEM, "hipMalloc(%zu B): %s", total, hipGetErrorString(e));
-    }
-    hipStream_t st = ctx->compute;
-    msw::PileupParams p = pile->p;
-    p.rows = d + o_rows;
-    p.read_len = reinterpret_cast<const uint16_t*>(d + o_rl);
-    p.row_stride = rs;
-    p.ref_pos = reinterpret_cast<const int64_t*>(d);
-    p.nm = reinterpret_cast<const int32_t*>(d + o_nm);
-    p.cigar_off = reinterpret_cast<const uint32_t*>(d + o_off);
-    p.cigar = reinterpret_cast<const uint32_t*>(d + o_ops);
-    p.cigar_cap = aln->cigar_cap;
-    p.strand = strand ? d + o_st : nullptr;
-    p.mapq = mapq ? d + o_mq : nullptr;
-    p.min_mapq = min_mapq;
-    p.orient = strand ? 1u : 0u;
-    const msw::PileupQual q{d + o_q, qual_stride, min_baseq, pile->d_lowq};
-    msw::PileupQsum qq = pile->qs;
-    qq.quals = q.quals;
-    qq.qual_stride = qual_stride;
-    qq.min_baseq = min_baseq;
-    for (uint64_t lo = 0; lo < n && e == hipSuccess; lo += chunk) {
-        const uint64_t c = std::min(chunk, n - lo);
-        auto up = [&](size_t at, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, st);
-        };
-        const uint32_t o0 = aln->cigar_off[lo], o1 = aln->cigar_off[lo + c];
-        up(0, aln->ref_pos + lo, c * 8);
-        up(o_nm, aln->nm + lo, c * 4);
-        up(o_off, aln->cigar_off + lo, (c + 1) * 4);
-        up(o_ops, aln->cigar + o0, (size_t)(o1 - o0) * 4);
-        up(o_rl, read_len + lo, c * 2);
-        if (strand) up(o_st, strand + lo, c);
-        if (mapq) up(o_mq, mapq + lo, c);
-        up(o_rows, reads + lo * rs, c * rs);
-        if (quals) up(o_q, quals + lo * qs, c * qs);
-        p.n = c;
-        p.cigar_base = o0;
-        if (e == hipSuccess)
-            e = qsum ? msw::launch_pileup_add_qsum(p, qq, st)
-                     : quals ? msw::launch_pileup_add_qual(p, q, st) : msw::launch_pileup_add(p, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // the buffers are the next chunk's
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup add: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-int msw_pileup_finish(msw_ctx* ctx, msw_pileup* pile, void* stream) {
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (pile->finished) return MSW_OK;
-    if ((rc = set_device(ctx))) return rc;
-    hipStream_t st = call_stream(ctx, stream);
-    if (pile->flags & MSW_PILEUP_QSUM) HIP_TRY(msw::launch_pileup_finish_qsum(pile->p, pile->qs, pile->d_scan_tmp, st));
-    else HIP_TRY(msw::launch_pileup_finish(pile->p, pile->d_scan_tmp, st));
-    HIP_TRY(hipEventRecord(pile->fin, st));
-    pile->finished = true;
-    return MSW_OK;
-}
-
-int msw_pileup_counts_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** counts, uint64_t* pos_stride,
-                             uint64_t* ch_stride) {
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (!counts || !pos_stride || !ch_stride) return fail(MSW_E_INVALID, "NULL output");
-    *counts = pile->p.counts;
-    *pos_stride = pile->p.pos_mul;
-    *ch_stride = pile->p.ch_mul;
-    return MSW_OK;
-}
-
-int msw_pileup_counts(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out) {
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (!pile->finished) return fail(MSW_E_INVALID, "pileup counts before msw_pileup_finish");
-    const uint64_t glen = pile->p.glen;
-    if (glen == 0) return MSW_OK;
-    if (!host_out) return fail(MSW_E_INVALID, "host_out is NULL");
-    if ((rc = set_device(ctx))) return rc;
-    HIP_TRY(hipEventSynchronize(pile->fin));
-    hipStream_t st = ctx->compute;
-    if (pile->p.pos_mul == 8) {
-        HIP_TRY(hipMemcpyAsync(host_out, pile->p.counts, glen * 32, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return MSW_OK;
-    }
-    // planes: rows are made on the GPU, a bounce buffer of them at a time
-    const uint64_t step = std::min<uint64_t>(glen, 1u << 20);
-    uint32_t* bounce = nullptr;
-    hipError_t e = hipMalloc((void**)&bounce, step * 32);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)step * 32, hipGetErrorString(e));
-    }
-    for (uint64_t pos = 0; pos < glen && e == hipSuccess; pos += step) {
-        const uint64_t m = std::min(step, glen - pos);
-        e = msw::launch_pileup_rows(pile->p, pos, m, bounce, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(host_out + pos * 8, bounce, m * 32, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    (void)hipFree(bounce);
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup counts: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_pileup_summary_t* out) {
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (!out) return fail(MSW_E_INVALID, "out is NULL");
-    if (min_depth == 0) return fail(MSW_E_INVALID, "pileup summary: min_depth is 0");
-    if (!pile->finished) return fail(MSW_E_INVALID, "pileup summary before msw_pileup_finish");
-    if ((rc = set_device(ctx))) return rc;
-    HIP_TRY(hipEventSynchronize(pile->fin));
-    hipStream_t st = ctx->compute;
-    HIP_TRY(msw::launch_pileup_summary(pile->p, min_depth, pile->d_stats, st));
-    // the read counters' slots, then covered, depth_sum, minority_ref, max_depth
-    constexpr uint32_t kWords = msw::kPileupReadSlots * 2 * msw::kPileupReadSlotWords;
-    std::vector<unsigned long long> h(kWords + 4);
-    HIP_TRY(hipMemcpyAsync(h.data(), pile->p.reads, h.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memset(out, 0, sizeof(*out));
-    for (uint32_t s = 0; s < msw::kPileupReadSlots; ++s) {
-        out->reads_used += h[(s * 2 + 0) * msw::kPileupReadSlotWords];
-        out->reads_skipped += h[(s * 2 + 1) * msw::kPileupReadSlotWords];
-    }
-    out->covered = h[kWords];
-    out->depth_sum = h[kWords + 1];
-    out->minority_ref = h[kWords + 2];
-    out->max_depth = (uint32_t)h[kWords + 3];
-    return MSW_OK;
-}
-
-int msw_pileup_lowq_columns(msw_ctx* ctx, msw_pileup* pile, uint64_t* out) {
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (!out) return fail(MSW_E_INVALID, "out is NULL");
-    if ((rc = set_device(ctx))) return rc;
-    // adds may have been enqueued on any stream: wait for all of them
-    HIP_TRY(hipDeviceSynchronize());
-    constexpr uint32_t kWords = msw::kPileupReadSlots * msw::kPileupReadSlotWords;
-    std::vector<unsigned long long> h(kWords);
-    HIP_TRY(hipMemcpy(h.data(), pile->d_lowq, h.size() * 8, hipMemcpyDeviceToHost));
-    *out = 0;
-    for (uint32_t s = 0; s < msw::kPileupReadSlots; ++s) *out += h[s * msw::kPileupReadSlotWords];
-    return MSW_OK;
-}
-
-// Quality sums (include/msw.h, "Quality sums and weighted genotypes").
-static int check_pileup_qsum(const msw_ctx* ctx, const msw_pileup* pile, const char* what) {
-    int rc;
-    if ((rc = check_pileup(ctx, pile))) return rc;
-    if (!(pile->flags & MSW_PILEUP_QSUM)) return fail(MSW_E_INVALID, "%s: the pileup was created without MSW_PILEUP_QSUM", what);
-    return MSW_OK;
-}
-
-int msw_pileup_qsums_device(msw_ctx* ctx, msw_pileup* pile, const uint32_t** qsums, uint64_t* pos_stride,
-                            uint64_t* ch_stride) {
-    int rc;
-    if ((rc = check_pileup_qsum(ctx, pile, "pileup qsums"))) return rc;
-    if (!qsums || !pos_stride || !ch_stride) return fail(MSW_E_INVALID, "NULL output");
-    *qsums = pile->qs.qsum;
-    *pos_stride = 4;
-    *ch_stride = 1;
-    return MSW_OK;
-}
-
-int msw_pileup_qsums(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out) {
-    int rc;
-    if ((rc = check_pileup_qsum(ctx, pile, "pileup qsums"))) return rc;
-    if (!pile->finished) return fail(MSW_E_INVALID, "pileup qsums before msw_pileup_finish");
-    const uint64_t glen = pile->p.glen;
-    if (glen == 0) return MSW_OK;
-    if (!host_out) return fail(MSW_E_INVALID, "host_out is NULL");
-    if ((rc = set_device(ctx))) return rc;
-    HIP_TRY(hipEventSynchronize(pile->fin));
-    hipStream_t st = ctx->compute;
-    HIP_TRY(hipMemcpyAsync(host_out, pile->qs.qsum, glen * 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return MSW_OK;
-}
-
-// Variants (include/msw.h, "Variants"; the kernels: msw_call.hip).
-void msw_call_qparams_default(msw_call_qparams_t* q) {
-    if (!q) return;
-    *q = msw_call_qparams_t{100, 477};
-}
-
-static int check_call_qparams(const msw_call_qparams_t* qparams, msw::CallParams* p) {
-    msw_call_qparams_t q;
-    if (qparams) q = *qparams;
-    else msw_call_qparams_default(&q);
-    if (q.q_scale > 65535u || q.q_third > 65535u)
-        return fail(MSW_E_INVALID, "call qparams: q_scale or q_third above 65535");
-    p->q_scale = q.q_scale;
-    p->q_third = q.q_third;
-    return MSW_OK;
-}
-
-void msw_call_params_default(msw_call_params_t* q) {
-    if (!q) return;
-    *q = msw_call_params_t{4, 2, 200, 20, 4, 2477, 304, 3000, 3301};
-}
-
-static int check_call_params(const msw_call_params_t* params, msw_call_params_t* q) {
-    if (params) *q = *params;
-    else msw_call_params_default(q);
-    if (q->q_hit > 65535u || q->q_miss > 65535u || q->q_het > 65535u)
-        return fail(MSW_E_INVALID, "call params: a q_* cost above 65535");
-    if (q->min_depth == 0) return fail(MSW_E_INVALID, "call params: min_depth is 0");
-    if (q->min_alt_permille > 1000u) return fail(MSW_E_INVALID, "call params: min_alt_permille %u > 1000", q->min_alt_permille);
-    return MSW_OK;
-}
-
-static_assert(sizeof(msw_variant_t) == 48, "msw_variant_t is 48 bytes, in memory and in the .var file");
-
-// both device forms; weighted: the call of "Quality sums and weighted genotypes"
-static int pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, bool weighted,
-                              const msw_call_qparams_t* qparams, msw_variant_t* out_dev, uint64_t cap,
-                              uint64_t* n_total_dev, void* stream) {
-    int rc;
-    msw::CallParams p{};
-    if ((rc = weighted ? check_pileup_qsum(ctx, pile, "pileup call") : check_pileup(ctx, pile))) return rc;
-    if ((rc = check_call_params(params, &p.q))) return rc;
-    if (weighted && (rc = check_call_qparams(qparams, &p))) return rc;
-    if (!pile->finished) return fail(MSW_E_INVALID, "pileup call before msw_pileup_finish");
-    if (cap && !out_dev) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
-    if (pile->p.glen > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "pileup call: genome above 2^31-1 bases");
-    if ((rc = set_device(ctx))) return rc;
-    hipStream_t st = call_stream(ctx, stream);
-    // behind the fold, whatever stream it ran on
-    HIP_TRY(hipStreamWaitEvent(st, pile->fin, 0));
-    p.genome = pile->p.genome;
-    p.counts = pile->p.counts;
-    p.pos_mul = pile->p.pos_mul;
-    p.ch_mul = pile->p.ch_mul;
-    p.m = p.rows = pile->p.glen;
-    p.out = out_dev;
-    p.cap = cap;
-    p.n_total = reinterpret_cast<unsigned long long*>(n_total_dev);
-    p.qsum = weighted ? pile->qs.qsum : nullptr;
-    HIP_TRY(hipMallocAsync((void**)&p.tile_off, msw::call_tmp_words(p.m) * sizeof(uint32_t), st));
-    hipError_t e = msw::launch_call(p, st);
-    const hipError_t ef = hipFreeAsync(p.tile_off, st);
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup call: %s", hipGetErrorString(e));
-    return MSW_OK;
-}
-
-int msw_pileup_call_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_dev,
-                           uint64_t cap, uint64_t* n_total_dev, void* stream) {
-    return pileup_call_device(ctx, pile, params, false, nullptr, out_dev, cap, n_total_dev, stream);
-}
-
-int msw_pileup_call_qual_device(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params,
-                                const msw_call_qparams_t* qparams, msw_variant_t* out_dev, uint64_t cap,
-                                uint64_t* n_total_dev, void* stream) {
-    return pileup_call_device(ctx, pile, params, true, qparams, out_dev, cap, n_total_dev, stream);
-}
-
-static int pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, bool weighted,
-                       const msw_call_qparams_t* qparams, msw_variant_t* out_host, uint64_t cap, uint64_t* n_total) {
-    int rc;
-    if ((rc = weighted ? check_pileup_qsum(ctx, pile, "pileup call") : check_pileup(ctx, pile))) return rc;
-    if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
-    if (cap && !out_host) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
-    if ((rc = set_device(ctx))) return rc;
-    // at most two records per base
-    const uint64_t dcap = std::min<uint64_t>(cap, pile->p.glen * 2);
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, 16 + dcap * sizeof(msw_variant_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)(16 + dcap * sizeof(msw_variant_t)),
-                    hipGetErrorString(e));
-    }
-    hipStream_t st = ctx->compute;
-    msw_variant_t* d_out = reinterpret_cast<msw_variant_t*>(d + 16);
-    rc = pileup_call_device(ctx, pile, params, weighted, qparams, dcap ? d_out : nullptr, dcap,
-                            reinterpret_cast<uint64_t*>(d), st);
-    if (rc == MSW_OK) {
-        uint64_t total = 0;
-        e = hipMemcpyAsync(&total, d, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        const uint64_t have = std::min(total, dcap);
-        if (e == hipSuccess && have) e = hipMemcpyAsync(out_host, d_out, have * sizeof(msw_variant_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(MSW_E_DEVICE, "pileup call: %s", hipGetErrorString(e));
-        else *n_total = total;
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    (void)hipFree(d);
-    return rc;
-}
-
-int msw_pileup_call(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params, msw_variant_t* out_host,
-                    uint64_t cap, uint64_t* n_total) {
-    return pileup_call(ctx, pile, params, false, nullptr, out_host, cap, n_total);
-}
-
-int msw_pileup_call_qual(msw_ctx* ctx, msw_pileup* pile, const msw_call_params_t* params,
-                         const msw_call_qparams_t* qparams, msw_variant_t* out_host, uint64_t cap, uint64_t* n_total) {
-    return pileup_call(ctx, pile, params, true, qparams, out_host, cap, n_total);
-}
-
-static int call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
-                       bool weighted, const uint32_t* qsums_host, const msw_call_params_t* params,
-                       const msw_call_qparams_t* qparams, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
-                       uint64_t* n_total) {
-    int rc;
-    msw::CallParams p{};
-    if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
-    if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
-    if ((rc = check_call_params(params, &p.q))) return rc;
-    if (weighted && (rc = check_call_qparams(qparams, &p))) return rc;
-    if (cap && !out_host) return fail(MSW_E_INVALID, "out is NULL with cap > 0");
-    if (chunk_pos > (1ull << 24)) return fail(MSW_E_RANGE, "call counts: chunk_pos above 2^24");
-    *n_total = 0;
-    if (glen == 0) return MSW_OK;
-    if (!genome_host || !counts_host || (weighted && !qsums_host)) return fail(MSW_E_INVALID, "NULL array");
-    if ((rc = set_device(ctx))) return rc;
-    const uint64_t chunk = std::min<uint64_t>(glen, chunk_pos ? chunk_pos : 1ull << 20);
-    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    // [rows of chunk + 1 positions | genome bytes | total u64 | tile offsets and scan words | weighted: rows of four]
-    const uint64_t o_gen = (chunk + 1) * 32, o_tot = o_gen + up16(chunk), o_tile = o_tot + 16,
-                   o_qsum = o_tile + up16(msw::call_tmp_words(chunk) * 4), bytes = o_qsum + (weighted ? chunk * 16 : 0);
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MSW_E_NOMEM, "hipMalloc(%llu B): %s", (unsigned long long)bytes, hipGetErrorString(e));
-    }
-    hipStream_t st = ctx->compute;
-    p.counts = reinterpret_cast<const uint32_t*>(d);
-    p.genome = d + o_gen;
-    p.pos_mul = 8;
-    p.ch_mul = 1;
-    p.n_total = reinterpret_cast<unsigned long long*>(d + o_tot);
-    p.tile_off = reinterpret_cast<uint32_t*>(d + o_tile);
-    p.qsum = weighted ? reinterpret_cast<const uint32_t*>(d + o_qsum) : nullptr;
-    msw_variant_t* d_out = nullptr;  // grows to the largest chunk's records that still fit cap
-    uint64_t d_out_cap = 0, total = 0, written = 0;
-    bool nomem = false;
-    for (uint64_t lo = 0; lo < glen && e == hipSuccess; lo += chunk) {
-        const uint64_t m = std::min(chunk, glen - lo);
-        p.m = m;
-        p.rows = lo + m < glen ? m + 1 : m;  // the look-ahead row
-        p.pos0 = lo;
-        p.out = nullptr;
-        p.cap = 0;
-        e = hipMemcpyAsync(d, counts_host + lo * 8, p.rows * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_gen, genome_host + lo, m, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && weighted)
-            e = hipMemcpyAsync(d + o_qsum, qsums_host + lo * 4, m * 16, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = msw::launch_call_count(p, st);
-        if (e == hipSuccess) e = msw::launch_call_scan(p, st);
-        uint64_t t = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&t, p.n_total, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) break;
-        const uint64_t want = std::min(t, cap - written);
-        if (want) {
-            if (want > d_out_cap) {
-                if (d_out) (void)hipFree(d_out);
-                d_out = nullptr;
-                d_out_cap = 0;
-                e = hipMalloc((void**)&d_out, want * sizeof(msw_variant_t));
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    nomem = true;
-                    break;
-                }
-                d_out_cap = want;
-            }
-            p.out = d_out;
-            p.cap = want;
-            e = msw::launch_call_emit(p, st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(out_host + written, d_out, want * sizeof(msw_variant_t), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);  // the buffers are the next chunk's
-            written += want;
-        }
-        total += t;
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    if (d_out) (void)hipFree(d_out);
-    (void)hipFree(d);
-    if (nomem) return fail(MSW_E_NOMEM, "hipMalloc for a chunk's records: %s", hipGetErrorString(e));
-    if (e != hipSuccess) return fail(MSW_E_DEVICE, "call counts: %s", hipGetErrorString(e));
-    *n_total = total;
-    return MSW_OK;
-}
-
-int msw_call_counts(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
-                    const msw_call_params_t* params, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
-                    uint64_t* n_total) {
-    return call_counts(ctx, genome_host, glen, counts_host, false, nullptr, params, nullptr, chunk_pos, out_host, cap,
-                       n_total);
-}
-
-int msw_call_counts_qual(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen, const uint32_t* counts_host,
-                         const uint32_t* qsums_host, const msw_call_params_t* params,
-                         const msw_call_qparams_t* qparams, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
-                         uint64_t* n_total) {
-    return call_counts(ctx, genome_host, glen, counts_host, true, qsums_host, params, qparams, chunk_pos, out_host, cap,
-                       n_total);
 }
 
 int msw_memcpy_d2h_async(msw_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {

@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 import aln_oracle as ao
+import mapq_oracle as mo
+import seed_oracle as sd
 import traceback_oracle as tbo
 
 pytestmark = pytest.mark.gpu
@@ -505,6 +507,114 @@ def test_host_call_and_wrapper(gpu_ctx, scheme):
                                                 ctypes.byref(batch), ctypes.byref(out), ctypes.byref(aln), 16))
     assert np.array_equal(off, d_off) and int(ovf[0]) == 0 and (cig[5:] == 0xDEADBEEF).all()
     assert np.array_equal(ref, d_ref) and np.array_equal(nm, d_nm)
+    genome.close()
+
+
+REGROW_CHUNK = 16          # rows per chunk: the drivers' ops buffer starts at 8 ops per row
+_REGROW = {}
+
+
+def regrow_case(scheme):
+    """40 reads of about 100 bases, each with six single-base indels 14 bases
+    apart (11 ops or more), then 24 exact ones (one op).  With the oracle's
+    records against the windows the mapping calls use (twice the read)."""
+    if scheme in _REGROW:
+        return _REGROW[scheme]
+    g = the_genome()
+    rng = np.random.default_rng(5)
+    reads, pos = [], []
+    for k in range(64):
+        a = 300 * k + int(rng.integers(50, 250))
+        r = [int(x) for x in g[a:a + 100]]
+        if k < 40:
+            for at in (84, 70, 56, 42, 28, 14):          # from the end: earlier places do not move
+                if rng.integers(0, 2):
+                    del r[at]
+                else:
+                    r[at:at] = [int(ACGT[(int(np.where(ACGT == r[at])[0][0]) + 1) % 4])]   # not the next base
+        reads.append(np.array(r, np.uint8))
+        pos.append(a - 20 - (k % 3))
+    pos = np.array(pos, np.int64)
+    want = np.array([2 * len(r) for r in reads], np.uint16)
+    recs = [ao.record(reads[k], ao.window_of(g, int(pos[k]), int(want[k])), int(pos[k]), *SCHEMES[scheme])
+            for k in range(64)]
+    _REGROW[scheme] = (g, reads, pos, want, recs)
+    return _REGROW[scheme]
+
+
+def revcomp_rows(R, rl):
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    out = np.zeros_like(R)
+    for p, m in enumerate(rl):
+        out[p, :m] = comp[R[p, :m][::-1]]
+    return out
+
+
+@pytest.mark.parametrize("scheme", ["lin", "aff"])
+def test_ops_buffer_regrow(gpu_ctx, scheme):
+    """Chunks whose packed ops exceed the drivers' first ops buffer (8 per row)
+    are packed again into a buffer of the chunk's size, and later chunks fit:
+    msw_align_reads_trace == the oracle, the raw call under a small cigar_cap
+    as in test_host_call_and_wrapper, and msw_map_reads / msw_map_pairs ==
+    msw_align_reads_trace at the loci and orientations they chose."""
+    from mini_parallel_amd import PairParams, _lib
+    g, reads, pos, want, recs = regrow_case(scheme)
+    n = len(reads)
+    # the branch is taken, and left again: from the oracle alone
+    per_chunk = [sum(len(r.ops) for r in recs[lo:lo + REGROW_CHUNK]) for lo in range(0, n, REGROW_CHUNK)]
+    assert all(len(r.ops) >= 11 for r in recs[:40]) and all(len(r.ops) == 1 for r in recs[40:])
+    first_over = next(k for k, t in enumerate(per_chunk) if t > 8 * REGROW_CHUNK)
+    assert any(t <= 8 * REGROW_CHUNK for t in per_chunk[first_over + 1:]), per_chunk
+    R, rl = pad_reads(reads, 128)
+    sc = scoring(SCHEMES[scheme], False)
+    genome = gpu_ctx.load_genome(g)
+    s, ei, ej, ref, nm, cigars = gpu_ctx.align_reads_trace(genome, R, rl, pos, want, sc, chunk_pairs=REGROW_CHUNK)
+    off = np.concatenate([[0], np.cumsum(cigars.n_cigar)]).astype(np.uint32)
+    ops = np.concatenate(list(cigars) + [np.full(1, 0x5EADBEEF, np.uint32)])
+    check_records((s, ei, ej), (ref, nm, off, ops, 0), recs, rl)
+    # raw: cigar_cap below the total
+    total = int(off[-1])
+    cap = 8 * REGROW_CHUNK + 5
+    assert cap < total
+    r_s, r_ei, r_ej = np.zeros(n, np.int32), np.zeros(n, np.int16), np.zeros(n, np.int16)
+    r_ref, r_nm, r_off = np.zeros(n, np.int64), np.zeros(n, np.int32), np.full(n + 1, 7, np.uint32)
+    cig = np.full(cap + GUARD, 0xDEADBEEF, np.uint32)
+    ovf = np.full(1, 9, np.uint32)
+    batch = _lib.ReadBatchT(R.ctypes.data, rl.ctypes.data, R.shape[1], pos.ctypes.data, want.ctypes.data, n)
+    out = _lib.OutT(r_s.ctypes.data, r_ei.ctypes.data, r_ej.ctypes.data)
+    aln = _lib.AlnT(r_ref.ctypes.data, r_nm.ctypes.data, r_off.ctypes.data, cig.ctypes.data, cap, ovf.ctypes.data)
+    _lib.check(_lib.lib().msw_align_reads_trace(gpu_ctx.handle, ctypes.byref(scoring(SCHEMES[scheme]).to_c()), genome.handle,
+                                                ctypes.byref(batch), ctypes.byref(out), ctypes.byref(aln), REGROW_CHUNK))
+    assert np.array_equal(r_off, off) and int(ovf[0]) == 0 and (cig[cap:] == 0xDEADBEEF).all()
+    assert np.array_equal(cig[:cap], ops[:cap])
+    assert np.array_equal(r_ref, ref) and np.array_equal(r_nm, nm)
+    # the mapping drivers: the same helper behind other stage lists; where the seeds put the reads, the chunks
+    # exceed the buffer as above (the oracle's mapping, on the CPU)
+    m_recs, _, _ = mo.map_records(g.tobytes(), sd.Index(g.tobytes(), 10, 64), [r.tobytes() for r in reads],
+                                  SCHEMES[scheme], True)
+    m_chunk = [sum(len(r.ops) for r in m_recs[lo:lo + REGROW_CHUNK]) for lo in range(0, n, REGROW_CHUNK)]
+    assert m_chunk[0] > 8 * REGROW_CHUNK and min(m_chunk[1:]) <= 8 * REGROW_CHUNK, m_chunk
+    index = gpu_ctx.build_index(genome, k=10)
+    (wp0, _, _, _), (wp1, _, _) = gpu_ctx.seed_candidates(index, R, rl)
+    rc_R = revcomp_rows(R, rl)
+    mapped = gpu_ctx.map_reads(genome, index, R, rl, sc, chunk_pairs=REGROW_CHUNK, mapq=True)
+    paired = gpu_ctx.map_pairs(genome, index, R, rl, sc, PairParams(rescue_min_score=0, slack=0),
+                               chunk_pairs=REGROW_CHUNK // 2)
+    for p, r in enumerate(m_recs):
+        assert (int(mapped[0][p]), int(mapped[3][p]), int(mapped[4][p]), [int(o) for o in mapped[6][p]]) == (
+            r.score, r.strand, r.ref_pos, r.ops), p
+    for got in (mapped, paired):
+        m_s, m_ei, m_ej, strand, m_ref, m_nm, m_cig, _, _, cand = got[:10]
+        assert set(np.unique(cand)) <= {0, 1}
+        wp = np.where(cand == 1, wp1, wp0)
+        rows = np.where(strand[:, None] == 1, rc_R, R)
+        t_s, t_ei, t_ej, t_ref, t_nm, t_cig = gpu_ctx.align_reads_trace(genome, rows, rl, wp, want, sc)
+        assert np.array_equal(m_s, t_s) and np.array_equal(m_ei, t_ei) and np.array_equal(m_ej, t_ej)
+        assert np.array_equal(m_ref, t_ref) and np.array_equal(m_nm, t_nm)
+        assert np.array_equal(m_cig.n_cigar, t_cig.n_cigar)
+        assert np.array_equal(np.concatenate(list(m_cig)), np.concatenate(list(t_cig)))
+    index.close()
     genome.close()
 
 

@@ -7,7 +7,8 @@ cd "$(dirname "$0")/../mini_parallel_amd/csrc"
 NAME=$1; shift
 OUT=../../tools/_variants
 mkdir -p "$OUT/o_$NAME"
-make -s msw_runtime.o msw_fastq.o msw_gfastq.o >/dev/null
+HOST="msw_runtime.o msw_rt_trace.o msw_rt_map.o msw_rt_pileup.o msw_fastq.o msw_gfastq.o"  # the Makefile's RTOBJS and readers
+make -s $HOST >/dev/null
 pids=()
 for f in *.hip; do  # every kernel unit of the Makefile's KOBJS and GZOBJS
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -falign-loops=32 --offload-arch=gfx950 -I../../include "$@" -c "$f" \
@@ -15,6 +16,6 @@ for f in *.hip; do  # every kernel unit of the Makefile's KOBJS and GZOBJS
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -lz -lpthread -ldl "$OUT/o_$NAME"/*.o msw_runtime.o msw_fastq.o msw_gfastq.o \
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -lz -lpthread -ldl "$OUT/o_$NAME"/*.o $HOST \
     -o "$OUT/libmsw_$NAME.so"
 rm -rf "$OUT/o_$NAME"
