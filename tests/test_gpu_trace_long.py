@@ -2,6 +2,9 @@
 strips of 384 rows, checkpointed) against the full-matrix restatement
 (tests/traceback_oracle.py) and tests/aln_oracle.py: score, end, start and op
 list, exactly.  Every output array of the raw calls has guard words behind it.
+The op buffer in scratch, the instances with R = 1, 2, 4, 5 rows per lane,
+rectangles under 129 columns, ties on the strip boundary and the 32,767 bounds
+are in tests/test_gpu_trace_long_paths.py.
 """
 import ctypes
 
