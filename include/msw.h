@@ -831,9 +831,45 @@ int msw_map_pairs(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, co
  * min_baseq == 0 or quals == NULL is exactly msw_pileup_add[_device];
  * min_baseq > 93 is MSW_E_RANGE.
  *
+ * Inserted sequences.  A pileup created with msw_pileup_create_ex(ctx, genome,
+ * flags | MSW_PILEUP_INS, &out) also collects what the I runs insert (the
+ * calls are declared below, after msw_pileup_create_ex).
+ *   Events.  For a read that counts (the rule above, unchanged), an I len op
+ *   met at walk state (i, g) with 0 <= g - 1 < glen -- exactly the condition
+ *   under which channel 6 gets its +1 -- yields one event:
+ *     pos = g - 1 and len;
+ *     flags: bit 0 (OTHER) when any base i + k, k < min(len, 32), lies at or
+ *       past read_len[p] or is not upper-case A/C/G/T; bit 1 (LONG) when
+ *       len > 32;
+ *     seq (64 bits): base k of the run in bits 2k .. 2k + 1 (A 0, C 1, G 2,
+ *       T 3) for k < len; 0 when flags != 0.
+ *   The bases are those of the row the CIGAR refers to.  In the host add forms
+ *   a strand-1 read is given as read, and base t of that row is
+ *   comp(reads[p][read_len[p] - 1 - t]), as in the M columns.  The number of
+ *   events at pos equals the finished counts[pos][6].  Qualities and min_baseq
+ *   do not touch events.
+ *   Alleles and the vote.  Two events at one position show the same allele iff
+ *   their (len, flags, seq) are equal.  Every position with at least one event
+ *   gives one msw_ins_site_t: events, the number of distinct alleles, and the
+ *   winner -- the allele with flags == 0 and the highest count, ties to the
+ *   smaller len, then to the smaller seq -- with its count, and second_count,
+ *   the highest count among the other alleles with flags == 0.  Sites come in
+ *   ascending pos.  The table is a function of the set of records alone.
+ *   The log.  Events wait in a log of max(2^20, glen / 4) events of 16 bytes
+ *   (msw_pileup_ins_capacity sets another size before the first add).  An
+ *   event that finds the log full is dropped and counted.  Counts, qsums and
+ *   calls then stay valid and exact, but WHICH events were dropped depends on
+ *   the race, so no partial table is handed out: the site queries return
+ *   MSW_E_RANGE.
+ *
  * The result is a function of the set of records (with qualities and
  * threshold, where given) alone: it is bit-reproducible whatever order the
  * batches and the GPU's atomics ran in.
+ *
+ * State of a MSW_PILEUP_INS pileup, beside what follows: the log, 16 bytes per
+ * event of its capacity (16 MB, or 4 bytes per base from 4 Mbase on); from the
+ * finish on the table, 32 bytes per min(capacity, glen); and during the finish
+ * only, stream-ordered, 8 bytes per base and 16 per event of the capacity.
  *
  * State: about 44 bytes of device memory per genome base (the 32-byte row, two
  * 4-byte difference arrays and a 4-byte mismatch count), so
@@ -933,7 +969,8 @@ int msw_pileup_summary(msw_ctx* ctx, msw_pileup* pile, uint32_t min_depth, msw_p
  *     makes the record a DEL (alt 0), any other an SNV with alt the base letter.
  *   Insertion (MSW_VAR_INS 2), for any genome byte: a = c[6],
  *     span = min(depth(pos), depth(pos + 1)), ref = span > a ? span - a : 0,
- *     n = ref + a.  The inserted sequence is not in the pileup: alt is 0.
+ *     n = ref + a.  The inserted sequence is not in the counts: alt is 0
+ *     (a MSW_PILEUP_INS pileup has it beside them: "Inserted sequences").
  *   The record's depth is n, its ref_count ref, its alt_count a.
  *
  * Candidate.  n >= min_depth, a >= min_alt and
@@ -1076,8 +1113,51 @@ typedef struct {
 /* Fills *qparams with the defaults noted beside the fields. */
 void msw_call_qparams_default(msw_call_qparams_t* qparams);
 
-/* msw_pileup_create with flags: 0 or MSW_PILEUP_QSUM. */
+/* msw_pileup_create with flags: 0 or any combination of MSW_PILEUP_QSUM and
+ * MSW_PILEUP_INS (0, 1, 4, 5); any other bit is MSW_E_INVALID, bit 1 among
+ * them.  With MSW_PILEUP_INS a genome above 2^32 - 1 bases is MSW_E_RANGE (a
+ * site's pos has 32 bits). */
 int msw_pileup_create_ex(msw_ctx* ctx, const msw_genome* genome, uint32_t flags, msw_pileup** out);
+
+/* Inserted sequences ("Pileup" above has the rule).  A pileup without
+ * MSW_PILEUP_INS launches exactly what it launched before the flag existed;
+ * with it, every add form enqueues the capture behind the add on the same
+ * stream, and msw_pileup_finish enqueues the vote behind the fold, still
+ * without host synchronisation.  All four calls below return MSW_E_INVALID on
+ * a pileup without the flag. */
+#define MSW_PILEUP_INS 4u
+/* A site deeper than this many events is voted in several sweeps over tiles of
+ * this size: the result is the same, the time is quadratic
+ * in the depth. */
+#define MSW_INS_VOTE_TILE 1024u
+typedef struct {
+    uint32_t pos;           /* the base the insertion follows */
+    uint32_t events;        /* == counts[pos][6] */
+    uint32_t alleles;       /* distinct (len, flags, seq) */
+    uint32_t best_count;    /* events of the winning allele; 0 when no allele has flags == 0 */
+    uint32_t second_count;  /* highest count among the other alleles with flags == 0; 0 if none */
+    uint16_t best_len;      /* 1..32, 0 when best_count == 0 */
+    uint16_t reserved;      /* 0 */
+    uint64_t seq;           /* the winner's bases, 2 bits each, base 0 lowest */
+} msw_ins_site_t;           /* 32 bytes */
+typedef struct {
+    uint64_t events;        /* events met so far, the dropped ones among them */
+    uint64_t dropped;       /* events that found the log full */
+    uint64_t sites;         /* records of the table; 0 before the finish and when events were dropped */
+    uint64_t capacity;      /* events the log holds */
+} msw_ins_info_t;
+/* The log's capacity in events, before the first add: afterwards
+ * MSW_E_INVALID.  events == 0 or above 2^31 - 1 is MSW_E_RANGE. */
+int msw_pileup_ins_capacity(msw_ctx* ctx, msw_pileup* pile, uint64_t events);
+/* Synchronous (it waits for the device), valid before or after the finish. */
+int msw_pileup_ins_info(msw_ctx* ctx, msw_pileup* pile, msw_ins_info_t* out);
+/* The table: min(cap, *n_total) records into host_out; synchronous (it waits
+ * for the finish).  Before msw_pileup_finish: MSW_E_INVALID; when events were
+ * dropped: MSW_E_RANGE. */
+int msw_pileup_ins_sites(msw_ctx* ctx, msw_pileup* pile, msw_ins_site_t* host_out, uint64_t cap, uint64_t* n_total);
+/* The table on the device and its length; it waits for the finish, since *n is
+ * a host value.  The same errors. */
+int msw_pileup_ins_sites_device(msw_ctx* ctx, msw_pileup* pile, const msw_ins_site_t** sites, uint64_t* n);
 /* The finished quality sums into host_out[glen][4]; synchronous (it waits for
  * the finish).  Before msw_pileup_finish, or on a pileup without
  * MSW_PILEUP_QSUM: MSW_E_INVALID. */

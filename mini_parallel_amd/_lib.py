@@ -45,6 +45,7 @@ EXPORTED = (
     "msw_insert_bounds", "msw_map_pairs",
     "msw_trace_long_batch_device", "msw_align_batch_trace_long", "msw_trace_reads_long_device",
     "msw_align_reads_trace_long",
+    "msw_pileup_ins_capacity", "msw_pileup_ins_info", "msw_pileup_ins_sites", "msw_pileup_ins_sites_device",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -146,6 +147,12 @@ class CallQParamsT(ctypes.Structure):
 
 
 MSW_PILEUP_QSUM = 1
+MSW_PILEUP_INS = 4
+MSW_INS_VOTE_TILE = 1024
+
+
+class InsInfoT(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("events", "dropped", "sites", "capacity")]
 
 
 class DevReadsT(ctypes.Structure):
@@ -262,6 +269,10 @@ def _declare(L):
         "msw_call_counts_qual": (I, [P, P, ctypes.c_uint64, P, P, ctypes.POINTER(CallParamsT),
                                      ctypes.POINTER(CallQParamsT), ctypes.c_uint64, P, ctypes.c_uint64,
                                      ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_pileup_ins_capacity": (I, [P, P, ctypes.c_uint64]),
+        "msw_pileup_ins_info": (I, [P, P, ctypes.POINTER(InsInfoT)]),
+        "msw_pileup_ins_sites": (I, [P, P, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_pileup_ins_sites_device": (I, [P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64)]),
         "msw_call_counts": (I, [P, P, ctypes.c_uint64, P, ctypes.POINTER(CallParamsT), ctypes.c_uint64, P,
                                 ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),

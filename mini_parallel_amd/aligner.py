@@ -26,7 +26,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, MSW_PILEUP_QSUM, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PairParamsT, PileupSummaryT,
+from ._lib import (MSW_E_INVALID, MSW_PILEUP_INS, MSW_PILEUP_QSUM, InsInfoT, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PairParamsT, PileupSummaryT,
                    ReadBatchT, ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
@@ -160,6 +160,19 @@ VARIANT_DTYPE = np.dtype([("pos", "<u8"), ("depth", "<u4"), ("ref_count", "<u4")
                           ("gt", "u1"), ("gq", "u1"), ("pad", "u1", (7,))])
 assert VARIANT_DTYPE.itemsize == 48
 VAR_SNV, VAR_DEL, VAR_INS = 0, 1, 2
+
+# One insertion site (msw_ins_site_t of include/msw.h, "Inserted sequences"): 32 bytes.
+INS_SITE_DTYPE = np.dtype([("pos", "<u4"), ("events", "<u4"), ("alleles", "<u4"), ("best_count", "<u4"),
+                           ("second_count", "<u4"), ("best_len", "<u2"), ("reserved", "<u2"), ("seq", "<u8")])
+assert INS_SITE_DTYPE.itemsize == 32
+
+
+def ins_sequence(len: int, seq: int) -> bytes:
+    """The bases of an insertion allele: ``len`` (1..32) bases, base k in
+    bits 2k .. 2k + 1 of ``seq`` (A 0, C 1, G 2, T 3)."""
+    if not 0 <= int(len) <= 32:
+        raise MswError(MSW_E_INVALID, "ins_sequence: len must be 0..32")
+    return bytes(b"ACGT"[int(seq) >> 2 * k & 3] for k in range(int(len)))
 
 
 @dataclass(frozen=True)
@@ -649,13 +662,16 @@ class Context:
         return self.align_reads_trace(genome, reads, read_len, win_pos, win_len, scoring, chunk_pairs=chunk_pairs)
 
     # -- pileup (include/msw.h, "Pileup") -----------------------------------------------
-    def pileup(self, genome: "Genome", qsum: bool = False) -> "Pileup":
+    def pileup(self, genome: "Genome", qsum: bool = False, ins: bool = False, ins_capacity: int = 0) -> "Pileup":
         """An empty pileup over a resident genome (msw_pileup_create): per
         base the allele, deletion, insertion and reverse-strand counts of the
         alignment records added to it.  With ``qsum`` it also carries the
         per-base quality sums (MSW_PILEUP_QSUM): every add then needs
-        ``quals``, and :meth:`Pileup.call` can weigh the genotypes by them."""
-        return Pileup(self, genome, qsum)
+        ``quals``, and :meth:`Pileup.call` can weigh the genotypes by them.
+        With ``ins`` it collects the inserted sequences (MSW_PILEUP_INS) for
+        :meth:`Pileup.insertions`; ``ins_capacity`` > 0 sizes its event log
+        (msw_pileup_ins_capacity)."""
+        return Pileup(self, genome, qsum, ins, ins_capacity)
 
     # -- variants (include/msw.h, "Variants") -------------------------------------------
     def call_variants(self, genome, counts, params: Optional[CallParams] = None, chunk_pos: int = 0, qsums=None,
@@ -1170,14 +1186,23 @@ class Pileup:
 
     CHANNELS = 8
 
-    def __init__(self, ctx: Context, genome: Genome, qsum: bool = False):
+    def __init__(self, ctx: Context, genome: Genome, qsum: bool = False, ins: bool = False, ins_capacity: int = 0):
         h = ctypes.c_void_p()
-        if qsum:
-            check(lib().msw_pileup_create_ex(ctx.handle, genome.handle, MSW_PILEUP_QSUM, ctypes.byref(h)))
+        if qsum or ins:
+            flags = (MSW_PILEUP_QSUM if qsum else 0) | (MSW_PILEUP_INS if ins else 0)
+            check(lib().msw_pileup_create_ex(ctx.handle, genome.handle, flags, ctypes.byref(h)))
         else:
             check(lib().msw_pileup_create(ctx.handle, genome.handle, ctypes.byref(h)))
         self._h = h
         self.qsum = bool(qsum)
+        self.ins = bool(ins)
+        if ins_capacity:
+            try:
+                check(lib().msw_pileup_ins_capacity(ctx.handle, h, ins_capacity))
+            except MswError:
+                lib().msw_pileup_destroy(h)
+                self._h = None
+                raise
         self.ctx = ctx        # keeps the context and the genome alive for as long as the pileup
         self.genome = genome
         self._glen = len(genome)
@@ -1305,6 +1330,24 @@ class Pileup:
         check(lib().msw_pileup_qsums_device(self.ctx.handle, self.handle, ctypes.byref(ptr), ctypes.byref(ps),
                                             ctypes.byref(cs)))
         return int(ptr.value or 0), int(ps.value), int(cs.value)
+
+    def ins_info(self) -> dict:
+        """events, dropped, sites and capacity of an ``ins`` pileup's event
+        log (msw_pileup_ins_info); synchronous, before or after finish()."""
+        s = InsInfoT()
+        check(lib().msw_pileup_ins_info(self.ctx.handle, self.handle, ctypes.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("events", "dropped", "sites", "capacity")}
+
+    def insertions(self) -> np.ndarray:
+        """The insertion sites of an ``ins`` pileup in ascending ``pos``
+        (msw_pileup_ins_sites), as a structured array of INS_SITE_DTYPE;
+        after finish().  MSW_E_RANGE when the log dropped events."""
+        n = ctypes.c_uint64()
+        check(lib().msw_pileup_ins_sites(self.ctx.handle, self.handle, None, 0, ctypes.byref(n)))
+        rec = np.zeros(int(n.value), INS_SITE_DTYPE)
+        if len(rec):
+            check(lib().msw_pileup_ins_sites(self.ctx.handle, self.handle, _fresh_ptr(rec), len(rec), ctypes.byref(n)))
+        return rec
 
     def summary(self, min_depth: int = 1) -> dict:
         """covered, depth_sum, max_depth, minority_ref, reads_used and

@@ -29,7 +29,8 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .aligner import VAR_DEL, VAR_INS, VAR_SNV, VARIANT_DTYPE, CallParams, CigarList, QualParams, Variants
+from .aligner import (VAR_DEL, VAR_INS, VAR_SNV, VARIANT_DTYPE, CallParams, CigarList, QualParams, Variants,
+                      ins_sequence)
 
 MAGIC = b"MSWA"
 VERSION = 1
@@ -397,13 +398,22 @@ def read_variants_qual(path):
             QualParams(*(int(v) for v in head["qparams"])))
 
 
-def write_vcf(path, variants: Variants, genome, contig: str = "ref", sample: str = "sample") -> None:
+def write_vcf(path, variants: Variants, genome, contig: str = "ref", sample: str = "sample", insertions=None) -> None:
     """VCF 4.2 text of the records over ``genome`` (bytes or a uint8 array).
     An SNV is written as it is.  Consecutive DEL records (pos, pos + 1, ...
     with equal genotype) become one deletion with the first record's numbers,
     anchored at the base before the run, or at the base after it when the run
     starts at position 0.  An insertion is the symbolic ``<INS>`` at its anchor
-    base: the pileup does not hold the inserted sequence."""
+    base: the counts do not hold the inserted sequence.  With ``insertions``
+    (the table of :meth:`Pileup.insertions`) an insertion record whose site has
+    ``best_count > 0`` and ``2 * best_count > events`` -- one allele of at most
+    32 plain bases in more than half of the events -- gets that allele as a
+    real ALT, the anchor base followed by ``ins_sequence(best_len, seq)``;
+    every other insertion stays ``<INS>``, and the ``##ALT=<ID=INS`` header
+    line is written only if one does.  With ``insertions=None`` the file is
+    what it was without the table."""
+    sites = {} if insertions is None else {int(r["pos"]): r for r in insertions}
+    symbolic = [insertions is None]
     g = bytes(genome) if isinstance(genome, (bytes, bytearray)) else np.asarray(genome, np.uint8).tobytes()
     rec = variants.to_records()
 
@@ -419,7 +429,13 @@ def write_vcf(path, variants: Variants, genome, contig: str = "ref", sample: str
             int(r["gq"]), int(r["pl"][0]), int(r["pl"][1]), int(r["pl"][2]))))
 
     def insertion(r):
-        line(int(r["pos"]) + 1, seq(int(r["pos"]), int(r["pos"]) + 1), "<INS>", r)
+        pos = int(r["pos"])
+        anchor, alt, s = seq(pos, pos + 1), "<INS>", sites.get(pos)
+        if s is not None and int(s["best_count"]) > 0 and 2 * int(s["best_count"]) > int(s["events"]):
+            alt = anchor + ins_sequence(int(s["best_len"]), int(s["seq"])).decode()
+        else:
+            symbolic[0] = True
+        line(pos + 1, anchor, alt, r)
 
     k = 0
     while k < len(rec):
@@ -453,7 +469,8 @@ def write_vcf(path, variants: Variants, genome, contig: str = "ref", sample: str
     with open(path, "w") as f:
         f.write("##fileformat=VCFv4.2\n")
         f.write("##contig=<ID=%s,length=%d>\n" % (contig, len(g)))
-        f.write('##ALT=<ID=INS,Description="Insertion after this base; the sequence is not known">\n')
+        if symbolic[0]:
+            f.write('##ALT=<ID=INS,Description="Insertion after this base; the sequence is not known">\n')
         f.write('##ALT=<ID=DEL,Description="Deletion">\n')
         f.write('##INFO=<ID=DP,Number=1,Type=Integer,Description="Observations at the site">\n')
         f.write('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n')

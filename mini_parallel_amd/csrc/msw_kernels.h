@@ -401,6 +401,34 @@ hipError_t launch_pileup_summary(const PileupParams& p, uint32_t min_depth, unsi
 // out[m][8] = the rows of positions [pos0, pos0 + m), whatever the layout
 hipError_t launch_pileup_rows(const PileupParams& p, uint64_t pos0, uint64_t m, uint32_t* out, hipStream_t stream);
 
+// Inserted sequences (msw_ins.hip; msw.h, "Inserted sequences"): the event log of a MSW_PILEUP_INS pileup.
+// An event is {pos, len | flags << 28, plane0, plane1}: bit k of plane0 / plane1 is the low / high bit of the
+// code of base k.  *cursor counts every event met; the first `cap` of them are in the log.
+struct PileupIns {
+    uint4* log;
+    uint64_t cap;
+    unsigned long long* cursor;
+};
+// behind an add of the same batch, on the same stream: one event per I run that marks channel 6
+hipError_t launch_ins_capture(const PileupParams& p, const PileupIns& ins, hipStream_t stream);
+static_assert(MSW_INS_VOTE_TILE == 1024, "msw.h names the vote's tile");
+constexpr uint32_t kInsVoteTile = MSW_INS_VOTE_TILE;  // events of a deep site a wave stages in LDS at a time
+struct InsVote {
+    const uint32_t* counts;   // the pileup's, channel 6 final
+    uint64_t pos_mul, ch_mul, glen;
+    const uint4* log;
+    uint64_t cap;
+    const unsigned long long* cursor;
+    uint32_t* off;            // [glen + 1] temporary: the events' offsets per position
+    uint32_t* sidx;           // [glen + 1] temporary: the sites' indices
+    uint4* sorted;            // [cap] temporary: the events grouped by position
+    msw_ins_site_t* sites;    // [sites_cap] the table
+    uint64_t sites_cap;
+    unsigned long long* n_sites;
+};
+// the table from the log: nothing is written but *n_sites = 0 when the log dropped events (*cursor > cap)
+hipError_t launch_ins_vote(const InsVote& v, uint32_t* scan_tmp, hipStream_t stream);
+
 // Variants (msw_call.hip; the contract is in include/msw.h, "Variants").  One
 // call over positions [0, m) of a counts slab: channel ch of position k is
 // counts[k * pos_mul + ch * ch_mul] (both pileup layouts, or a plain [m][8]

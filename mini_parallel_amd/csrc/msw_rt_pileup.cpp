@@ -23,7 +23,13 @@ struct msw_pileup {
     unsigned long long* d_lowq = nullptr;  // PileupQual::lowq
     uint32_t* d_scan_tmp = nullptr;
     bool finished = false;
-    hipEvent_t fin = nullptr;      // recorded behind the fold
+    hipEvent_t fin = nullptr;      // recorded behind the fold (and the vote)
+    // with MSW_PILEUP_INS ("Inserted sequences"; the kernels: msw_ins.hip): the log, an allocation of its own; its
+    // cursor and the number of sites are words 8 and 9 of the sixteen at d_stats
+    msw::PileupIns ins{};
+    bool added = false;            // an add has been enqueued: the log's capacity is fixed
+    msw_ins_site_t* d_sites = nullptr;  // the table, allocated by the finish
+    uint64_t sites_cap = 0;
 };
 
 static int check_pileup(const msw_ctx* ctx, const msw_pileup* pile) {
@@ -39,12 +45,14 @@ int msw_pileup_create(msw_ctx* ctx, const msw_genome* g, msw_pileup** out) {
 int msw_pileup_create_ex(msw_ctx* ctx, const msw_genome* g, uint32_t flags, msw_pileup** out) {
     if (!ctx || !g || !out) return fail(MSW_E_INVALID, "ctx/genome/out is NULL");
     *out = nullptr;
-    if (flags & ~MSW_PILEUP_QSUM) return fail(MSW_E_INVALID, "pileup create: unknown flag in 0x%x", flags);
+    if (flags & ~(MSW_PILEUP_QSUM | MSW_PILEUP_INS)) return fail(MSW_E_INVALID, "pileup create: unknown flag in 0x%x", flags);
     const bool qsum = (flags & MSW_PILEUP_QSUM) != 0;
     if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
     int rc = set_device(ctx);
     if (rc) return rc;
     const uint64_t glen = g->len;
+    if ((flags & MSW_PILEUP_INS) && glen > 0xFFFFFFFFull)
+        return fail(MSW_E_RANGE, "pileup create: MSW_PILEUP_INS over a genome above 2^32-1 bases");
     auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
     const uint64_t read_words = (uint64_t)msw::kPileupReadSlots * 2 * msw::kPileupReadSlotWords;
     const uint64_t lowq_words = (uint64_t)msw::kPileupReadSlots * msw::kPileupReadSlotWords;
@@ -90,6 +98,11 @@ int msw_pileup_create_ex(msw_ctx* ctx, const msw_genome* g, uint32_t flags, msw_
     e = hipEventCreateWithFlags(&pile->fin, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemsetAsync(pile->d_state, 0, total, ctx->compute);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->compute);
+    if (e == hipSuccess && (flags & MSW_PILEUP_INS)) {
+        pile->ins.cursor = pile->d_stats + 8;
+        pile->ins.cap = std::max<uint64_t>(1ull << 20, glen / 4);
+        e = hipMalloc((void**)&pile->ins.log, pile->ins.cap * sizeof(uint4));
+    }
     if (e != hipSuccess) {
         msw_pileup_destroy(pile);
         return fail(MSW_E_DEVICE, "pileup state: %s", hipGetErrorString(e));
@@ -103,6 +116,8 @@ void msw_pileup_destroy(msw_pileup* pile) {
     (void)hipSetDevice(pile->device);
     if (pile->fin) (void)hipEventDestroy(pile->fin);
     if (pile->d_state) (void)hipFree(pile->d_state);
+    if (pile->ins.log) (void)hipFree(pile->ins.log);
+    if (pile->d_sites) (void)hipFree(pile->d_sites);
     delete pile;
 }
 
@@ -162,6 +177,7 @@ int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* ro
     p.strand = strand;
     p.mapq = mapq;
     p.min_mapq = min_mapq;
+    pile->added = true;
     if (pile->flags & MSW_PILEUP_QSUM) {
         msw::PileupQsum q = pile->qs;
         q.quals = quals;
@@ -174,6 +190,7 @@ int msw_pileup_add_qual_device(msw_ctx* ctx, msw_pileup* pile, const uint8_t* ro
     } else {
         HIP_TRY(msw::launch_pileup_add(p, call_stream(ctx, stream)));
     }
+    if (pile->flags & MSW_PILEUP_INS) HIP_TRY(msw::launch_ins_capture(p, pile->ins, call_stream(ctx, stream)));
     return MSW_OK;
 }
 
@@ -212,6 +229,8 @@ int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, co
     for (uint64_t k = 0; k < n; ++k)
         if (read_len[k] > read_stride) return fail(MSW_E_INVALID, "a length exceeds its stride");
     if ((rc = set_device(ctx))) return rc;
+    pile->added = true;
+    const bool ins = (pile->flags & MSW_PILEUP_INS) != 0;
     const size_t rs = read_stride, qs = qual_stride;
     DeviceArena a;
     const auto d_ref = a.take<int64_t>(chunk);
@@ -258,9 +277,41 @@ int msw_pileup_add_qual(msw_ctx* ctx, msw_pileup* pile, const uint8_t* reads, co
         if (cp.ok())
             cp.note(qsum ? msw::launch_pileup_add_qsum(p, qq, st)
                          : quals ? msw::launch_pileup_add_qual(p, q, st) : msw::launch_pileup_add(p, st));
+        if (ins && cp.ok()) cp.note(msw::launch_ins_capture(p, pile->ins, st));
         cp.sync();  // the buffers are the next chunk's
     }
     return cp.finish(MSW_OK, "pileup add");
+}
+
+// The vote of "Inserted sequences" behind the fold: the table is allocated here and kept, the glen-sized offsets and
+// the grouped events live for these launches only; everything is stream-ordered.
+static int pileup_ins_vote(msw_pileup* pile, hipStream_t st) {
+    const msw::PileupParams& p = pile->p;
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    msw::InsVote v{};
+    v.counts = p.counts;
+    v.pos_mul = p.pos_mul;
+    v.ch_mul = p.ch_mul;
+    v.glen = p.glen;
+    v.log = pile->ins.log;
+    v.cap = pile->ins.cap;
+    v.cursor = pile->ins.cursor;
+    v.n_sites = pile->ins.cursor + 1;
+    // a site has at least one event, and a position at most one site
+    v.sites_cap = pile->sites_cap = std::max<uint64_t>(1, std::min(v.cap, p.glen));
+    HIP_TRY(hipMallocAsync((void**)&pile->d_sites, v.sites_cap * sizeof(msw_ins_site_t), st));
+    v.sites = pile->d_sites;
+    const uint64_t words = up16((p.glen + 1) * 4);
+    uint8_t* tmp = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&tmp, 2 * words + v.cap * sizeof(uint4), st));
+    v.off = reinterpret_cast<uint32_t*>(tmp);
+    v.sidx = reinterpret_cast<uint32_t*>(tmp + words);
+    v.sorted = reinterpret_cast<uint4*>(tmp + 2 * words);
+    hipError_t e = msw::launch_ins_vote(v, pile->d_scan_tmp, st);
+    const hipError_t ef = hipFreeAsync(tmp, st);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return fail(MSW_E_DEVICE, "pileup finish, inserted sequences: %s", hipGetErrorString(e));
+    return MSW_OK;
 }
 
 int msw_pileup_finish(msw_ctx* ctx, msw_pileup* pile, void* stream) {
@@ -271,6 +322,7 @@ int msw_pileup_finish(msw_ctx* ctx, msw_pileup* pile, void* stream) {
     hipStream_t st = call_stream(ctx, stream);
     if (pile->flags & MSW_PILEUP_QSUM) HIP_TRY(msw::launch_pileup_finish_qsum(pile->p, pile->qs, pile->d_scan_tmp, st));
     else HIP_TRY(msw::launch_pileup_finish(pile->p, pile->d_scan_tmp, st));
+    if ((pile->flags & MSW_PILEUP_INS) && (rc = pileup_ins_vote(pile, st))) return rc;
     HIP_TRY(hipEventRecord(pile->fin, st));
     pile->finished = true;
     return MSW_OK;
@@ -395,6 +447,89 @@ int msw_pileup_qsums(msw_ctx* ctx, msw_pileup* pile, uint32_t* host_out) {
     hipStream_t st = ctx->compute;
     HIP_TRY(hipMemcpyAsync(host_out, pile->qs.qsum, glen * 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return MSW_OK;
+}
+
+// Inserted sequences (include/msw.h, "Inserted sequences"; the kernels: msw_ins.hip).
+static int check_pileup_ins(const msw_ctx* ctx, const msw_pileup* pile, const char* what) {
+    int rc;
+    if ((rc = check_pileup(ctx, pile))) return rc;
+    if (!(pile->flags & MSW_PILEUP_INS)) return fail(MSW_E_INVALID, "%s: the pileup was created without MSW_PILEUP_INS", what);
+    return MSW_OK;
+}
+
+static_assert(sizeof(msw_ins_site_t) == 32, "msw_ins_site_t is 32 bytes");
+
+int msw_pileup_ins_capacity(msw_ctx* ctx, msw_pileup* pile, uint64_t events) {
+    int rc;
+    if ((rc = check_pileup_ins(ctx, pile, "pileup ins capacity"))) return rc;
+    if (pile->added || pile->finished) return fail(MSW_E_INVALID, "pileup ins capacity: after the first add");
+    if (events == 0 || events > 0x7FFFFFFFull) return fail(MSW_E_RANGE, "pileup ins capacity: %llu events", (unsigned long long)events);
+    if (events == pile->ins.cap) return MSW_OK;
+    if ((rc = set_device(ctx))) return rc;
+    uint4* log = nullptr;
+    const hipError_t e = hipMalloc((void**)&log, events * sizeof(uint4));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MSW_E_NOMEM, "hipMalloc(%llu B) for the insertion log: %s", (unsigned long long)(events * sizeof(uint4)),
+                    hipGetErrorString(e));
+    }
+    (void)hipFree(pile->ins.log);
+    pile->ins.log = log;
+    pile->ins.cap = events;
+    return MSW_OK;
+}
+
+// cursor and n_sites, once the device (all = true) or the finish has drained
+static int pileup_ins_words(msw_ctx* ctx, msw_pileup* pile, bool all, unsigned long long h[2]) {
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    // adds may have been enqueued on any stream
+    if (all) HIP_TRY(hipDeviceSynchronize());
+    else HIP_TRY(hipEventSynchronize(pile->fin));
+    HIP_TRY(hipMemcpy(h, pile->ins.cursor, 16, hipMemcpyDeviceToHost));
+    return MSW_OK;
+}
+
+int msw_pileup_ins_info(msw_ctx* ctx, msw_pileup* pile, msw_ins_info_t* out) {
+    int rc;
+    if ((rc = check_pileup_ins(ctx, pile, "pileup ins info"))) return rc;
+    if (!out) return fail(MSW_E_INVALID, "out is NULL");
+    unsigned long long h[2];
+    if ((rc = pileup_ins_words(ctx, pile, true, h))) return rc;
+    out->events = h[0];
+    out->dropped = h[0] > pile->ins.cap ? h[0] - pile->ins.cap : 0;
+    out->sites = pile->finished ? h[1] : 0;
+    out->capacity = pile->ins.cap;
+    return MSW_OK;
+}
+
+int msw_pileup_ins_sites_device(msw_ctx* ctx, msw_pileup* pile, const msw_ins_site_t** sites, uint64_t* n) {
+    int rc;
+    if ((rc = check_pileup_ins(ctx, pile, "pileup ins sites"))) return rc;
+    if (!sites || !n) return fail(MSW_E_INVALID, "NULL output");
+    if (!pile->finished) return fail(MSW_E_INVALID, "pileup ins sites before msw_pileup_finish");
+    unsigned long long h[2];
+    if ((rc = pileup_ins_words(ctx, pile, false, h))) return rc;
+    if (h[0] > pile->ins.cap)
+        return fail(MSW_E_RANGE, "pileup ins sites: the log of %llu events dropped %llu (msw_pileup_ins_capacity)",
+                    (unsigned long long)pile->ins.cap, h[0] - pile->ins.cap);
+    *sites = pile->d_sites;
+    *n = h[1];
+    return MSW_OK;
+}
+
+int msw_pileup_ins_sites(msw_ctx* ctx, msw_pileup* pile, msw_ins_site_t* host_out, uint64_t cap, uint64_t* n_total) {
+    int rc;
+    if ((rc = check_pileup_ins(ctx, pile, "pileup ins sites"))) return rc;
+    if (!n_total) return fail(MSW_E_INVALID, "n_total is NULL");
+    if (cap && !host_out) return fail(MSW_E_INVALID, "host_out is NULL with cap > 0");
+    const msw_ins_site_t* d = nullptr;
+    uint64_t n = 0;
+    if ((rc = msw_pileup_ins_sites_device(ctx, pile, &d, &n))) return rc;
+    const uint64_t have = std::min(cap, n);
+    if (have) HIP_TRY(hipMemcpy(host_out, d, have * sizeof(msw_ins_site_t), hipMemcpyDeviceToHost));
+    *n_total = n;
     return MSW_OK;
 }
 

@@ -27,7 +27,10 @@ both strands, traced and packed on the device.  HIP events on the stream,
               that takes every read for one M run
   finish_qsum msw_pileup_finish of such a pileup (one more scan and fold)
 
-  python3 tools/pileup_bench.py [--planes] [--reads 40000]"""
+``--ins`` prints the rows of a MSW_PILEUP_INS pileup instead:
+add and finish with and without the flag, and one site 64 .. 40,000 events deep.
+
+  python3 tools/pileup_bench.py [--planes] [--ins] [--reads 40000]"""
 import argparse
 import json
 import os
@@ -37,6 +40,67 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def ins_rows(args, ctx, genome, rec, timed, add_to, st, torch, batch, h_nm, h_off, h_ops, up):
+    """--ins: the capture and the vote of a MSW_PILEUP_INS pileup beside the add
+    and the fold of a pileup without the flag, alternated in this process (the
+    capture is enqueued by the add and the vote by the finish, so each is the
+    difference of the two), then one site `depth` events deep: every read a
+    copy of the first read that carries an I run."""
+    oriented, d_rl, ref, nm, strand, ops, ors = batch
+    s, n = st.cuda_stream, rec["reads"]
+    rec["row"] = "pileup_ins"
+
+    def finish_ms(flag, add, reps):
+        ms = []
+        for k in range(reps):
+            pk = ctx.pileup(genome, ins=flag)
+            add(pk)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            pk.finish(s)
+            e1.record(st)
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+            info = pk.ins_info() if flag else None
+            pk.close()
+        return round(sorted(ms[1:])[len(ms[1:]) // 2], 4), info
+
+    runs = {"add_ms": [], "add_ins_ms": [], "finish_ms": [], "finish_ins_ms": []}
+    for _ in range(3):
+        plain, flagged = ctx.pileup(genome), ctx.pileup(genome, ins=True)
+        runs["add_ms"].append(timed(lambda: add_to(plain)))
+        runs["add_ins_ms"].append(timed(lambda: add_to(flagged)))
+        plain.close()
+        flagged.close()
+        runs["finish_ms"].append(finish_ms(False, add_to, 6)[0])
+        t, rec["batch_info"] = finish_ms(True, add_to, 6)
+        runs["finish_ins_ms"].append(t)
+    for k, v in runs.items():
+        rec[k], rec[k + "_runs"] = sorted(v)[1], v
+    rec["capture_ms"] = round(rec["add_ins_ms"] - rec["add_ms"], 4)
+    rec["vote_ms"] = round(rec["finish_ins_ms"] - rec["finish_ms"], 4)
+    # one locus: the first counted read with an I op, `depth` copies of it
+    has_i = [p for p in np.flatnonzero(h_nm >= 0) if (h_ops[h_off[p]:h_off[p + 1]].view(np.uint32) & 15 == 1).any()]
+    one = int(has_i[0])
+    k1 = int(h_off[one + 1] - h_off[one])
+    c_rows, c_ops = oriented.view(n, ors)[one].repeat(n), ops[int(h_off[one]):int(h_off[one + 1])].repeat(n)
+    c_rl, c_ref, c_nm, c_strand = d_rl[one].repeat(n), ref[one].repeat(n), nm[one].repeat(n), strand[one].repeat(n)
+    c_off = up((np.arange(n + 1, dtype=np.int64) * k1).astype(np.uint32).view(np.int32))
+    rec["deep"] = []
+    for depth in (64, 256, 1024, 4096, 16384, n):
+        def contend(pile, depth=depth):
+            pile.add_device(c_rows.data_ptr(), c_rl.data_ptr(), ors, depth, c_ref.data_ptr(), c_nm.data_ptr(),
+                            c_off.data_ptr(), c_ops.data_ptr(), depth * k1, c_strand.data_ptr(), 0, 0, s)
+        plain, flagged = ctx.pileup(genome), ctx.pileup(genome, ins=True)
+        row = {"depth": depth, "add_ms": timed(lambda: contend(plain)), "add_ins_ms": timed(lambda: contend(flagged))}
+        plain.close()
+        flagged.close()
+        row["finish_ms"] = finish_ms(False, contend, 4)[0]
+        row["finish_ins_ms"], row["info"] = finish_ms(True, contend, 4)
+        rec["deep"].append(row)
+    print(json.dumps(rec), flush=True)
 
 
 def main():
@@ -49,6 +113,7 @@ def main():
     ap.add_argument("--cigar-stride", type=int, default=32)
     ap.add_argument("--genome-mbases", type=int, default=4)
     ap.add_argument("--planes", action="store_true")
+    ap.add_argument("--ins", action="store_true", help="the rows of a MSW_PILEUP_INS pileup (DESIGN.md 4.21) instead")
     args = ap.parse_args()
     if args.planes:
         os.environ["MSW_PILEUP_PLANES"] = "1"       # read once, when the context is created
@@ -140,6 +205,13 @@ def main():
     rec = {"row": "pileup", "layout": "planes" if args.planes else "rows8", "shape": "config 3 (150 x 300, affine)",
            "reads": n, "genome_bases": int(g.shape[0]), "steps": args.steps, "warmup": args.warmup,
            "ops": total_ops, "nm_sum": int(h_nm[h_nm > 0].sum()), "reads_with_record": int((h_nm >= 0).sum())}
+    if args.ins:
+        ins_rows(args, ctx, genome, rec, timed, add_to, st, torch,
+                 (oriented, d_rl, ref, nm, strand, ops, ors), h_nm, h_off, ops.cpu().numpy(), up)
+        index.close()
+        genome.close()
+        ctx.close()
+        return
     rec["strands_ms"] = timed(strands)      # the batch's scoring on both strands, with end cells
     rec["pack_ms"] = timed(pack)
     pile = ctx.pileup(genome)
