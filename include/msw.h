@@ -1186,6 +1186,70 @@ int msw_call_counts_qual(msw_ctx* ctx, const uint8_t* genome_host, uint64_t glen
                          const msw_call_qparams_t* qparams, uint64_t chunk_pos, msw_variant_t* out_host, uint64_t cap,
                          uint64_t* n_total);
 
+/* Banded alignment: score, best cell and traceback inside a diagonal band.
+ *
+ * The band has a centre c and a half-width w.  Cell (i, j), 0-based, i in the
+ * read of length L and j in the window of length W, EXISTS iff
+ *   0 <= i < L,  0 <= j < W  and  |j - i - c| <= w.
+ * H, E and F are the scorer's recurrence over the existing cells.  A cell that
+ * does not exist has H = 0, and no gap may start in it, pass through it or end
+ * in it (E = F = -inf there): the rule the rectangle's border already has.
+ * Best cell: maximum score, then smallest i, then smallest j, over the
+ * existing cells; score 0 or no existing cell gives score 0 and (-1, -1).
+ * The canonical alignment is the one of "Traceback" above, the same walk with
+ * the same precedence (diagonal > I > D, open > extend), on the BANDED H, E and
+ * F, so a record's score and its CIGAR always agree (tracing a banded end cell
+ * on the full rectangle would not give that: H there can exceed the banded H).
+ * With w >= max(L, W) and every cell inside the band the results are those of
+ * msw_align_batch / msw_align_batch_trace, bit for bit.
+ *
+ * Limits (MSW_E_RANGE outside them): 0 <= w <= 63 (the band is B = 2w + 1 <= 127
+ * cells a row); max_read_len <= 32,767 and max_read_len + 2w <= 32,767; scoring
+ * schemes as everywhere.  A traced call keeps one 4-bit direction code per band
+ * cell in LDS, 64 bytes per row for the block whatever w is, under the 64 KiB a
+ * block may hold: max_read_len <= 1008 with `tr`, else MSW_E_RANGE.  Cells are
+ * i32 at every length.  A read longer than max_read_len scores 0.  In the
+ * padded form columns at or past 32,767 do not exist (end_j is an int16).
+ *
+ * Windows are read where they lie: the padded form reads the batch's `wins`
+ * rows, the genome form genome[...] itself.  The band says which bytes are
+ * needed, [c - w, c + L + w); nothing is cut into a slab.
+ *
+ * Composing with seeding ("Placing reads"): a seed d0 with `band` says the
+ * read's diagonal lies in [d0, d0 + band), so c = d0 + (band - 1) / 2 (a genome
+ * coordinate, for the genome form) covers all of it with w >= (band - 1) / 2;
+ * every unit of w beyond that admits one more base of net insertion or
+ * deletion off the seeded diagonal: indels up to w - (band - 1) / 2. */
+
+/* Device-resident, padded form: every pointer in `batch`, `out` and `tr` and
+ * `diag` (int32[n_pairs], c relative to the pair's window) is device memory.
+ * want_coords = 0 writes out->score only; `tr` (may be NULL) forces the
+ * coordinates and traces in the same launch.  Enqueued on `stream` (NULL = the
+ * context's compute stream), no host synchronisation. */
+int msw_align_batch_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch,
+                                  const int32_t* diag, uint32_t w, msw_out_t* out, msw_trace_t* tr,
+                                  uint32_t max_read_len, void* stream);
+/* Device-resident, genome form: diag is int64[n], the genome coordinate of c
+ * (it may be negative or past the genome's end); a cell's column is a genome
+ * coordinate and exists inside [0, genome length).  diag[p] == INT64_MIN is an
+ * unplaced read: score 0, (-1, -1), win_pos_out -1, win_len_out 0.  Otherwise
+ * win_pos_out[p] = max(0, c - w) and win_len_out[p] = the length of
+ * [c - w, c + L + w) clipped to the genome (either may be NULL); end_j and
+ * start_j are relative to that implied window, so msw_aln_pack_device and the
+ * pileup take out / tr / win_pos_out as they take a scoring call's. */
+int msw_align_reads_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                                  const uint16_t* read_len, uint32_t read_stride, const int64_t* diag, uint64_t n,
+                                  uint32_t w, uint32_t max_read_len, msw_out_t* out, int64_t* win_pos_out,
+                                  uint16_t* win_len_out, msw_trace_t* tr, void* stream);
+/* Host memory, synchronous, in chunks of `chunk_pairs` (0 = 65536), like
+ * msw_align_batch_trace.  In the genome form batch->win_pos holds diag and
+ * batch->win_len is not read. */
+int msw_align_batch_banded(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch, const int32_t* diag,
+                           uint32_t w, msw_out_t* out, msw_trace_t* tr, uint64_t chunk_pairs);
+int msw_align_reads_banded(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* batch,
+                           uint32_t w, msw_out_t* out, int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr,
+                           uint64_t chunk_pairs);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

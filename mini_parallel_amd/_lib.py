@@ -46,6 +46,8 @@ EXPORTED = (
     "msw_trace_long_batch_device", "msw_align_batch_trace_long", "msw_trace_reads_long_device",
     "msw_align_reads_trace_long",
     "msw_pileup_ins_capacity", "msw_pileup_ins_info", "msw_pileup_ins_sites", "msw_pileup_ins_sites_device",
+    "msw_align_batch_banded_device", "msw_align_reads_banded_device", "msw_align_batch_banded",
+    "msw_align_reads_banded",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -275,6 +277,15 @@ def _declare(L):
         "msw_pileup_ins_sites_device": (I, [P, P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_uint64)]),
         "msw_call_counts": (I, [P, P, ctypes.c_uint64, P, ctypes.POINTER(CallParamsT), ctypes.c_uint64, P,
                                 ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_align_batch_banded_device": (I, [P, ctypes.POINTER(ScoringT), ctypes.POINTER(BatchT), P, ctypes.c_uint32,
+                                              ctypes.POINTER(OutT), ctypes.POINTER(TraceT), ctypes.c_uint32, P]),
+        "msw_align_reads_banded_device": (I, [P, ctypes.POINTER(ScoringT), P, P, P, ctypes.c_uint32, P,
+                                              ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.POINTER(OutT), P, P, ctypes.POINTER(TraceT), P]),
+        "msw_align_batch_banded": (I, [P, ctypes.POINTER(ScoringT), ctypes.POINTER(BatchT), P, ctypes.c_uint32,
+                                       ctypes.POINTER(OutT), ctypes.POINTER(TraceT), ctypes.c_uint64]),
+        "msw_align_reads_banded": (I, [P, ctypes.POINTER(ScoringT), P, ctypes.POINTER(ReadBatchT), ctypes.c_uint32,
+                                       ctypes.POINTER(OutT), P, P, ctypes.POINTER(TraceT), ctypes.c_uint64]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

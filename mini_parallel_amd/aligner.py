@@ -363,16 +363,27 @@ class Context:
                        reads.shape[1] if reads.ndim == 2 else 0,
                        wins.shape[1] if wins.ndim == 2 else 0, B)
         sc = _scoring_c(scoring)
-        call = lib().msw_align_batch_trace_long if long_pairs else lib().msw_align_batch_trace
+        fn = lib().msw_align_batch_trace_long if long_pairs else lib().msw_align_batch_trace
+
+        def call(out, tr):
+            check(fn(self.handle, ctypes.byref(sc), ctypes.byref(batch), ctypes.byref(out), ctypes.byref(tr),
+                     chunk_pairs))
+        return self._traced(B, True, True, cigar_stride, call)
+
+    def _traced(self, B: int, coords: bool, trace: bool, cigar_stride: Optional[int], call):
+        """The output arrays and the stride retry of the calls that trace into
+        padded CIGAR rows; ``call(out, tr)`` runs one of them (tr is None
+        without ``trace``)."""
         stride = 32 if cigar_stride is None else int(cigar_stride)
         while True:
-            (score, ei, ej), out = _outputs(B, True)
+            (score, ei, ej), out = _outputs(B, coords)
+            if not trace:
+                call(out, None)
+                return score, ei, ej
             si, sj = np.empty(B, np.int16), np.empty(B, np.int16)
             nc = np.zeros(B, np.int32)
             cig = np.zeros((B, stride), np.uint32)
-            tr = TraceT(_fresh_ptr(si), _fresh_ptr(sj), _fresh_ptr(nc), _fresh_ptr(cig), stride)
-            check(call(self.handle, ctypes.byref(sc), ctypes.byref(batch), ctypes.byref(out), ctypes.byref(tr),
-                       chunk_pairs))
+            call(out, TraceT(_fresh_ptr(si), _fresh_ptr(sj), _fresh_ptr(nc), _fresh_ptr(cig), stride))
             need = int(nc.max()) if B else 0
             if cigar_stride is None and need > stride:
                 stride = need  # once: the counts do not depend on the stride
@@ -381,6 +392,58 @@ class Context:
         ops = CigarList(cig[p, :nc[p]].copy() if nc[p] <= stride else None for p in range(B))
         ops.n_cigar = nc
         return score, ei, ej, si, sj, ops
+
+    # -- banded alignment (include/msw.h, "Banded alignment") ---------------------------
+    def align_batch_banded(self, reads: np.ndarray, read_len: np.ndarray, wins: np.ndarray, win_len: np.ndarray,
+                           diag: np.ndarray, w: int, scoring: Scoring = LINEAR, trace: bool = False,
+                           cigar_stride: Optional[int] = None, chunk_pairs: int = 0):
+        """:meth:`align_batch` inside a diagonal band (msw_align_batch_banded):
+        pair p scores only the cells with ``|j - i - diag[p]| <= w`` (0 <= w <=
+        63), every other cell counting as H = 0.  Returns (score, end_i, end_j)
+        like :meth:`align_batch`, or with ``trace`` what
+        :meth:`align_batch_trace` returns, the alignment being the canonical
+        one of the banded recurrence (traced reads <= 1008 bases)."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        wins = np.ascontiguousarray(wins, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        win_len = np.ascontiguousarray(win_len, dtype=np.uint16)
+        diag = np.ascontiguousarray(diag, dtype=np.int32)
+        B = reads.shape[0]
+        if wins.shape[0] != B or read_len.shape[0] != B or win_len.shape[0] != B or diag.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of pairs")
+        batch = BatchT(_ptr(reads), _ptr(wins), _ptr(read_len), _ptr(win_len),
+                       reads.shape[1] if reads.ndim == 2 else 0, wins.shape[1] if wins.ndim == 2 else 0, B)
+        sc = _scoring_c(scoring)
+
+        def call(out, tr):
+            check(lib().msw_align_batch_banded(self.handle, ctypes.byref(sc), ctypes.byref(batch), _ptr(diag), w,
+                                               ctypes.byref(out), ctypes.byref(tr) if tr else None, chunk_pairs))
+        return self._traced(B, scoring.want_coords or trace, trace, cigar_stride, call)
+
+    def align_reads_banded(self, genome: "Genome", reads: np.ndarray, read_len: np.ndarray, diag: np.ndarray,
+                           w: int, scoring: Scoring = LINEAR, trace: bool = False,
+                           cigar_stride: Optional[int] = None, chunk_pairs: int = 0):
+        """Reads against the genome inside a band (msw_align_reads_banded):
+        ``diag[p]`` (int64) is the genome coordinate of the band's centre for
+        read base 0, ``INT64_MIN`` an unplaced read.  Returns what
+        :meth:`align_batch_banded` returns followed by (win_pos int64[B],
+        win_len uint16[B]): the implied window ``max(0, diag - w)`` that end_j
+        and start_j are relative to, and its clipped length."""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
+        diag = np.ascontiguousarray(diag, dtype=np.int64)
+        B = reads.shape[0]
+        if read_len.shape[0] != B or diag.shape[0] != B:
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of pairs")
+        batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0, _ptr(diag), 0, B)
+        sc = _scoring_c(scoring)
+        win_pos, wlen = np.empty(B, np.int64), np.empty(B, np.uint16)
+
+        def call(out, tr):
+            check(lib().msw_align_reads_banded(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch), w,
+                                               ctypes.byref(out), _fresh_ptr(win_pos), _fresh_ptr(wlen),
+                                               ctypes.byref(tr) if tr else None, chunk_pairs))
+        return self._traced(B, scoring.want_coords or trace, trace, cigar_stride, call) + (win_pos, wlen)
 
     def trace_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int, win_len_ptr: int,
                            read_stride: int, win_stride: int, n_pairs: int, score_ptr: int,

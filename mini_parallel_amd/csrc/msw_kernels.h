@@ -612,6 +612,40 @@ hipError_t launch_strand_select(const uint8_t* reads, const uint16_t* read_len, 
 // blocks per CU of the two kernels (the smaller); the query loads the module
 int strand_blocks_per_cu();
 
+// Banded Smith-Waterman (sw_band_kernel, msw_band.hip; the recurrence is in
+// include/msw.h, "Banded alignment").  Lanes own diagonals of the band and
+// step along anti-diagonals; i32 cells.  Windows come from `wins` rows (diag32:
+// the window-relative centre) or straight from the genome (genome != null,
+// diag64: the centre's genome coordinate, INT64_MIN: unplaced).
+struct BandParams {
+    const uint8_t* reads;
+    const uint16_t* read_len;
+    uint64_t read_stride;
+    const uint8_t* wins;
+    const uint16_t* win_len;
+    uint64_t win_stride;
+    const int32_t* diag32;
+    const uint8_t* genome;
+    uint64_t glen;
+    const int64_t* diag64;
+    int64_t* win_pos_out;     // genome form: max(0, c - w); may be null
+    uint16_t* win_len_out;    // genome form: the implied window's clipped length; may be null
+    int32_t* score;
+    int16_t* end_i;           // null with score-only launches
+    int16_t* end_j;
+    int16_t* start_i;         // traced launches
+    int16_t* start_j;
+    int32_t* n_cigar;
+    uint32_t* cigar;
+    uint32_t cigar_stride;
+    uint32_t n_pairs;
+    uint32_t w;
+    uint32_t max_rows;        // bound of read_len: a longer read scores 0
+    int32_t match, mismatch, gap, goe;  // gap: linear penalty / affine gap_extend
+};
+// mode 0: score, 1: score + best cell, 2: score + best cell + traceback
+hipError_t launch_sw_band(const BandParams& p, bool affine, int mode, hipStream_t stream);
+
 // smith_waterman_align restated: result must be zeroed before the launch.
 hipError_t launch_compat(const uint8_t* s1, const uint8_t* s2, int32_t* result, uint64_t L,
                          uint32_t W, uint64_t G, hipStream_t stream);

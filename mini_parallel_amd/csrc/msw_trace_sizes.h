@@ -73,4 +73,26 @@ inline TraceLongLayout trace_long_layout(bool affine, uint32_t max_rows, uint32_
     return l;
 }
 
+// sw_band_kernel (msw_band.hip): one wave per block; a group of G lanes owns
+// the 2G diagonals of one pair's band, so a wave carries 64 / G pairs.
+//   LDS = [byte tiles | direction codes]
+//   byte tiles: per group kBandTile read bytes + kBandTile window bytes, the
+//     bytes of the next 64 rows' anti-diagonals (64 + G each, <= kBandTile)
+//   direction codes (traced calls only): per group max_rows rows of G bytes,
+//     one 4-bit code per band cell, [row][diagonal], two diagonals per byte;
+//     64 / G groups x G bytes = 64 bytes per row for the block whatever w is
+// A block's LDS is capped at 64 KiB, so a traced call holds
+// (65536 - 1024) / 64 = 1008 rows: kBandTraceMaxRows.
+constexpr uint32_t kBandMaxW = 63;
+constexpr uint32_t kBandTile = 128;
+constexpr uint32_t kBandTileBytes = 2u * kBandTile * 4u;  // at most four groups: 1 KiB
+constexpr uint32_t kBandTraceMaxRows = (65536u - kBandTileBytes) / 64u;
+
+// lanes per pair for half-width w: 16 (B <= 32), 32 (B <= 64), 64 (B <= 127)
+inline uint32_t band_group_lanes(uint32_t w) { return w <= 15 ? 16u : (w <= 31 ? 32u : 64u); }
+// dynamic LDS bytes of a launch
+inline uint32_t band_lds_bytes(uint32_t max_rows, bool trace) {
+    return kBandTileBytes + (trace ? 64u * max_rows : 0u);
+}
+
 }  // namespace msw

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../mini_parallel_amd/csrc"
 NAME=$1; shift
 OUT=../../tools/_variants
 mkdir -p "$OUT/o_$NAME"
-HOST="msw_runtime.o msw_rt_trace.o msw_rt_map.o msw_rt_pileup.o msw_fastq.o msw_gfastq.o"  # the Makefile's RTOBJS and readers
+HOST="msw_runtime.o msw_rt_trace.o msw_rt_map.o msw_rt_pileup.o msw_rt_band.o msw_fastq.o msw_gfastq.o"  # the Makefile's RTOBJS and readers
 make -s $HOST >/dev/null
 pids=()
 for f in *.hip; do  # every kernel unit of the Makefile's KOBJS and GZOBJS
