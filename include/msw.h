@@ -1250,6 +1250,95 @@ int msw_align_reads_banded(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
                            uint32_t w, msw_out_t* out, int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr,
                            uint64_t chunk_pairs);
 
+/* Sorting and duplicates: a device-wide stable sort, the coordinate order of
+ * records, and duplicate flags by unclipped 5' position.  Everything is
+ * integers; the results are functions of the inputs alone, whatever order the
+ * GPU's blocks and atomics ran in.
+ *
+ * The sort.  A stable ascending sort of (keys[i] & mask, vals[i]) by the masked
+ * key, mask = the low key_bits bits: the keys come back in that order with all
+ * 64 bits carried along, equal masked keys keep their input order, and vals
+ * (NULL: keys only) moves with them.  LSD radix, 8 bits a pass, ceil(key_bits /
+ * 8) passes over tiles of MSW_SORT_TILE elements.
+ *
+ * The key of a read.  L and T are the lengths of the first and the last op of
+ * the read's packed CIGAR where that op is S (an only op counts as the first),
+ * else 0; span is the sum of its M and D lengths (I and S consume no
+ * reference).  The unclipped 5' coordinate is
+ *   strand 0:  u5 = ref_pos - L
+ *   strand 1:  u5 = ref_pos + span - 1 + T
+ * (strand == NULL: every read is on strand 0) and the key
+ *   k = ((u5 + 32768) << 1) | strand,
+ * non-negative because a clip is at most 32,767 bases.  A read is UNKEYED when
+ * ref_pos < 0, score <= 0 or nm < 0 (a trace overflow: no ops to walk), in the
+ * device form also when its ops do not lie inside cigar_cap; its key is
+ *   K_NONE = (ref_len + 65536) << 1,
+ * above every key of a record on a genome of ref_len bases (a k that would
+ * reach K_NONE makes the read unkeyed too).  ref_len > 2^61 is MSW_E_RANGE.
+ * Sorts run over key_bits = the bit length of K_NONE: 24 bits, three passes,
+ * for a 4 Mbase genome.
+ *
+ * Fragments.  Single-end: fragment f is read f, (K1, K2) = (k, 0), quality =
+ * score.  Pairs (pairs != 0; rows 2p and 2p + 1 are the mates of fragment p, as
+ * in "Pairs"; an odd row count is MSW_E_INVALID): K1 = min(k_a, k_b), K2 =
+ * max(k_a, k_b), quality = the 64-bit sum of the scores of the keyed mates.  A
+ * pair with one keyed mate so has K2 = K_NONE and meets only its like; a pair
+ * with none has K1 = K_NONE.  The two mates are treated symmetrically: which
+ * of them is mate 1 does not enter (Picard tells FR from RF by mate order; here
+ * the strand bits inside the keys carry the orientation, and two pairs that are
+ * equal after swapping their mates are duplicates).
+ *
+ * Order.  order[t] is the fragment at rank t of the stable ascending sort by
+ * (K1, K2): unkeyed fragments come last, ties keep input order.
+ *
+ * Flags.  The fragments of equal (K1, K2) with K1 != K_NONE form a group.  Its
+ * representative has the greatest quality, on ties the smallest fragment index;
+ * every other fragment of the group is a duplicate.  dup[r], per read ROW, is 1
+ * for the keyed rows of a duplicate fragment and 0 for every other row (the
+ * unkeyed mate of a duplicate pair stays 0); *n_dup is the number of duplicate
+ * fragments.  The pileup is not changed by any of this: a caller leaves the
+ * duplicates out by giving the adds a mapq that is 0 where dup is 1 and
+ * min_mapq = 1.
+ *
+ * Coordinate order.  The key is ref_pos << 1 | strand; the reads with
+ * ref_pos < 0 share one key above all others, whatever their strand byte, so
+ * they come last in input order; ties keep input order everywhere.  ref_len, when not 0, promises
+ * ref_pos < ref_len and lets the call sort bit_length(ref_len << 1) bits
+ * instead of 64 (a ref_pos at or past it sorts with the unplaced reads; with
+ * ref_len == 0 that bound is 2^62). */
+#define MSW_SORT_TILE 4096u
+
+/* Device memory; in place from the caller's view.  key_bits outside 1..64 and
+ * n > 2^31 - 1 are MSW_E_RANGE; n == 0 launches nothing.  Enqueued on `stream`
+ * (NULL = the context's compute stream) with no host synchronisation; the
+ * temporaries (12 bytes per element and 256 counters per tile) are allocated
+ * and freed stream-ordered. */
+int msw_sort_pairs_device(msw_ctx* ctx, uint64_t* keys, uint32_t* vals, uint64_t n, uint32_t key_bits, void* stream);
+
+/* Device memory: aln->ref_pos / nm / cigar_off / cigar / cigar_cap as
+ * msw_aln_pack_device wrote them (aln->n_overflow is not read; read lengths are
+ * not needed), strand (may be NULL) and score per row, n_rows <= 2^31 - 1.
+ * Writes order[n_rows, or n_rows / 2 with pairs], dup[n_rows] and *n_dup (device
+ * u64, may be NULL).  Enqueued on `stream`, no host synchronisation;
+ * temporaries are stream-ordered, about 41 bytes per fragment (57 with
+ * pairs). */
+int msw_markdup_device(msw_ctx* ctx, const msw_aln_t* aln, const uint8_t* strand, const int32_t* score,
+                       uint64_t n_rows, uint64_t ref_len, int pairs, uint32_t* order, uint8_t* dup, uint64_t* n_dup,
+                       void* stream);
+/* The same from host memory, synchronous, in one piece (a duplicate is a
+ * property of the whole set, so there are no chunks).  aln->cigar_off must not
+ * decrease and the ops of every read must lie inside aln->cigar_cap, else
+ * MSW_E_INVALID, as in msw_pileup_add. */
+int msw_markdup(msw_ctx* ctx, const msw_aln_t* aln, const uint8_t* strand, const int32_t* score, uint64_t n_rows,
+                uint64_t ref_len, int pairs, uint32_t* order, uint8_t* dup, uint64_t* n_dup);
+
+/* Coordinate order of n <= 2^31 - 1 records into order[n]: device memory,
+ * enqueued on `stream`; then the same from host memory, synchronous. */
+int msw_aln_order_device(msw_ctx* ctx, const int64_t* ref_pos, const uint8_t* strand, uint64_t n, uint64_t ref_len,
+                         uint32_t* order, void* stream);
+int msw_aln_order(msw_ctx* ctx, const int64_t* ref_pos, const uint8_t* strand, uint64_t n, uint64_t ref_len,
+                  uint32_t* order);
+
 /* Device memory helpers for callers that keep batches resident in HBM. */
 void* msw_dev_alloc(msw_ctx* ctx, size_t bytes);
 void msw_dev_free(msw_ctx* ctx, void* p);

@@ -48,6 +48,7 @@ EXPORTED = (
     "msw_pileup_ins_capacity", "msw_pileup_ins_info", "msw_pileup_ins_sites", "msw_pileup_ins_sites_device",
     "msw_align_batch_banded_device", "msw_align_reads_banded_device", "msw_align_batch_banded",
     "msw_align_reads_banded",
+    "msw_sort_pairs_device", "msw_markdup_device", "msw_markdup", "msw_aln_order_device", "msw_aln_order",
 )
 # include/msw_fastq.h
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
@@ -151,6 +152,7 @@ class CallQParamsT(ctypes.Structure):
 MSW_PILEUP_QSUM = 1
 MSW_PILEUP_INS = 4
 MSW_INS_VOTE_TILE = 1024
+MSW_SORT_TILE = 4096
 
 
 class InsInfoT(ctypes.Structure):
@@ -286,6 +288,12 @@ def _declare(L):
                                        ctypes.POINTER(OutT), ctypes.POINTER(TraceT), ctypes.c_uint64]),
         "msw_align_reads_banded": (I, [P, ctypes.POINTER(ScoringT), P, ctypes.POINTER(ReadBatchT), ctypes.c_uint32,
                                        ctypes.POINTER(OutT), P, P, ctypes.POINTER(TraceT), ctypes.c_uint64]),
+        "msw_sort_pairs_device": (I, [P, P, P, ctypes.c_uint64, ctypes.c_uint32, P]),
+        "msw_markdup_device": (I, [P, ctypes.POINTER(AlnT), P, P, ctypes.c_uint64, ctypes.c_uint64, I, P, P, P, P]),
+        "msw_markdup": (I, [P, ctypes.POINTER(AlnT), P, P, ctypes.c_uint64, ctypes.c_uint64, I, P, P,
+                            ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_aln_order_device": (I, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P]),
+        "msw_aln_order": (I, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P]),
         "msw_plan_create": (I, [P, ctypes.POINTER(ScoringT), P, P, ctypes.c_uint64, ctypes.POINTER(P)]),
         "msw_align_batch_planned": (I, [P, P, ctypes.POINTER(BatchT), ctypes.POINTER(OutT), P]),
         "msw_plan_destroy": (None, [P]),

@@ -26,11 +26,12 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MSW_E_INVALID, MSW_PILEUP_INS, MSW_PILEUP_QSUM, InsInfoT, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PairParamsT, PileupSummaryT,
+from ._lib import (MSW_E_INVALID, MSW_PILEUP_INS, MSW_PILEUP_QSUM, MSW_SORT_TILE, InsInfoT, AlnT, BatchT, CallParamsT, CallQParamsT, CandT, DeviceInfoT, IndexInfoT, MapqT, MswError, OutT, PairParamsT, PileupSummaryT,
                    ReadBatchT, ScoringT, SeedAltT, SeedOutT, SeedParamsT, StatsT, TraceT, check, lib)
 
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
 GPU_MAX_WORK_GROUPS = 1_000_000     # gpu.rs:10
+SORT_TILE = MSW_SORT_TILE           # elements one block of a sort pass ranks and moves (include/msw.h)
 
 
 @dataclass
@@ -972,6 +973,108 @@ class Context:
         check(lib().msw_insert_hist_device(self.handle, ctypes.c_void_p(tlen_ptr or None),
                                            ctypes.c_void_p(mapq_ptr or None), n_pairs, min_mapq,
                                            ctypes.c_void_p(hist_ptr or None), ctypes.c_void_p(stream or None)))
+
+    # -- sorting and duplicates (include/msw.h, "Sorting and duplicates") ---------------
+    def sort_pairs_device(self, keys_ptr: int, vals_ptr: int, n: int, key_bits: int = 64, stream: int = 0) -> None:
+        """Enqueue the stable sort of device uint64[n] ``keys_ptr`` and uint32[n]
+        ``vals_ptr`` (0: keys only) by the low ``key_bits`` bits of the keys,
+        in place (msw_sort_pairs_device)."""
+        check(lib().msw_sort_pairs_device(self.handle, ctypes.c_void_p(keys_ptr or None),
+                                          ctypes.c_void_p(vals_ptr or None), n, key_bits,
+                                          ctypes.c_void_p(stream or None)))
+
+    def sort_pairs(self, keys, vals=None, key_bits: int = 64):
+        """The same for host arrays: returns ``(keys, vals)`` sorted (``vals``
+        None when none were given); the arguments are left as they are."""
+        keys = np.array(keys, dtype=np.uint64, ndmin=1)
+        n = keys.shape[0]
+        if vals is not None:
+            vals = np.array(vals, dtype=np.uint32, ndmin=1)
+            if vals.shape != keys.shape:
+                raise MswError(MSW_E_INVALID, "keys and vals disagree on the number of elements")
+        L, h = lib(), self.handle
+        d_keys = L.msw_dev_alloc(h, max(1, 12 * n))
+        if not d_keys:
+            raise MswError(MSW_E_INVALID, "sort_pairs: device allocation failed")
+        d_vals = d_keys + 8 * n if vals is not None else 0
+        try:
+            if n:
+                check(L.msw_memcpy_h2d(h, d_keys, _ptr(keys), 8 * n))
+                if vals is not None:
+                    check(L.msw_memcpy_h2d(h, d_vals, _ptr(vals), 4 * n))
+            self.sort_pairs_device(d_keys, d_vals, n, key_bits)
+            check(L.msw_synchronize(h))
+            if n:
+                check(L.msw_memcpy_d2h(h, _ptr(keys), d_keys, 8 * n))
+                if vals is not None:
+                    check(L.msw_memcpy_d2h(h, _ptr(vals), d_vals, 4 * n))
+        finally:
+            L.msw_dev_free(h, d_keys)
+        return keys, vals
+
+    def mark_duplicates_device(self, ref_pos_ptr: int, nm_ptr: int, cigar_off_ptr: int, cigar_ptr: int,
+                               cigar_cap: int, strand_ptr: int, score_ptr: int, n_rows: int, ref_len: int,
+                               order_ptr: int, dup_ptr: int, n_dup_ptr: int = 0, pairs: bool = False,
+                               stream: int = 0) -> None:
+        """Enqueue the duplicate flags of n_rows device-resident records (raw
+        device pointers, the arrays msw_aln_pack_device wrote; msw_markdup_device)."""
+        aln = AlnT(ref_pos_ptr or None, nm_ptr or None, cigar_off_ptr or None, cigar_ptr or None, cigar_cap, None)
+        check(lib().msw_markdup_device(self.handle, ctypes.byref(aln), ctypes.c_void_p(strand_ptr or None),
+                                       ctypes.c_void_p(score_ptr or None), n_rows, ref_len, 1 if pairs else 0,
+                                       ctypes.c_void_p(order_ptr or None), ctypes.c_void_p(dup_ptr or None),
+                                       ctypes.c_void_p(n_dup_ptr or None), ctypes.c_void_p(stream or None)))
+
+    def mark_duplicates(self, ref_pos, nm, cigars, strand, score, ref_len: int, pairs: bool = False):
+        """Duplicate flags by unclipped 5' position (msw_markdup): records as
+        :meth:`map_reads` / :meth:`map_pairs` return them (``cigars`` in the
+        forms :meth:`Pileup.add` takes, ``strand`` may be None), ``ref_len`` the
+        genome's length; with ``pairs`` rows 2p and 2p + 1 are mates.  Returns
+        ``(dup, order, n_dup)``: uint8 per row, the fragments in (K1, K2) order,
+        and the number of duplicate fragments.  Leave the duplicates out of a
+        pileup with ``mapq=np.where(dup, 0, mapq), min_mapq=1``."""
+        ref_pos = np.ascontiguousarray(ref_pos, dtype=np.int64)
+        nm = np.ascontiguousarray(nm, dtype=np.int32)
+        score = np.ascontiguousarray(score, dtype=np.int32)
+        B = ref_pos.shape[0]
+        if strand is not None:
+            strand = np.ascontiguousarray(strand, dtype=np.uint8)
+        if not (nm.shape[0] == score.shape[0] == len(cigars) == B) or (strand is not None and strand.shape[0] != B):
+            raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        off = np.zeros(B + 1, np.uint32)
+        off[1:] = np.cumsum([0 if c is None else len(c) for c in cigars], dtype=np.uint64)
+        parts = [np.asarray(c, np.uint32) for c in cigars if c is not None and len(c)]
+        cig = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1, np.uint32), dtype=np.uint32)
+        aln = AlnT(_ptr(ref_pos) or None, _ptr(nm) or None, _ptr(off), _ptr(cig), int(off[B]), None)
+        dup = np.zeros(B, np.uint8)
+        order = np.zeros(B // 2 if pairs else B, np.uint32)
+        n_dup = ctypes.c_uint64(0)
+        check(lib().msw_markdup(self.handle, ctypes.byref(aln), _ptr(strand) if B else None,
+                                _ptr(score) if B else None, B, ref_len, 1 if pairs else 0,
+                                _ptr(order) if order.size else None, _ptr(dup) if B else None, ctypes.byref(n_dup)))
+        return dup, order, int(n_dup.value)
+
+    def coordinate_order_device(self, ref_pos_ptr: int, strand_ptr: int, n: int, order_ptr: int, ref_len: int = 0,
+                                stream: int = 0) -> None:
+        """Enqueue the coordinate order of n device-resident records
+        (msw_aln_order_device)."""
+        check(lib().msw_aln_order_device(self.handle, ctypes.c_void_p(ref_pos_ptr or None),
+                                         ctypes.c_void_p(strand_ptr or None), n, ref_len,
+                                         ctypes.c_void_p(order_ptr or None), ctypes.c_void_p(stream or None)))
+
+    def coordinate_order(self, ref_pos, strand=None, ref_len: int = 0) -> np.ndarray:
+        """The records' indices in coordinate order (msw_aln_order): by
+        ``ref_pos``, then strand, ties in input order, ``ref_pos < 0`` last.
+        ``ref_len`` (0: unknown) bounds ``ref_pos`` and shortens the sort."""
+        ref_pos = np.ascontiguousarray(ref_pos, dtype=np.int64)
+        n = ref_pos.shape[0]
+        if strand is not None:
+            strand = np.ascontiguousarray(strand, dtype=np.uint8)
+            if strand.shape[0] != n:
+                raise MswError(MSW_E_INVALID, "batch arrays disagree on the number of reads")
+        order = np.zeros(n, np.uint32)
+        check(lib().msw_aln_order(self.handle, _ptr(ref_pos) if n else None, _ptr(strand) if n else None, n, ref_len,
+                                  _ptr(order) if n else None))
+        return order
 
     # -- HBM-resident batches ----------------------------------------------------------
     def align_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int,

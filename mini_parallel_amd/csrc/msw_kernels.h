@@ -646,6 +646,49 @@ struct BandParams {
 // mode 0: score, 1: score + best cell, 2: score + best cell + traceback
 hipError_t launch_sw_band(const BandParams& p, bool affine, int mode, hipStream_t stream);
 
+// Sorting and duplicates (msw_sort.hip, msw_markdup.hip; the contract is in
+// include/msw.h, "Sorting and duplicates").
+static_assert(MSW_SORT_TILE == 4096, "msw.h names the sort's tile");
+constexpr uint32_t kSortTile = MSW_SORT_TILE;  // keys one block of a pass ranks and moves
+// bytes of temporaries a sort of n elements takes: the second key (and value) array, the 256 x tiles digit
+// counts and their scan's block sums, each 256-byte aligned
+uint64_t sort_tmp_bytes(uint64_t n, bool vals);
+// The stable LSD sort of (keys, vals) by the low key_bits bits, in place from the caller's view; vals may be
+// null.  1 <= key_bits <= 64 and n <= 2^31 - 1, else hipErrorInvalidValue and nothing launched; n == 0
+// launches nothing.  tmp: sort_tmp_bytes(n, vals != null) bytes, 256-byte aligned.
+hipError_t launch_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t n, uint32_t key_bits, void* tmp,
+                             hipStream_t st);
+struct MarkdupParams {
+    const int64_t* ref_pos;
+    const int32_t* nm;
+    const uint32_t* cigar_off;
+    const uint32_t* cigar;
+    uint64_t cigar_cap;
+    const uint8_t* strand;    // or null
+    const int32_t* score;
+    uint64_t frags;           // reads, or pairs of rows
+    uint64_t k_none;
+    uint32_t pairs;
+    uint32_t* order;          // [frags]
+    uint8_t* dup;             // [rows]
+    unsigned long long* n_dup;  // or null
+    // temporaries, laid out by launch_markdup
+    uint64_t* work;           // [frags] the keys being sorted; K1 by rank from the last sort on
+    uint64_t* k1;             // [frags] pairs only: K1, K2 by fragment
+    uint64_t* k2;
+    uint64_t* pk;             // [frags] quality << 31 | (2^31 - 1 - fragment)
+    uint8_t* km;              // [frags] bit 0 / 1: the fragment's first / second row is keyed
+    uint32_t* rid;            // [frags] run id by rank
+    unsigned long long* best; // [frags] by run id
+};
+uint64_t markdup_tmp_bytes(uint64_t frags, bool pairs);
+// p's temporaries are set here; frags == 0 (tmp not read) clears *n_dup only
+hipError_t launch_markdup(MarkdupParams p, uint32_t key_bits, void* tmp, hipStream_t st);
+uint64_t aln_order_tmp_bytes(uint64_t n);
+// keys min(ref_pos << 1 | strand, k_last), ref_pos < 0 -> k_last; n >= 1
+hipError_t launch_aln_order(const int64_t* ref_pos, const uint8_t* strand, uint64_t n, uint64_t k_last,
+                            uint32_t key_bits, uint32_t* order, void* tmp, hipStream_t st);
+
 // smith_waterman_align restated: result must be zeroed before the launch.
 hipError_t launch_compat(const uint8_t* s1, const uint8_t* s2, int32_t* result, uint64_t L,
                          uint32_t W, uint64_t G, hipStream_t stream);

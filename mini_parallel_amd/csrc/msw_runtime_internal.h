@@ -5,6 +5,7 @@
 //   msw_rt_map.cpp     index, seeds, candidates, MAPQ, pairs, the map drivers
 //   msw_rt_pileup.cpp  pileup, variant calls
 //   msw_rt_band.cpp    banded alignment
+//   msw_rt_sort.cpp    sorting and duplicates
 // Each section of include/msw.h is implemented in one of them; nothing but
 // this header is shared between them.  Not installed, not part of the C ABI.
 #pragma once
