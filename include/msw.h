@@ -1250,6 +1250,62 @@ int msw_align_reads_banded(msw_ctx* ctx, const msw_scoring_t* sc, const msw_geno
                            uint32_t w, msw_out_t* out, int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr,
                            uint64_t chunk_pairs);
 
+/* Banded end-to-end alignment: the whole read, from its first base to its
+ * last, against a window that is free at both ends (semi-global), inside the
+ * band of "Banded alignment".  Notation is that section's: read length L,
+ * window length W, centre c, half-width w; cell (i, j) EXISTS iff
+ *   0 <= i < L,  0 <= j < W  and  |j - i - c| <= w.
+ *
+ * Start row.  A virtual cell (-1, j) exists for -1 <= j < W with
+ * |j + 1 - c| <= w and has H = 0; E and F are -inf in the whole virtual row.
+ * There is no virtual column: (i, -1) does not exist for i >= 0.
+ *
+ * Recurrence, over the existing cells; H, E and F are -inf at every cell that
+ * does not exist, -inf plus anything is -inf, and there is NO floor at 0:
+ *   linear:  H(i,j) = max(H(i-1,j-1) + s(i,j), H(i-1,j) - g, H(i,j-1) - g)
+ *   affine, goe = gap_open + gap_extend:
+ *            F(i,j) = max(H(i-1,j) - goe, F(i-1,j) - gap_extend)   up, op I
+ *            E(i,j) = max(H(i,j-1) - goe, E(i,j-1) - gap_extend)   left, op D
+ *            H(i,j) = max(H(i-1,j-1) + s(i,j), F(i,j), E(i,j))
+ *
+ * Result.  The maximum H over the existing cells of row L - 1, then the
+ * smallest j: `score` (it may be <= 0), end_i = L - 1, end_j.  If no cell of
+ * row L - 1 can be reached (its H is -inf everywhere), score = MSW_E2E_NONE,
+ * the ends are (-1, -1), the starts (-1, -1) and n_cigar 0: that covers L = 0,
+ * L > max_read_len, an unplaced read (INT64_MIN) and W = 0.
+ *
+ * Traceback.  The walk of "Traceback" above, unchanged in precedence (diagonal
+ * > I > D, open > extend), on THESE H, E and F, from (L - 1, end_j) until it
+ * steps into the virtual row at some (-1, j0): start_i = 0, start_j = j0 + 1.
+ * The ops, run-length merged as in every msw_trace_t row, consume exactly L
+ * read bases (M + I = L); they may begin with I and never begin with D, and
+ * they end with D only on a zero-cost tie, which the smallest-j rule already
+ * removes.  n_cigar beyond the stride writes the count alone, as everywhere.
+ *
+ * Records.  With start_i = 0 and end_i = L - 1 the record packer of "Alignment
+ * records" takes out / tr / win_pos_out unchanged and emits no soft clip; it
+ * treats score <= 0 (MSW_E2E_NONE included) as unaligned, as it does today.
+ *
+ * Limits are the banded section's: w <= 63, max_read_len + 2w <= 32,767,
+ * traced reads <= 1008 rows, scoring schemes as everywhere; with those every
+ * true value fits an i32 many times over.  The genome form implies the same
+ * window, max(0, c - w) clipped to the genome, with the same win_pos_out and
+ * win_len_out.  The four calls take the arguments of their local twins. */
+#define MSW_E2E_NONE (-2147483647 - 1)
+int msw_align_batch_banded_e2e_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch,
+                                      const int32_t* diag, uint32_t w, msw_out_t* out, msw_trace_t* tr,
+                                      uint32_t max_read_len, void* stream);
+int msw_align_reads_banded_e2e_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                                      const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
+                                      const int64_t* diag, uint64_t n, uint32_t w, uint32_t max_read_len,
+                                      msw_out_t* out, int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr,
+                                      void* stream);
+int msw_align_batch_banded_e2e(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* batch, const int32_t* diag,
+                               uint32_t w, msw_out_t* out, msw_trace_t* tr, uint64_t chunk_pairs);
+int msw_align_reads_banded_e2e(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                               const msw_read_batch_t* batch, uint32_t w, msw_out_t* out, int64_t* win_pos_out,
+                               uint16_t* win_len_out, msw_trace_t* tr, uint64_t chunk_pairs);
+
 /* Sorting and duplicates: a device-wide stable sort, the coordinate order of
  * records, and duplicate flags by unclipped 5' position.  Everything is
  * integers; the results are functions of the inputs alone, whatever order the

@@ -10,7 +10,7 @@ from .aligner import (AFFINE, CallParams, PairParams, QualParams, Variants, GPU_
                       Context, Genome, GpuAlignmentResult, GpuDevice, Index, Pending, Pileup, Scoring, cigar_string,
                       get_chunk_size_reads, get_context, get_gpu_devices, gpu_align,
                       gpu_align_chunk_self, insert_bounds, is_gpu_available, pack_batch, pinned_empty, reverse_complement,
-                      INS_SITE_DTYPE, SORT_TILE, ins_sequence)
+                      INS_SITE_DTYPE, SORT_TILE, E2E_NONE, ins_sequence)
 from .alnfile import (AlnBlock, Alignments, read_alignments, read_pileup, read_qsums, read_variants,  # noqa: F401
                       read_variants_qual, write_alignments, write_pileup, write_qsums, write_variants, write_vcf)
 

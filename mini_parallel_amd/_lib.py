@@ -48,6 +48,8 @@ EXPORTED = (
     "msw_pileup_ins_capacity", "msw_pileup_ins_info", "msw_pileup_ins_sites", "msw_pileup_ins_sites_device",
     "msw_align_batch_banded_device", "msw_align_reads_banded_device", "msw_align_batch_banded",
     "msw_align_reads_banded",
+    "msw_align_batch_banded_e2e_device", "msw_align_reads_banded_e2e_device", "msw_align_batch_banded_e2e",
+    "msw_align_reads_banded_e2e",
     "msw_sort_pairs_device", "msw_markdup_device", "msw_markdup", "msw_aln_order_device", "msw_aln_order",
 )
 # include/msw_fastq.h
@@ -355,6 +357,10 @@ def _declare(L):
                        ("msw_trace_reads_long_device", "msw_trace_reads_device"),
                        ("msw_align_reads_trace_long", "msw_align_reads_trace")):
         sigs[name] = sigs[base]
+    # and the end-to-end banded calls those of their local twins
+    for base in ("msw_align_batch_banded_device", "msw_align_reads_banded_device", "msw_align_batch_banded",
+                 "msw_align_reads_banded"):
+        sigs[base.replace("_banded", "_banded_e2e")] = sigs[base]
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
         fn.restype = res

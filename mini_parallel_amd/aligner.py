@@ -32,6 +32,7 @@ from ._lib import (MSW_E_INVALID, MSW_PILEUP_INS, MSW_PILEUP_QSUM, MSW_SORT_TILE
 GPU_WORK_GROUP_SIZE = 1024          # gpu.rs:9
 GPU_MAX_WORK_GROUPS = 1_000_000     # gpu.rs:10
 SORT_TILE = MSW_SORT_TILE           # elements one block of a sort pass ranks and moves (include/msw.h)
+E2E_NONE = -(1 << 31)               # MSW_E2E_NONE: the score of an end-to-end call without an alignment
 
 
 @dataclass
@@ -397,13 +398,18 @@ class Context:
     # -- banded alignment (include/msw.h, "Banded alignment") ---------------------------
     def align_batch_banded(self, reads: np.ndarray, read_len: np.ndarray, wins: np.ndarray, win_len: np.ndarray,
                            diag: np.ndarray, w: int, scoring: Scoring = LINEAR, trace: bool = False,
-                           cigar_stride: Optional[int] = None, chunk_pairs: int = 0):
+                           cigar_stride: Optional[int] = None, chunk_pairs: int = 0, end_to_end: bool = False):
         """:meth:`align_batch` inside a diagonal band (msw_align_batch_banded):
         pair p scores only the cells with ``|j - i - diag[p]| <= w`` (0 <= w <=
         63), every other cell counting as H = 0.  Returns (score, end_i, end_j)
         like :meth:`align_batch`, or with ``trace`` what
         :meth:`align_batch_trace` returns, the alignment being the canonical
-        one of the banded recurrence (traced reads <= 1008 bases)."""
+        one of the banded recurrence (traced reads <= 1008 bases).
+
+        ``end_to_end`` aligns the whole read instead (msw_align_batch_banded_e2e,
+        include/msw.h "Banded end-to-end alignment"): no floor at 0, the window
+        free at both ends, start_i = 0 and end_i = len - 1, a score that may be
+        negative, and ``E2E_NONE`` with (-1, -1) where no alignment exists."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         wins = np.ascontiguousarray(wins, dtype=np.uint8)
         read_len = np.ascontiguousarray(read_len, dtype=np.uint16)
@@ -415,16 +421,18 @@ class Context:
         batch = BatchT(_ptr(reads), _ptr(wins), _ptr(read_len), _ptr(win_len),
                        reads.shape[1] if reads.ndim == 2 else 0, wins.shape[1] if wins.ndim == 2 else 0, B)
         sc = _scoring_c(scoring)
+        fn = lib().msw_align_batch_banded_e2e if end_to_end else lib().msw_align_batch_banded
 
         def call(out, tr):
-            check(lib().msw_align_batch_banded(self.handle, ctypes.byref(sc), ctypes.byref(batch), _ptr(diag), w,
-                                               ctypes.byref(out), ctypes.byref(tr) if tr else None, chunk_pairs))
+            check(fn(self.handle, ctypes.byref(sc), ctypes.byref(batch), _ptr(diag), w, ctypes.byref(out),
+                     ctypes.byref(tr) if tr else None, chunk_pairs))
         return self._traced(B, scoring.want_coords or trace, trace, cigar_stride, call)
 
     def align_reads_banded(self, genome: "Genome", reads: np.ndarray, read_len: np.ndarray, diag: np.ndarray,
                            w: int, scoring: Scoring = LINEAR, trace: bool = False,
-                           cigar_stride: Optional[int] = None, chunk_pairs: int = 0):
-        """Reads against the genome inside a band (msw_align_reads_banded):
+                           cigar_stride: Optional[int] = None, chunk_pairs: int = 0, end_to_end: bool = False):
+        """Reads against the genome inside a band (msw_align_reads_banded, with
+        ``end_to_end`` msw_align_reads_banded_e2e):
         ``diag[p]`` (int64) is the genome coordinate of the band's centre for
         read base 0, ``INT64_MIN`` an unplaced read.  Returns what
         :meth:`align_batch_banded` returns followed by (win_pos int64[B],
@@ -439,11 +447,11 @@ class Context:
         batch = ReadBatchT(_ptr(reads), _ptr(read_len), reads.shape[1] if reads.ndim == 2 else 0, _ptr(diag), 0, B)
         sc = _scoring_c(scoring)
         win_pos, wlen = np.empty(B, np.int64), np.empty(B, np.uint16)
+        fn = lib().msw_align_reads_banded_e2e if end_to_end else lib().msw_align_reads_banded
 
         def call(out, tr):
-            check(lib().msw_align_reads_banded(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch), w,
-                                               ctypes.byref(out), _fresh_ptr(win_pos), _fresh_ptr(wlen),
-                                               ctypes.byref(tr) if tr else None, chunk_pairs))
+            check(fn(self.handle, ctypes.byref(sc), genome.handle, ctypes.byref(batch), w, ctypes.byref(out),
+                     _fresh_ptr(win_pos), _fresh_ptr(wlen), ctypes.byref(tr) if tr else None, chunk_pairs))
         return self._traced(B, scoring.want_coords or trace, trace, cigar_stride, call) + (win_pos, wlen)
 
     def trace_batch_device(self, reads_ptr: int, read_len_ptr: int, wins_ptr: int, win_len_ptr: int,

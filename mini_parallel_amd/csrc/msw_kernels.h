@@ -645,6 +645,10 @@ struct BandParams {
 };
 // mode 0: score, 1: score + best cell, 2: score + best cell + traceback
 hipError_t launch_sw_band(const BandParams& p, bool affine, int mode, hipStream_t stream);
+// Banded end-to-end alignment (sw_band_e2e_kernel, msw_e2e.hip; include/msw.h, "Banded end-to-end
+// alignment"): the same parameters, modes and LDS sizes (the start row keeps no direction codes); a read
+// beyond max_rows, an unplaced read and a pair whose last row has no reachable cell score MSW_E2E_NONE.
+hipError_t launch_sw_band_e2e(const BandParams& p, bool affine, int mode, hipStream_t stream);
 
 // Sorting and duplicates (msw_sort.hip, msw_markdup.hip; the contract is in
 // include/msw.h, "Sorting and duplicates").

@@ -1,6 +1,7 @@
-// msw_rt_band.cpp -- banded alignment (include/msw.h, "Banded alignment"):
-// the limit checks, the two device calls and their chunked host drivers.
-// The kernel: msw_band.hip.
+// msw_rt_band.cpp -- banded alignment (include/msw.h, "Banded alignment" and
+// "Banded end-to-end alignment"): the limit checks, the two device calls and
+// their chunked host drivers, each once for both modes (`e2e` picks the
+// kernel).  The kernels: msw_band.hip, msw_e2e.hip.
 #include "msw_runtime_internal.h"
 #include "msw_trace_sizes.h"
 
@@ -45,10 +46,13 @@ static void band_call_params(msw::BandParams& p, const msw_scoring_t* sc, uint64
     }
 }
 
-extern "C" {
+static hipError_t launch_band(const msw::BandParams& p, bool e2e, bool affine, int mode, hipStream_t st) {
+    return e2e ? msw::launch_sw_band_e2e(p, affine, mode, st) : msw::launch_sw_band(p, affine, mode, st);
+}
 
-int msw_align_batch_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const int32_t* diag,
-                                  uint32_t w, msw_out_t* out, msw_trace_t* tr, uint32_t max_read_len, void* stream) {
+static int batch_banded_device(bool e2e, msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b,
+                               const int32_t* diag, uint32_t w, msw_out_t* out, msw_trace_t* tr,
+                               uint32_t max_read_len, void* stream) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");
     if (!b) return fail(MSW_E_INVALID, "batch is NULL");
     bool coords = false;
@@ -70,14 +74,14 @@ int msw_align_batch_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const m
     p.win_stride = b->win_stride;
     p.diag32 = diag;
     band_call_params(p, sc, b->n_pairs, w, max_read_len, out, tr, coords);
-    HIP_TRY(msw::launch_sw_band(p, sch.affine, tr ? 2 : (coords ? 1 : 0), call_stream(ctx, stream)));
+    HIP_TRY(launch_band(p, e2e, sch.affine, tr ? 2 : (coords ? 1 : 0), call_stream(ctx, stream)));
     return MSW_OK;
 }
 
-int msw_align_reads_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
-                                  const uint16_t* read_len, uint32_t read_stride, const int64_t* diag, uint64_t n,
-                                  uint32_t w, uint32_t max_read_len, msw_out_t* out, int64_t* win_pos_out,
-                                  uint16_t* win_len_out, msw_trace_t* tr, void* stream) {
+static int reads_banded_device(bool e2e, msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                               const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
+                               const int64_t* diag, uint64_t n, uint32_t w, uint32_t max_read_len, msw_out_t* out,
+                               int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr, void* stream) {
     if (!ctx || !g) return fail(MSW_E_INVALID, "ctx/genome is NULL");
     if (g->ctx != ctx) return fail(MSW_E_INVALID, "genome belongs to another context");
     bool coords = false;
@@ -100,13 +104,13 @@ int msw_align_reads_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const m
     p.win_pos_out = win_pos_out;
     p.win_len_out = win_len_out;
     band_call_params(p, sc, n, w, max_read_len, out, tr, coords);
-    HIP_TRY(msw::launch_sw_band(p, sch.affine, tr ? 2 : (coords ? 1 : 0), call_stream(ctx, stream)));
+    HIP_TRY(launch_band(p, e2e, sch.affine, tr ? 2 : (coords ? 1 : 0), call_stream(ctx, stream)));
     return MSW_OK;
 }
 
 // Both host drivers: per chunk upload, one launch, download; simple and
 // synchronous like msw_align_batch_trace.  g == NULL: the padded form.
-static int banded_host(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+static int banded_host(bool e2e, msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
                        const uint16_t* read_len, size_t rs, const uint8_t* wins, const uint16_t* win_len, size_t ws,
                        const int32_t* diag32, const int64_t* diag64, uint64_t n, uint32_t w, msw_out_t* out,
                        int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr, uint64_t chunk_pairs) {
@@ -157,11 +161,11 @@ static int banded_host(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* 
         msw_out_t dout = {d_score, d_ei, d_ej};
         msw_trace_t dtr = {d_si, d_sj, d_nc, d_cig, (uint32_t)cs};
         if (g) {
-            rc = msw_align_reads_banded_device(ctx, sc, g, d_reads, d_rl, (uint32_t)rs, d_d64, c, w, cm, &dout, d_pos,
-                                               d_wl, tr ? &dtr : nullptr, st);
+            rc = reads_banded_device(e2e, ctx, sc, g, d_reads, d_rl, (uint32_t)rs, d_d64, c, w, cm, &dout, d_pos, d_wl,
+                                     tr ? &dtr : nullptr, st);
         } else {
             msw_batch_t db = {d_reads, d_wins, d_rl, d_wl, (uint32_t)rs, (uint32_t)ws, c};
-            rc = msw_align_batch_banded_device(ctx, sc, &db, d_d32, w, &dout, tr ? &dtr : nullptr, cm, st);
+            rc = batch_banded_device(e2e, ctx, sc, &db, d_d32, w, &dout, tr ? &dtr : nullptr, cm, st);
         }
         if (rc) break;
         cp.down(out->score + lo, d_score, c * 4);
@@ -182,20 +186,68 @@ static int banded_host(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* 
     return cp.finish(rc, "banded alignment");
 }
 
+static int batch_banded_host(bool e2e, msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b,
+                             const int32_t* diag, uint32_t w, msw_out_t* out, msw_trace_t* tr, uint64_t chunk_pairs) {
+    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
+    return banded_host(e2e, ctx, sc, nullptr, b->reads, b->read_len, b->read_stride, b->wins, b->win_len,
+                       b->win_stride, diag, nullptr, b->n_pairs, w, out, nullptr, nullptr, tr, chunk_pairs);
+}
+
+static int reads_banded_host(bool e2e, msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                             const msw_read_batch_t* b, uint32_t w, msw_out_t* out, int64_t* win_pos_out,
+                             uint16_t* win_len_out, msw_trace_t* tr, uint64_t chunk_pairs) {
+    if (!g) return fail(MSW_E_INVALID, "genome is NULL");
+    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
+    return banded_host(e2e, ctx, sc, g, b->reads, b->read_len, b->read_stride, nullptr, nullptr, 0, nullptr,
+                       b->win_pos, b->n_pairs, w, out, win_pos_out, win_len_out, tr, chunk_pairs);
+}
+
+extern "C" {
+
+int msw_align_batch_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const int32_t* diag,
+                                  uint32_t w, msw_out_t* out, msw_trace_t* tr, uint32_t max_read_len, void* stream) {
+    return batch_banded_device(false, ctx, sc, b, diag, w, out, tr, max_read_len, stream);
+}
+int msw_align_batch_banded_e2e_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b,
+                                      const int32_t* diag, uint32_t w, msw_out_t* out, msw_trace_t* tr,
+                                      uint32_t max_read_len, void* stream) {
+    return batch_banded_device(true, ctx, sc, b, diag, w, out, tr, max_read_len, stream);
+}
+
+int msw_align_reads_banded_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const uint8_t* reads,
+                                  const uint16_t* read_len, uint32_t read_stride, const int64_t* diag, uint64_t n,
+                                  uint32_t w, uint32_t max_read_len, msw_out_t* out, int64_t* win_pos_out,
+                                  uint16_t* win_len_out, msw_trace_t* tr, void* stream) {
+    return reads_banded_device(false, ctx, sc, g, reads, read_len, read_stride, diag, n, w, max_read_len, out,
+                               win_pos_out, win_len_out, tr, stream);
+}
+int msw_align_reads_banded_e2e_device(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                                      const uint8_t* reads, const uint16_t* read_len, uint32_t read_stride,
+                                      const int64_t* diag, uint64_t n, uint32_t w, uint32_t max_read_len,
+                                      msw_out_t* out, int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr,
+                                      void* stream) {
+    return reads_banded_device(true, ctx, sc, g, reads, read_len, read_stride, diag, n, w, max_read_len, out,
+                               win_pos_out, win_len_out, tr, stream);
+}
+
 int msw_align_batch_banded(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const int32_t* diag,
                            uint32_t w, msw_out_t* out, msw_trace_t* tr, uint64_t chunk_pairs) {
-    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
-    return banded_host(ctx, sc, nullptr, b->reads, b->read_len, b->read_stride, b->wins, b->win_len, b->win_stride,
-                       diag, nullptr, b->n_pairs, w, out, nullptr, nullptr, tr, chunk_pairs);
+    return batch_banded_host(false, ctx, sc, b, diag, w, out, tr, chunk_pairs);
+}
+int msw_align_batch_banded_e2e(msw_ctx* ctx, const msw_scoring_t* sc, const msw_batch_t* b, const int32_t* diag,
+                               uint32_t w, msw_out_t* out, msw_trace_t* tr, uint64_t chunk_pairs) {
+    return batch_banded_host(true, ctx, sc, b, diag, w, out, tr, chunk_pairs);
 }
 
 int msw_align_reads_banded(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g, const msw_read_batch_t* b,
                            uint32_t w, msw_out_t* out, int64_t* win_pos_out, uint16_t* win_len_out, msw_trace_t* tr,
                            uint64_t chunk_pairs) {
-    if (!g) return fail(MSW_E_INVALID, "genome is NULL");
-    if (!b) return fail(MSW_E_INVALID, "batch is NULL");
-    return banded_host(ctx, sc, g, b->reads, b->read_len, b->read_stride, nullptr, nullptr, 0, nullptr, b->win_pos,
-                       b->n_pairs, w, out, win_pos_out, win_len_out, tr, chunk_pairs);
+    return reads_banded_host(false, ctx, sc, g, b, w, out, win_pos_out, win_len_out, tr, chunk_pairs);
+}
+int msw_align_reads_banded_e2e(msw_ctx* ctx, const msw_scoring_t* sc, const msw_genome* g,
+                               const msw_read_batch_t* b, uint32_t w, msw_out_t* out, int64_t* win_pos_out,
+                               uint16_t* win_len_out, msw_trace_t* tr, uint64_t chunk_pairs) {
+    return reads_banded_host(true, ctx, sc, g, b, w, out, win_pos_out, win_len_out, tr, chunk_pairs);
 }
 
 }  // extern "C"

@@ -13,7 +13,12 @@ rounds in one process so their ranges can be compared.
 
 Each case runs linear score-only and affine with the best cell.  `same` is the
 share of reads whose banded score equals the full one.  One JSON line per case.
-  python3 tools/band_bench.py [--cases 10000x150,1000000x150,4000x1000] [--rounds 5]"""
+  python3 tools/band_bench.py [--cases 10000x150,1000000x150,4000x1000] [--rounds 5]
+
+--end-to-end times msw_align_reads_banded_e2e_device against the local banded
+call instead, the two alternated at every width on the same diagonals: linear
+score-only, affine with the end cell, and (reads up to 1008 bases) affine score
++ trace at w = 16.  `aligned` is the share of reads the end-to-end call aligns."""
 import argparse
 import ctypes
 import json
@@ -34,6 +39,7 @@ def main():
     ap.add_argument("--min-ms", type=float, default=300.0, help="GPU time a timed window should fill")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--stride", type=int, default=16, help="CIGAR ops per read the trace rows hold")
+    ap.add_argument("--end-to-end", action="store_true", help="the end-to-end launch against the local banded one")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     import torch
@@ -80,10 +86,44 @@ def main():
                                                d_rl.data_ptr(), rs, d_pos.data_ptr(), n, W, mr, ctypes.byref(out),
                                                None, s))
 
-        def band(sc_c, w, tr=None):
-            check(lib().msw_align_reads_banded_device(ctx.handle, ctypes.byref(sc_c), genome.handle, d_R.data_ptr(),
-                                                      d_rl.data_ptr(), rs, d_diag.data_ptr(), n, w, mr,
-                                                      ctypes.byref(out_b), None, None, tr, s))
+        def band(sc_c, w, tr=None, e2e=False):
+            fn = lib().msw_align_reads_banded_e2e_device if e2e else lib().msw_align_reads_banded_device
+            check(fn(ctx.handle, ctypes.byref(sc_c), genome.handle, d_R.data_ptr(), d_rl.data_ptr(), rs,
+                     d_diag.data_ptr(), n, w, mr, ctypes.byref(out_b), None, None, tr, s))
+
+        def against_local(rec, sc_c, w, tr=None):
+            """local and end-to-end launches alternated; ms per launch and pairs/s, min-max over the rounds"""
+            ms = {False: [], True: []}
+            for _ in range(args.rounds):
+                for e2e in (False, True):
+                    ms[e2e].append(round(timed(lambda: band(sc_c, w, tr, e2e)), 4))
+            rec[f"w{w}_local_ms"], rec[f"w{w}_e2e_ms"] = ms[False], ms[True]
+            for e2e, key in ((False, "local"), (True, "e2e")):
+                rec[f"w{w}_{key}_pairs_per_s"] = [round(n / (max(ms[e2e]) * 1e-3)), round(n / (min(ms[e2e]) * 1e-3))]
+            rec[f"w{w}_e2e_over_local"] = round(min(ms[True]) / min(ms[False]), 3)
+            torch.cuda.synchronize()   # the last timed launch was end to end
+            rec[f"w{w}_aligned"] = round(float((score_b.cpu().numpy() > -(1 << 31)).mean()), 4)
+
+        if args.end_to_end:
+            aff_c = AFFINE.to_c()
+            full(aff_c)  # the diagonals: the affine best cell's, 3 off centre
+            torch.cuda.synchronize()
+            c = (b.pos.astype(np.int64) + ej.cpu().numpy() - ei.cpu().numpy() + 3)
+            c[score.cpu().numpy() <= 0] = UNPLACED
+            d_diag.copy_(up(c))
+            widths = [int(x) for x in args.widths.split(",")] if L <= 384 else [32]
+            for name, sc in (("linear score", LINEAR), ("affine + end cell", AFFINE)):
+                rec = {"case": case, "scheme": name, "reads": n, "rounds": args.rounds}
+                for w in widths:
+                    against_local(rec, sc.to_c(), w)
+                print(json.dumps(rec), flush=True)
+            if mr <= 1008:
+                rows = torch.zeros(n * args.stride, dtype=torch.int32, device=dev)
+                tr = TraceT(si.data_ptr(), sj.data_ptr(), nc.data_ptr(), rows.data_ptr(), args.stride)
+                rec = {"case": case, "scheme": "affine score + trace", "reads": n, "rounds": args.rounds}
+                against_local(rec, aff_c, 16, ctypes.byref(tr))
+                print(json.dumps(rec), flush=True)
+            continue
 
         for name, sc in (("linear score", LINEAR), ("affine + best cell", AFFINE)):
             sc_c, aff_c = sc.to_c(), AFFINE.to_c()
