@@ -162,6 +162,29 @@ void msw_gfastq_close(msw_gfastq* g);
 int msw_bgzf_inflate(msw_ctx* ctx, const uint8_t* data, uint64_t len, uint8_t* out, uint64_t cap,
                      uint64_t* out_len);
 
+/* BGZF deflate on the GPU: the bytes of data become a BGZF file, one gzip
+ * member with the 'BC' field and one DEFLATE block per MSW_BGZF_BLOCK input
+ * bytes (dynamic Huffman codes over a greedy LZ77 parse, or stored where that
+ * is not smaller), followed by the 28-byte EOF member unless flags says not.
+ * The same input gives the same bytes on every run. */
+#define MSW_BGZF_BLOCK 65280u
+#define MSW_BGZF_NO_EOF 1u            /* flags: do not append the EOF member */
+
+/* Bytes that always suffice for len input bytes (every block stored, plus EOF). */
+uint64_t msw_bgzf_deflate_bound(uint64_t len);
+
+/* data, out, out_len: device, data and out 4-byte aligned.  Enqueued on stream
+ * (NULL = the compute stream), no host synchronisation; scratch is allocated
+ * and freed in stream order, its size bounded by the context's inflate group
+ * size.  cap below the bound of len -> MSW_E_RANGE; unknown flag bits ->
+ * MSW_E_INVALID; len == 0 writes only the EOF member (or nothing). */
+int msw_bgzf_deflate_device(msw_ctx* ctx, const uint8_t* data, uint64_t len, uint8_t* out, uint64_t cap,
+                            uint64_t* out_len, uint32_t flags, void* stream);
+
+/* Host to host: the tool / test form of the same kernels. */
+int msw_bgzf_deflate(msw_ctx* ctx, const uint8_t* data, uint64_t len, uint8_t* out, uint64_t cap,
+                     uint64_t* out_len, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,5 +13,6 @@ from .aligner import (AFFINE, CallParams, PairParams, QualParams, Variants, GPU_
                       INS_SITE_DTYPE, SORT_TILE, E2E_NONE, ins_sequence)
 from .alnfile import (AlnBlock, Alignments, read_alignments, read_pileup, read_qsums, read_variants,  # noqa: F401
                       read_variants_qual, write_alignments, write_pileup, write_qsums, write_variants, write_vcf)
+from .fastq import bgzf_deflate, bgzf_inflate  # noqa: F401
 
 __version__ = "0.1.0"

@@ -56,7 +56,8 @@ EXPORTED = (
 FASTQ_EXPORTED = ("msw_fastq_open", "msw_fastq_close", "msw_fastq_next", "msw_fastq_next_packed",
                   "msw_fastq_stats", "msw_fastq_count_bases", "msw_is_bgzf", "msw_gfastq_open",
                   "msw_gfastq_next", "msw_gfastq_stats", "msw_gfastq_close", "msw_bgzf_inflate",
-                  "msw_gfastq_reset", "msw_gfastq_prefetch", "msw_gfastq_open_ex", "msw_gfastq_quals")
+                  "msw_gfastq_reset", "msw_gfastq_prefetch", "msw_gfastq_open_ex", "msw_gfastq_quals",
+                  "msw_bgzf_deflate_bound", "msw_bgzf_deflate_device", "msw_bgzf_deflate")
 
 
 class MswError(RuntimeError):
@@ -350,6 +351,10 @@ def _declare(L):
         "msw_gfastq_reset": (I, [P, ctypes.c_char_p]),
         "msw_gfastq_prefetch": (I, [P, ctypes.c_char_p]),
         "msw_bgzf_inflate": (I, [P, P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "msw_bgzf_deflate_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
+        "msw_bgzf_deflate_device": (I, [P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, ctypes.c_uint32, P]),
+        "msw_bgzf_deflate": (I, [P, P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                 ctypes.c_uint32]),
     }
     # the long-pair traceback calls take the argument lists of the calls they extend
     for name, base in (("msw_trace_long_batch_device", "msw_trace_batch_device"),

@@ -97,7 +97,9 @@ uint32_t multmodp(uint32_t a, uint32_t b) {
     return p;
 }
 
-msw::GzCrcConsts crc_consts() {
+}  // namespace
+
+msw::GzCrcConsts msw::gz_crc_consts() {
     msw::GzCrcConsts c;
     uint32_t p = 1u << 30;  // x^1
     c.x2n[0] = p;
@@ -106,6 +108,8 @@ msw::GzCrcConsts crc_consts() {
         for (uint32_t v = 0; v < 256; ++v) c.adv[i][v] = multmodp(c.x2n[11], v << (8 * i));  // x^2048
     return c;
 }
+
+namespace {
 
 // Size of the BGZF member whose 18-byte header is h, or 0 if h is not one.
 size_t member_size(const uint8_t* h) {
@@ -181,7 +185,7 @@ struct Inflater {
     int init() {
         GZ_TRY(hipMalloc((void**)&d_flag, 64));
         GZ_TRY(hipMalloc((void**)&d_crc, sizeof(msw::GzCrcConsts)));
-        const msw::GzCrcConsts c = crc_consts();
+        const msw::GzCrcConsts c = msw::gz_crc_consts();
         GZ_TRY(hipMemcpy(d_crc, &c, sizeof(c), hipMemcpyHostToDevice));
         GZ_TRY(hipHostMalloc((void**)&h_flag, 64, hipHostMallocDefault));
         return MSW_OK;

@@ -56,6 +56,34 @@ hipError_t launch_gz_inflate(const uint8_t* cdata, size_t cbytes, const GzMember
 // CRC-32 of every member's output against its trailer (one wave per member).
 hipError_t launch_gz_crc(const uint8_t* out, const GzMember* members, uint32_t n, const GzCrcConsts* consts,
                          uint32_t* status, uint32_t* any_error, hipStream_t stream);
+// The constants above (msw_gfastq.cpp).
+GzCrcConsts gz_crc_consts();
+
+// ---------------------------------------------------------------------------
+// BGZF deflate (msw_deflate.hip; the host side is msw_rt_deflate.cpp).  Input
+// block b is data[b * kDeflateBlock, ...); its member is built in slot b of
+// `slots` (kDeflateSlot bytes each, 4-byte aligned) and sizes[b] is its size.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDeflateBlock = 65280;  // input bytes per member (0xFF00)
+constexpr uint32_t kDeflateSlot = 65536;   // a member is never larger
+// One wave per block, `waves` of them looping over the blocks; data 4-byte
+// aligned.  tokens: kDeflateBlock words per wave.  sizes: nblocks + 1 words,
+// the last one set to 0 for the scan.  Everything of a member but its CRC-32.
+hipError_t launch_gz_deflate(const uint8_t* data, uint64_t len, uint32_t nblocks, uint32_t waves, uint8_t* slots,
+                             uint32_t* sizes, uint32_t* tokens, hipStream_t stream);
+// The CRC-32 of every block into its member's trailer (msw_inflate.hip: the
+// CRC kernel of the inflate, writing instead of comparing).
+hipError_t launch_gz_crc_put(const uint8_t* data, uint64_t len, uint32_t block, uint32_t n, const GzCrcConsts* consts,
+                             uint8_t* slots, uint32_t slot_bytes, const uint32_t* sizes, hipStream_t stream);
+// off = the exclusive scan of sizes: the members back to back at out + *base
+// (base NULL = 0).
+hipError_t launch_gz_gather(const uint8_t* slots, const uint32_t* off, uint32_t nblocks, const uint64_t* base,
+                            uint8_t* out, hipStream_t stream);
+// *base (taken as 0 when first) += *total (NULL = 0); when last, the EOF
+// member unless flags has bit 0, and *out_len.
+hipError_t launch_gz_finish(const uint32_t* total, uint64_t* base, bool first, bool last, uint32_t flags, uint8_t* out,
+                            uint64_t* out_len, hipStream_t stream);
+
 // Load the inflate / CRC and the parse / emit code objects now (a reader's
 // setup) instead of at their first launch, which sat inside the first span.
 hipError_t gz_preload();

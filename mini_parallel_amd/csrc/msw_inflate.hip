@@ -1021,24 +1021,11 @@ __device__ uint32_t x2nmodp(const GzCrcConsts& c, uint64_t n, uint32_t k) {  // 
 // raw(X || Y) = raw(X) * x^(8|Y|) ^ raw(Y)   (zlib crc32_combine).
 constexpr uint32_t kCrcMembersPerBlock = 4;
 
-__global__ __launch_bounds__(256) void gz_crc_kernel(const uint8_t* __restrict__ out,
-                                                     const GzMember* __restrict__ members, uint32_t n,
-                                                     const GzCrcConsts* __restrict__ consts,
-                                                     uint32_t* __restrict__ status, uint32_t* __restrict__ any_error) {
-    __shared__ uint32_t A[4][256];
-    for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) (&A[0][0])[i] = (&consts->adv[0][0])[i];
-    __syncthreads();
-    const uint32_t m = blockIdx.x * kCrcMembersPerBlock + (threadIdx.x >> 6);
-    if (m >= n || status[m] != GZ_OK) return;  // no barrier below; failed members stay failed
-    const uint32_t lane = threadIdx.x & 63;
-    const GzMember mem = members[m];
-    if (mem.isize == 0) {
-        if (lane == 0 && mem.crc != 0) {
-            status[m] = GZ_E_CRC;
-            atomicOr(any_error, 1u);
-        }
-        return;
-    }
+// CRC-32 of out[ooff, ooff + isize), isize > 0, by one wave; A = the advance
+// tables in LDS.  The result is lane 0's.
+__device__ __forceinline__ uint32_t wave_crc(const uint8_t* __restrict__ out, const GzMember& mem,
+                                             const uint32_t (*A)[256], const GzCrcConsts* __restrict__ consts,
+                                             uint32_t lane) {
     const uint32_t chunks = (mem.isize + 255) >> 8;
     const uint64_t end = mem.ooff + mem.isize;
     // dword q of chunk k starts at byte end - 256 (chunks - k) + 4 lane
@@ -1081,13 +1068,55 @@ __global__ __launch_bounds__(256) void gz_crc_kernel(const uint8_t* __restrict__
         const uint32_t right = __shfl_down(c, step);
         if ((lane & (2 * step - 1)) == 0) c = multmodp(consts->x2n[5 + lv], c) ^ right;
     }
-    if (lane == 0) {
-        c = multmodp(consts->x2n[5], c);  // lane 0's state is aligned to its dword's start: 4 more bytes
-        // standard CRC: pre-condition 0xFFFFFFFF shifted over the data, post-xor
-        const uint32_t crc = c ^ multmodp(x2nmodp(*consts, mem.isize, 3), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
-        if (crc != mem.crc) {
+    c = multmodp(consts->x2n[5], c);  // lane 0's state is aligned to its dword's start: 4 more bytes
+    // standard CRC: pre-condition 0xFFFFFFFF shifted over the data, post-xor
+    return c ^ multmodp(x2nmodp(*consts, mem.isize, 3), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(256) void gz_crc_kernel(const uint8_t* __restrict__ out,
+                                                     const GzMember* __restrict__ members, uint32_t n,
+                                                     const GzCrcConsts* __restrict__ consts,
+                                                     uint32_t* __restrict__ status, uint32_t* __restrict__ any_error) {
+    __shared__ uint32_t A[4][256];
+    for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) (&A[0][0])[i] = (&consts->adv[0][0])[i];
+    __syncthreads();
+    const uint32_t m = blockIdx.x * kCrcMembersPerBlock + (threadIdx.x >> 6);
+    if (m >= n || status[m] != GZ_OK) return;  // no barrier below; failed members stay failed
+    const uint32_t lane = threadIdx.x & 63;
+    const GzMember mem = members[m];
+    if (mem.isize == 0) {
+        if (lane == 0 && mem.crc != 0) {
             status[m] = GZ_E_CRC;
             atomicOr(any_error, 1u);
+        }
+        return;
+    }
+    const uint32_t crc = wave_crc(out, mem, A, consts, lane);
+    if (lane == 0 && crc != mem.crc) {
+        status[m] = GZ_E_CRC;
+        atomicOr(any_error, 1u);
+    }
+}
+
+// The same CRC written instead of compared: block b of the deflate's input is
+// data[b * block, ...), and its member lies in slot b with sizes[b] bytes, the
+// CRC-32 eight bytes before its end (msw_deflate.hip writes the rest).
+__global__ __launch_bounds__(256) void gz_crc_put_kernel(const uint8_t* __restrict__ data, uint64_t len, uint32_t block,
+                                                         uint32_t n, const GzCrcConsts* __restrict__ consts,
+                                                         uint8_t* __restrict__ slots, uint32_t slot_bytes,
+                                                         const uint32_t* __restrict__ sizes) {
+    __shared__ uint32_t A[4][256];
+    for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) (&A[0][0])[i] = (&consts->adv[0][0])[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t b = blockIdx.x * kCrcMembersPerBlock + (threadIdx.x >> 6); b < n; b += gridDim.x * kCrcMembersPerBlock) {
+        GzMember mem;
+        mem.ooff = (uint64_t)b * block;
+        mem.isize = (uint32_t)min((uint64_t)block, len - mem.ooff);
+        const uint32_t crc = wave_crc(data, mem, A, consts, lane);
+        if (lane == 0) {
+            uint8_t* t = slots + (uint64_t)b * slot_bytes + sizes[b] - 8;
+            for (int k = 0; k < 4; ++k) t[k] = (uint8_t)(crc >> (8 * k));
         }
     }
 }
@@ -1109,6 +1138,15 @@ hipError_t launch_gz_inflate(const uint8_t* cdata, size_t cbytes, const GzMember
 hipError_t gz_preload() {
     int nb = 0;  // an occupancy query loads the kernel's code object (msw_ctx_prepare does the same)
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gz_crc_kernel, 256, 0);
+}
+
+hipError_t launch_gz_crc_put(const uint8_t* data, uint64_t len, uint32_t block, uint32_t n, const GzCrcConsts* consts,
+                             uint8_t* slots, uint32_t slot_bytes, const uint32_t* sizes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = std::min<uint32_t>((n + kCrcMembersPerBlock - 1) / kCrcMembersPerBlock, 1u << 16);
+    hipLaunchKernelGGL(gz_crc_put_kernel, dim3(blocks), dim3(256), 0, stream, data, len, block, n, consts, slots,
+                       slot_bytes, sizes);
+    return hipGetLastError();
 }
 
 hipError_t launch_gz_crc(const uint8_t* out, const GzMember* members, uint32_t n, const GzCrcConsts* consts,

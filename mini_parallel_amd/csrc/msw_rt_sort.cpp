@@ -16,25 +16,6 @@ uint32_t bit_length(uint64_t v) {
     return b;
 }
 
-// Temporaries of one call on `st`: allocated before its launches, freed behind them.
-struct StreamTmp {
-    void* p = nullptr;
-    hipStream_t st;
-    explicit StreamTmp(hipStream_t s) : st(s) {}
-    StreamTmp(const StreamTmp&) = delete;
-    StreamTmp& operator=(const StreamTmp&) = delete;
-    ~StreamTmp() {
-        if (p) (void)hipFreeAsync(p, st);
-    }
-    int alloc(uint64_t bytes) {
-        const hipError_t e = hipMallocAsync(&p, bytes + DeviceArena::kTail, st);
-        if (e == hipSuccess) return MSW_OK;
-        p = nullptr;
-        (void)hipGetLastError();
-        return fail(MSW_E_NOMEM, "hipMallocAsync(%llu B): %s", (unsigned long long)bytes, hipGetErrorString(e));
-    }
-};
-
 int check_markdup(msw_ctx* ctx, const msw_aln_t* aln, const int32_t* score, uint64_t n_rows, uint64_t ref_len,
                   int pairs, const uint32_t* order, const uint8_t* dup) {
     if (!ctx) return fail(MSW_E_INVALID, "ctx is NULL");

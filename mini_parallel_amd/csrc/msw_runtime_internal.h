@@ -6,6 +6,7 @@
 //   msw_rt_pileup.cpp  pileup, variant calls
 //   msw_rt_band.cpp    banded alignment
 //   msw_rt_sort.cpp    sorting and duplicates
+//   msw_rt_deflate.cpp BGZF deflate (include/msw_fastq.h)
 // Each section of include/msw.h is implemented in one of them; nothing but
 // this header is shared between them.  Not installed, not part of the C ABI.
 #pragma once
@@ -289,6 +290,25 @@ public:
 private:
     uint8_t* base_ = nullptr;
     size_t bytes_ = 0;
+};
+
+// Temporaries of one call on `st`: allocated before its launches, freed behind them.
+struct StreamTmp {
+    void* p = nullptr;
+    hipStream_t st;
+    explicit StreamTmp(hipStream_t s) : st(s) {}
+    StreamTmp(const StreamTmp&) = delete;
+    StreamTmp& operator=(const StreamTmp&) = delete;
+    ~StreamTmp() {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+    int alloc(uint64_t bytes) {
+        const hipError_t e = hipMallocAsync(&p, bytes + DeviceArena::kTail, st);
+        if (e == hipSuccess) return MSW_OK;
+        p = nullptr;
+        (void)hipGetLastError();
+        return fail(MSW_E_NOMEM, "hipMallocAsync(%llu B): %s", (unsigned long long)bytes, hipGetErrorString(e));
+    }
 };
 
 // The copies of a chunked driver on one stream, with a sticky error: after a

@@ -202,6 +202,22 @@ def bgzf_inflate(ctx, data: bytes) -> bytes:
     return out[:n.value].tobytes()
 
 
+BGZF_NO_EOF = 1  # MSW_BGZF_NO_EOF
+
+
+def bgzf_deflate(ctx, data: bytes, eof: bool = True) -> bytes:
+    """msw_bgzf_deflate: ``data`` as a BGZF file compressed on the GPU (host to
+    host), one member per 65,280 bytes, then the EOF member unless ``eof`` is
+    false."""
+    src = np.frombuffer(data, np.uint8)
+    cap = lib().msw_bgzf_deflate_bound(len(data))
+    out = np.zeros(cap, np.uint8)
+    n = ctypes.c_uint64()
+    check(lib().msw_bgzf_deflate(ctx.handle, src.ctypes.data if len(src) else None, len(data), out.ctypes.data,
+                                 cap, ctypes.byref(n), 0 if eof else BGZF_NO_EOF))
+    return out[:n.value].tobytes()
+
+
 def process_fastq_file_in_chunks(filepath: str, chunk_size_reads: int,
                                  processor: Callable[[list], Optional[object]]) -> None:
     """aligner.rs:107-178: call ``processor`` with lists of sequence strings
